@@ -11,9 +11,14 @@ m=30 000 000 fragments (~240 M nnz), on one MI355X.  N>1: one such sample per GP
 independently (samples shard one-per-GPU, no data-path collective: "scaling": "weak");
 value = total VI iterations of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with `roofline` (sparse likelihood kernel vs HBM) and, at N=1,
-`cpu_baseline` (the CPU oracle -- a port keeping the reference's loop structure -- timed on
-this box's host cores on a bounded sample of the same workload).
+Prints ONE JSON line (rank 0) with `roofline` (sparse likelihood kernel vs HBM, from the timed run's own HIP
+events).  A plain run does only what that line needs; `--full` adds the measurements that take runs of their own:
+`roofline.by_input` (the same measurement on other inputs), at N=1 `cpu_baseline` (the CPU oracle -- a port keeping
+the reference's loop structure -- timed on the host's cores on a bounded sample of the same workload), and at
+N>1 the all-reduce's own time.  `--dump-outputs DIR` writes what the timed path computed (the fitted parameters) as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.  The default
+float-atomic gradient sums differ in their last bits from run to run, and the steps can carry that further in a few
+parameters; `--deterministic` makes repeated runs bitwise equal.
 """
 import argparse
 import json
@@ -43,6 +48,7 @@ WORKLOADS = {
     "c4": (200000, 8, 2),
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+MAX_DUMP_BYTES = 60 << 20  # --dump-outputs: arrays of at most 64 MB in all, .npy headers and rounding included
 
 
 def algorithmic_bytes_per_pass(nnz, m, n, K):
@@ -72,6 +78,21 @@ def emit(out):
     except Exception:
         pass
     print(json.dumps(out), flush=True)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path hands its caller, as <path>/<name>.npy in f32 (f64 where the path
+    computes f64).  Above MAX_DUMP_BYTES in all, every array is cut to a fixed seeded sample of its (flattened) elements,
+    the same positions in every run of the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > MAX_DUMP_BYTES:
+            keep = max(1, a.size * MAX_DUMP_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def launch_ranks(args):
@@ -208,11 +229,14 @@ def regression_bench(args):
     reg.fit(max(args.warmup, 1), seed=args.seed)
     barrier()
     t0 = time.perf_counter()
-    trace = reg.fit(args.steps, seed=args.seed, return_trace=True)[-1]  # synchronises before returning
+    res = reg.fit(args.steps, seed=args.seed, return_trace=True)  # synchronises before returning
     barrier()
     elapsed = ranks.max(time.perf_counter() - t0)
+    trace = res[-1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("qx_loc", "qw_loc", "qw_scale", "qx_bias_loc", "qx_scale", "loss"), res)))
     ar = None
-    if comm is not None:  # (the first N > 1 run describes itself: the exchange's own HIP-event time on every rank)
+    if comm is not None and args.full:  # (the first N > 1 run describes itself: the exchange's own HIP-event time on every rank)
         ar = {"count_f32": (F + 2) * n, "ms_avg_per_rank": ranks.gather(comm.allreduce_ms((F + 2) * n)),
               "what": "one all-reduce of (F+2) n f32 on the model's stream between two HIP events, mean of 20 calls behind an untimed first one"}
     if rank == 0:
@@ -327,7 +351,7 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("POLEE_BENCH_WORKLOAD", "c2"), choices=sorted(WORKLOADS))
     ap.add_argument("--draws", type=int, default=6, help="MC draws per VI iteration (LIKAP_NUM_MC_SAMPLES)")
     ap.add_argument("--tree", default="hclust", choices=["hclust", "balanced", "spine"])
-    ap.add_argument("--cpu-steps", type=int, default=5, help="VI iterations timed for the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-steps", type=int, default=5, help="VI iterations timed for the CPU baseline of --full (0 = skip)")
     ap.add_argument("--seed", type=int, default=123456789)
     ap.add_argument("--row-shard", action="store_true",
                     help="ONE sample for the whole job: its fragments are sharded over the GPUs and the likelihood "
@@ -352,12 +376,17 @@ def main():
                          "exon structure induces in real data: few distinct sets per gene); reported under roofline.by_input")
     ap.add_argument("--literal-subsets", action="store_true", help="(kept for scripts) same as --generator literal")
     ap.add_argument("--no-by-input", action="store_true",
-                    help="skip the two extra inputs of roofline.by_input (the other generator and the tiled real fixture)")
+                    help="with --full: skip the extra inputs of roofline.by_input (the other generator and the tiled real fixture)")
     ap.add_argument("--profile-every", type=int, default=4, metavar="N",
                     help="bracket every N-th sparse pass of the timed region with HIP events (the roofline's kernel time); "
                          "bracketing every pass puts ~20 us of gaps into each C2 iteration (profiles/r05_event_gaps.txt)")
     ap.add_argument("--samples-per-gpu", type=int, default=1,
                     help="fits run concurrently on one GPU, each on its own stream (cohort mode; the headline uses 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements the headline does not need: roofline.by_input (C2), the CPU baseline "
+                         "(N = 1) and the all-reduce's own time (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the fitted parameters) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.literal_subsets:
         args.generator = "literal"
@@ -462,6 +491,10 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t_start
     st1 = fit.stats()
+    if args.dump_outputs and rank == 0:  # (fit 0's parameters; with S > 1 every fit's, stacked)
+        params = [f.params() for f in fits]
+        dump_outputs(args.dump_outputs, {k: params[0][i] if S == 1 else np.stack([p[i] for p in params])
+                                         for i, k in enumerate(("mu", "omega", "alpha"))})
 
     elapsed = ranks.max(elapsed)  # slowest rank
 
@@ -531,7 +564,7 @@ def main():
     if world > 1:  # the first N > 1 run describes itself: every rank's kernel time, and the exchange's own time
         out["detail"]["kernel_ms_avg_per_rank"] = ranks.gather(roof["kernel_ms_avg"])
         out["detail"]["pass_ms_avg_per_rank"] = ranks.gather(roof["pass_ms_avg"])
-        if comm is not None:
+        if comm is not None and args.full:
             ar = comm.allreduce_ms(n * K)
             out["detail"]["allreduce"] = {"count_f32": n * K, "ms_avg_per_rank": ranks.gather(ar), "what": "one all-reduce of K*n f32 on the fit's stream "
                                           "between two HIP events, mean of 20 calls behind an untimed first one", "comm": comm.info()}
@@ -543,9 +576,9 @@ def main():
     roof["by_input"] = {input_name: main_entry}
 
     cpu_inputs = None
-    if rank == 0 and world == 1 and args.cpu_steps > 0 and S == 1:
+    if args.full and rank == 0 and world == 1 and args.cpu_steps > 0 and S == 1:
         cpu_inputs = (smp, parents, js)
-    by_input_wanted = (rank == 0 and world == 1 and S == 1 and not args.row_shard and not args.no_by_input
+    by_input_wanted = (args.full and rank == 0 and world == 1 and S == 1 and not args.row_shard and not args.no_by_input
                        and args.workload == "c2" and not args.set_diversity)
     if by_input_wanted:
         # The same measurement on the inputs the headline's generator is not: the other generator at the same size, and

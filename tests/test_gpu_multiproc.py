@@ -51,7 +51,7 @@ def _hooks():
 
 
 def test_bench_row_shard_two_ranks():
-    d = _bench(["--gpus", "2", "--workload", "c1", "--steps", "20", "--warmup", "3", "--row-shard"], **_hooks())
+    d = _bench(["--gpus", "2", "--workload", "c1", "--steps", "20", "--warmup", "3", "--row-shard", "--full"], **_hooks())
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
     # the first N > 1 run describes itself: determinism on by default, the build, every rank's kernel time, the exchange's time
     assert d["config"]["deterministic"] is True and "hipcc" in d["detail"]["build"]
@@ -62,7 +62,7 @@ def test_bench_row_shard_two_ranks():
 
 
 def test_bench_regression_two_ranks():
-    d = _bench(["--gpus", "2", "--workload", "c3", "--steps", "20", "--warmup", "3"], **_hooks())
+    d = _bench(["--gpus", "2", "--workload", "c3", "--steps", "20", "--warmup", "3", "--full"], **_hooks())
     assert d["n_gpus"] == 2 and d["detail"]["finite"]
     assert "hipcc" in d["detail"]["build"] and len(d["detail"]["allreduce"]["ms_avg_per_rank"]) == 2
 

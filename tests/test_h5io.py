@@ -1,5 +1,5 @@
 """On-disk contracts (prep / likelihood-matrix HDF5) through polee_amd.h5io: round trips, the reference's own
-fixture files when the reference tree is mounted (build container only), and the model-entry loader."""
+fixture files (tests/golden), and the model-entry loader."""
 import os
 
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 
 from polee_amd import h5io
 
-REF = "/root/reference/test/dataset"
+from conftest import GOLDEN
 
 try:
     h5io.lib()
@@ -47,14 +47,13 @@ def test_prepared_sample_roundtrip_and_version_check(tmp_path, prep_fixture):
         h5io.check_prepared_sample_version(f, bad)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_reads_the_reference_fixture_files(lm_fixture, prep_fixture):
     """The files the reference itself wrote are read identically to the h5dump-converted npz fixtures."""
-    r = h5io.read_likelihood_matrix(os.path.join(REF, "mBr_M_6w_1.likelihood-matrix.h5"))
+    r = h5io.read_likelihood_matrix(os.path.join(GOLDEN, "mBr_M_6w_1.likelihood-matrix.h5"))
     assert r["m"] == lm_fixture["m"] and r["n"] == lm_fixture["n"]
     for k in ("colptr", "rowval", "nzval", "effective_lengths"):
         np.testing.assert_array_equal(r[k], lm_fixture[k])
-    p = h5io.read_prepared_sample(os.path.join(REF, "mBr_M_6w_1.prep.h5"))
+    p = h5io.read_prepared_sample(os.path.join(GOLDEN, "mBr_M_6w_1.prep.h5"))
     for k in ("mu", "omega", "alpha", "node_parent_idxs", "node_js", "effective_lengths"):
         np.testing.assert_array_equal(p[k], prep_fixture[k])
     assert p["metadata"]["version"] == 2 and p["metadata"]["gfffilename"] == "annotations.gff3"

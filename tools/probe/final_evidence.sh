@@ -6,7 +6,7 @@ mkdir -p $O
 cd $GRAFT_REPO_ROOT
 tools/profile.sh $R > $O/profile.log 2>&1
 cd $GRAFT_REPO_ROOT
-python3 bench.py --steps 20 --warmup 5 2> $O/bench_c2.err | tail -1 > $O/bench_c2.json
+python3 bench.py --steps 20 --warmup 5 --full 2> $O/bench_c2.err | tail -1 > $O/bench_c2.json
 python3 bench.py --steps 500 --warmup 5 --cpu-steps 0 2>/dev/null | tail -1 > $O/bench_c2_500.json
 python3 bench.py --steps 20 --warmup 5 --cpu-steps 0 --deterministic 2>/dev/null | tail -1 > $O/bench_c2_det.json
 python3 bench.py --workload c5 --steps 20 --warmup 3 --cpu-steps 0 2>/dev/null | tail -1 > $O/bench_c5.json

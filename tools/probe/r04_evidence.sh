@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 TAG=${1:-r04}
 OUT=gpurun_out/evidence_$TAG; mkdir -p $OUT
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err; tail -1 $OUT/bench_c2.json | cut -c1-600
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err; tail -1 $OUT/bench_c2.json | cut -c1-600
 python3 bench.py --steps 500 --warmup 5 --cpu-steps 0 --no-by-input > $OUT/bench_c2_500.json 2> $OUT/bench_c2_500.err
 python3 bench.py --steps 20 --warmup 5 --cpu-steps 0 --no-by-input --deterministic > $OUT/bench_c2_det.json 2> $OUT/bench_c2_det.err
 python3 bench.py --workload c5 --steps 20 --warmup 5 --cpu-steps 0 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
