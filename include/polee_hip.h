@@ -667,6 +667,50 @@ polee_status polee_loglik_create_from_xbuild(polee_ctx *ctx, const polee_xbuild 
  * without X visiting the host (the columns of X by a stable sort of the result's rows by transcript). */
 polee_status polee_hclust_parallel_device_from_xbuild(polee_ctx *ctx, const polee_xbuild *xb, int32_t *node_parent_idxs, int32_t *node_js);
 
+/* ---- Gibbs sampler of the exact posterior (src/gibbs.jl; `polee debug-sample`, src/main.jl:925-957) -----------------------------
+ * Collapsed Gibbs sampling over fragment assignments: draws of the transcript mixture from p(y | X) under a Dirichlet(1) prior,
+ * num_chains (1..32) chains at once (csrc/gibbs.hip).  X as polee_loglik_create takes it (or fragment-major, _from_xt:
+ * the same layout); efflens_or_null: effective lengths (> 0), NULL = --no-efflen.  Every chain starts from Gamma(1) draws of its own.
+ * A sweep = one assignment of every fragment + one draw of the mixture, two kernel launches; polee_gibbs_run only queues them.
+ * Randomness: Philox4x32-10 keyed by (seed, sweep, chain, original fragment / transcript), sweeps numbered 1, 2, ... from creation:
+ * a chain's draws depend on (X, seed, chain index) only -- not on the number of chains -- and are bitwise reproducible. */
+typedef struct polee_gibbs polee_gibbs;
+polee_status polee_gibbs_create(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes, const uint32_t *rowval,
+                                const float *nzval, const float *efflens_or_null, int32_t num_chains, uint64_t seed, polee_gibbs **out);
+/* X given fragment-major (tcolptr [m+1] uint64 1-based, trowval 1-based: polee_loglik_create_from_xt's arguments) */
+polee_status polee_gibbs_create_from_xt(polee_ctx *ctx, int64_t m, int64_t n, const uint64_t *tcolptr, const uint32_t *trowval,
+                                        const float *tnzval, const float *efflens_or_null, int32_t num_chains, uint64_t seed,
+                                        polee_gibbs **out);
+void polee_gibbs_destroy(polee_gibbs *g);
+/* the chains' mixture state, unnormalised: g0 f32 [C][n] (finite, >= 0), or NULL = fresh Gamma(1) draws */
+polee_status polee_gibbs_set_state(polee_gibbs *g, const float *g0_or_null);
+/* room for draws_per_chain stored draws per chain (f32 [C][draws][n] on the device); empties the store */
+polee_status polee_gibbs_reserve(polee_gibbs *g, int32_t draws_per_chain);
+/* nsweeps sweeps; stride > 0: the state after every stride-th sweep is stored (x_j = (g_j / l_j) / sum_k g_k / l_k), counted
+ * across calls with the same stride; stride 0 = burn-in, nothing stored.  Asynchronous: polee_gibbs_sync waits. */
+polee_status polee_gibbs_run(polee_gibbs *g, int32_t nsweeps, int32_t stride);
+/* waits for the queued sweeps; POLEE_ERR_NONFINITE if a mixture draw was not finite and positive */
+polee_status polee_gibbs_sync(polee_gibbs *g);
+polee_status polee_gibbs_num_stored(const polee_gibbs *g, int32_t *draws_per_chain);
+/* stored draws [first, first + count) of every chain -> out f32 [C][count][n] */
+polee_status polee_gibbs_get_draws(polee_gibbs *g, int32_t first, int32_t count, float *out);
+/* fragments per transcript in the last sweep, single-transcript fragments included -> counts u32 [C][n] */
+polee_status polee_gibbs_get_counts(polee_gibbs *g, uint32_t *counts);
+/* split-R-hat per transcript over all stored draws (convergence_stats, gibbs.jl:283-319) -> rhat f32 [n] */
+polee_status polee_gibbs_rhat(polee_gibbs *g, float *rhat);
+typedef struct {
+    int64_t m, n, nnz;
+    int32_t num_chains;
+    int64_t num_multi_rows;   /* fragments sampled every sweep (two or more compatible transcripts)          */
+    int64_t num_single_rows;  /* fragments with one compatible transcript: a constant count per transcript     */
+    int64_t num_empty_rows;   /* fragments with none: dropped (gibbs.jl:202-211 never counts them)            */
+    int64_t multi_nnz;        /* non-zeros a sweep reads                                                      */
+    int64_t num_tiles;        /* workgroups of the assignment kernel                                          */
+    int32_t rows_per_tile;
+    int64_t sweeps_done;      /* sweeps run since creation (the next sweep is number sweeps_done + 1)         */
+} polee_gibbs_info;
+polee_status polee_gibbs_get_info(const polee_gibbs *g, polee_gibbs_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,10 @@ polee_status polee_debug_fast_log(polee_ctx *ctx, const double *x, int64_t count
 /* fast_exp (csrc/scan.hpp), the double-precision exp of the VI loop's forward kernel (leaf u = exp of a path sum of edge logs) */
 polee_status polee_debug_fast_exp(polee_ctx *ctx, const double *x, int64_t count, double *out);
 
+/* The Gibbs sampler's last sweep, chain `chain`: z i32 [m] = the 1-based transcript each fragment was assigned (original fragment
+ * order; 0 = a fragment with no compatible transcript).  Recomputed by the assignment kernel on the state that sweep started from. */
+polee_status polee_debug_gibbs_assignments(polee_gibbs *g, int32_t chain, int32_t *z);
+
 #ifdef __cplusplus
 }
 #endif

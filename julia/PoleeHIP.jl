@@ -1028,4 +1028,94 @@ function debug_fast_log(ctx::Context, x::Vector{Float64})
     return out
 end
 
+# ---- Gibbs sampler of the exact posterior (src/gibbs.jl; `polee debug-sample`, main.jl:925-957) -------------------------------
+mutable struct GibbsSampler
+    h::Ptr{Cvoid}
+    ctx::Context
+    n::Int
+    num_chains::Int
+end
+
+struct GibbsInfo
+    m::Int64; n::Int64; nnz::Int64
+    num_chains::Int32
+    num_multi_rows::Int64; num_single_rows::Int64; num_empty_rows::Int64; multi_nnz::Int64; num_tiles::Int64
+    rows_per_tile::Int32
+    sweeps_done::Int64
+end
+
+function wrap_gibbs(r::Ref{Ptr{Cvoid}}, ctx::Context, n, num_chains)
+    g = GibbsSampler(r[], ctx, Int(n), Int(num_chains))
+    finalizer(x -> ccall((:polee_gibbs_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), g)
+    return g
+end
+
+"X by columns exactly as RNASeqSample holds it (colptr, rowval 1-based); efflens === nothing = --no-efflen"
+function GibbsSampler(ctx::Context, m::Integer, n::Integer, colptr::Vector{UInt32}, rowval::Vector{UInt32}, nzval::Vector{Float32},
+                      efflens::Union{Nothing,Vector{Float32}}, num_chains::Integer, seed::Integer)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve colptr rowval nzval efflens check(
+        ccall((:polee_gibbs_create, LIB), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{UInt32}, Ptr{Float32}, Ptr{Float32}, Int32, UInt64, Ref{Ptr{Cvoid}}),
+              ctx.h, m, n, colptr, 4, rowval, nzval, efflens === nothing ? C_NULL : pointer(efflens), num_chains, UInt64(seed), r), ctx.h)
+    return wrap_gibbs(r, ctx, n, num_chains)
+end
+
+"X given fragment-major (Xt = SparseMatrixCSC(transpose(X)), as gibbs.jl:26 builds it)"
+function gibbs_sampler_from_xt(ctx::Context, m::Integer, n::Integer, tcolptr::Vector{UInt64}, trowval::Vector{UInt32},
+                               tnzval::Vector{Float32}, efflens::Union{Nothing,Vector{Float32}}, num_chains::Integer, seed::Integer)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve tcolptr trowval tnzval efflens check(
+        ccall((:polee_gibbs_create_from_xt, LIB), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Ptr{UInt64}, Ptr{UInt32}, Ptr{Float32}, Ptr{Float32}, Int32, UInt64, Ref{Ptr{Cvoid}}),
+              ctx.h, m, n, tcolptr, trowval, tnzval, efflens === nothing ? C_NULL : pointer(efflens), num_chains, UInt64(seed), r), ctx.h)
+    return wrap_gibbs(r, ctx, n, num_chains)
+end
+
+"g0: [n, C] (column c = chain c's unnormalised mixture), or nothing = fresh Gamma(1) draws"
+function set_state!(g::GibbsSampler, g0::Union{Nothing,Matrix{Float32}})
+    GC.@preserve g0 check(ccall((:polee_gibbs_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), g.h,
+                                g0 === nothing ? C_NULL : pointer(g0)), g.ctx.h)
+end
+reserve!(g::GibbsSampler, draws_per_chain::Integer) =
+    check(ccall((:polee_gibbs_reserve, LIB), Cint, (Ptr{Cvoid}, Int32), g.h, draws_per_chain), g.ctx.h)
+"nsweeps sweeps; stride > 0 stores every stride-th state, 0 = burn-in"
+run!(g::GibbsSampler, nsweeps::Integer, stride::Integer=0) =
+    check(ccall((:polee_gibbs_run, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), g.h, nsweeps, stride), g.ctx.h)
+sync!(g::GibbsSampler) = check(ccall((:polee_gibbs_sync, LIB), Cint, (Ptr{Cvoid},), g.h), g.ctx.h)
+function num_stored(g::GibbsSampler)
+    k = Ref{Int32}(0)
+    check(ccall((:polee_gibbs_num_stored, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), g.h, k), g.ctx.h)
+    return Int(k[])
+end
+"stored draws first+1 .. first+count: [n, count, C] (the samples array of gibbs.jl:71, dimensions reversed)"
+function get_draws(g::GibbsSampler, first::Integer=0, count::Integer=num_stored(g) - first)
+    out = Array{Float32}(undef, g.n, count, g.num_chains)
+    GC.@preserve out check(ccall((:polee_gibbs_get_draws, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float32}),
+                                 g.h, first, count, out), g.ctx.h)
+    return out
+end
+function get_counts(g::GibbsSampler)
+    out = Matrix{UInt32}(undef, g.n, g.num_chains)
+    GC.@preserve out check(ccall((:polee_gibbs_get_counts, LIB), Cint, (Ptr{Cvoid}, Ptr{UInt32}), g.h, out), g.ctx.h)
+    return out
+end
+"split-R-hat per transcript over all stored draws (convergence_stats, gibbs.jl:283-319)"
+function rhat(g::GibbsSampler)
+    out = Vector{Float32}(undef, g.n)
+    GC.@preserve out check(ccall((:polee_gibbs_rhat, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), g.h, out), g.ctx.h)
+    return out
+end
+function info(g::GibbsSampler)
+    i = Ref{GibbsInfo}()
+    check(ccall((:polee_gibbs_get_info, LIB), Cint, (Ptr{Cvoid}, Ref{GibbsInfo}), g.h, i), g.ctx.h)
+    return i[]
+end
+"test hook: the 1-based transcript the last sweep gave each fragment, chain `chain` (0-based), 0 = empty fragment"
+function debug_gibbs_assignments(g::GibbsSampler, chain::Integer, m::Integer)
+    z = Vector{Int32}(undef, m)
+    GC.@preserve z check(ccall((:polee_debug_gibbs_assignments, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), g.h, chain, z), g.ctx.h)
+    return z
+end
+
 end # module

@@ -13,6 +13,7 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   RNASeqApproxLikelihood(...).log_prob, rnaseq_approx_likelihood_sampler     src/polee_approx_likelihood.py
   RNASeqLinearRegression / RNASeqTranscriptLinearRegression(...).fit         models/polee_regression.py
   build_likelihood_matrix (X from alignments, SimplisticFragModel)           src/rnaseq_sample.jl:58-121, src/fragmodel.jl
+  gibbs_sampler / GibbsSampler (`polee debug-sample`)                        src/gibbs.jl, src/main.jl:925-957
 
 All numerics run in libpolee_hip.so on the GPU; nothing here computes on the CPU.
 """
@@ -33,3 +34,11 @@ from .regression import (RNASeqLinearRegression, RNASeqTranscriptLinearRegressio
 from .salmon import load_salmon_likelihood, SalmonLikelihood  # noqa: F401,E402
 from .cohort import approximate_likelihood_cohort, approximate_likelihood_cohort_processes  # noqa: F401,E402
 from .xbuild import build_likelihood_matrix  # noqa: F401,E402
+
+
+def __getattr__(name):
+    # (imported on first use: `python -m polee_amd.gibbs` must not find the module already imported by the package)
+    if name in ("GibbsSampler", "gibbs_sampler"):
+        from . import gibbs
+        return getattr(gibbs, name)
+    raise AttributeError("module 'polee_amd' has no attribute %r" % name)

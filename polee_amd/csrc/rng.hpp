@@ -51,4 +51,19 @@ __device__ inline float philox_randn(uint64_t seed, uint32_t step, uint32_t draw
     return z[draw & 3];
 }
 
+// One Philox4x32-10 block of a caller-chosen counter under the key `seed` (the Gibbs sampler, gibbs.hip; counter layout in
+// DESIGN.md §3.7), and the 24-bit uniform in (0,1) that philox_randn4 uses, exact in f32 and f64.
+__host__ __device__ inline void philox4x32_10(uint32_t (&c)[4], uint64_t seed)
+{
+    uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, key);
+        key[0] += 0x9E3779B9u;
+        key[1] += 0xBB67AE85u;
+    }
+}
+__host__ __device__ inline float philox_u01f(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+__host__ __device__ inline double philox_u01d(uint32_t w) { return ((double)(w >> 8) + 0.5) * (1.0 / 16777216.0); }
+
 }  // namespace polee

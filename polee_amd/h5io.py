@@ -24,6 +24,7 @@ H5S_SCALAR, H5S_ALL = 0, 0
 H5T_CSET_UTF8 = 1
 H5T_INTEGER, H5T_FLOAT, H5T_STRING = 0, 1, 3
 H5T_VARIABLE = C.c_size_t(-1).value
+H5T_STR_NULLPAD = 1
 
 
 class HDF5Error(IOError):
@@ -148,6 +149,78 @@ class File:
         L.H5Sclose(hid_t(sp))
         if plist is not None:
             L.H5Pclose(hid_t(plist))
+
+    def write_strings(self, name, values):
+        """A fixed-length UTF-8 string dataset, null-padded to the longest entry: a list gives a 1-d array, a str a scalar."""
+        L = lib()
+        scalar = isinstance(values, str)
+        enc = [str(v).encode("utf-8") for v in ([values] if scalar else values)]
+        size = max([len(e) for e in enc] + [1])
+        buf = C.create_string_buffer(b"".join(e.ljust(size, b"\0") for e in enc), size * max(len(enc), 1))
+        t = L.H5Tcopy(hid_t(_g("H5T_C_S1_g")))
+        L.H5Tset_size(hid_t(t), C.c_size_t(size))
+        L.H5Tset_strpad(hid_t(t), H5T_STR_NULLPAD)
+        L.H5Tset_cset(hid_t(t), H5T_CSET_UTF8)
+        if scalar:
+            sp = L.H5Screate(H5S_SCALAR)
+        else:
+            dims = (C.c_uint64 * 1)(len(enc))
+            sp = L.H5Screate_simple(1, dims, None)
+        try:
+            d = _chk(L.H5Dcreate2(hid_t(self.id), name.encode(), hid_t(t), hid_t(sp), hid_t(H5P_DEFAULT), hid_t(H5P_DEFAULT),
+                                  hid_t(H5P_DEFAULT)), "create dataset " + name)
+            try:
+                if enc:
+                    _chk(L.H5Dwrite(hid_t(d), hid_t(t), hid_t(H5S_ALL), hid_t(H5S_ALL), hid_t(H5P_DEFAULT), buf), "write " + name)
+            finally:
+                L.H5Dclose(hid_t(d))
+        finally:
+            L.H5Sclose(hid_t(sp))
+            L.H5Tclose(hid_t(t))
+
+    def read_strings(self, name):
+        """A fixed-length string dataset: a list of str (1-d), or one str (scalar)."""
+        L = lib()
+        d = _chk(L.H5Dopen2(hid_t(self.id), name.encode(), hid_t(H5P_DEFAULT)), "dataset " + name)
+        try:
+            t = L.H5Dget_type(hid_t(d))
+            sp = L.H5Dget_space(hid_t(d))
+            try:
+                if L.H5Tget_class(hid_t(t)) != H5T_STRING or L.H5Tis_variable_str(hid_t(t)) > 0:
+                    raise HDF5Error("%s is not a fixed-length string dataset" % name)
+                size = L.H5Tget_size(hid_t(t))
+                npts = L.H5Sget_simple_extent_npoints(hid_t(sp))
+                scalar = L.H5Sget_simple_extent_ndims(hid_t(sp)) == 0
+                buf = C.create_string_buffer(max(size * npts, 1))
+                if npts:
+                    _chk(L.H5Dread(hid_t(d), hid_t(t), hid_t(H5S_ALL), hid_t(H5S_ALL), hid_t(H5P_DEFAULT), buf), "read " + name)
+            finally:
+                L.H5Sclose(hid_t(sp))
+                L.H5Tclose(hid_t(t))
+        finally:
+            L.H5Dclose(hid_t(d))
+        out = [buf.raw[i * size:(i + 1) * size].split(b"\0")[0].decode("utf-8", "replace") for i in range(npts)]
+        return out[0] if scalar else out
+
+    def dataset_kind(self, name):
+        """(class, element bytes, shape) of a dataset: class is "integer", "float", "string" or "other"."""
+        L = lib()
+        d = _chk(L.H5Dopen2(hid_t(self.id), name.encode(), hid_t(H5P_DEFAULT)), "dataset " + name)
+        try:
+            t = L.H5Dget_type(hid_t(d))
+            sp = L.H5Dget_space(hid_t(d))
+            cls = L.H5Tget_class(hid_t(t))
+            size = int(L.H5Tget_size(hid_t(t)))
+            nd = L.H5Sget_simple_extent_ndims(hid_t(sp))
+            dims = (C.c_uint64 * max(nd, 1))()
+            if nd > 0:
+                L.H5Sget_simple_extent_dims(hid_t(sp), dims, None)
+            L.H5Sclose(hid_t(sp))
+            L.H5Tclose(hid_t(t))
+        finally:
+            L.H5Dclose(hid_t(d))
+        kind = {H5T_INTEGER: "integer", H5T_FLOAT: "float", H5T_STRING: "string"}.get(cls, "other")
+        return kind, size, tuple(int(dims[i]) for i in range(nd))
 
     # ---- groups / attributes
     def create_group(self, name):
