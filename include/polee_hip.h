@@ -711,6 +711,56 @@ typedef struct {
 } polee_gibbs_info;
 polee_status polee_gibbs_get_info(const polee_gibbs *g, polee_gibbs_info *info);
 
+/* ---- EM maximum-likelihood estimate (src/em.jl:3-87; `polee debug-optimize`, src/main.jl:960-988) -------------------------------
+ * expectation_maximization: the mixture y that maximises sum_i ks_i log sum_j X_ij y_j, by y_j <- y_j g_j / M with g the gradient
+ * of a likelihood pass and M = the sum of ks over the non-empty fragments (csrc/em.hip).  The handle works on an
+ * existing polee_loglik -- X is neither uploaded nor laid out again -- and keeps it alive.  An iteration is one K = 1 likelihood
+ * pass and one small launch; mixture, log-likelihood trace and stop rule stay on the device.
+ * An EM handle uses its loglik's ONE evaluation slot (see polee_loglik_eval): while polee_em_create / _reset with a y0 that has
+ * zeros, polee_em_run, or iterations it queued are in flight, nothing else -- polee_loglik_eval, a polee_vi or polee_regression step,
+ * another polee_em -- may evaluate the same polee_loglik.  With polee_loglik_set_deterministic(ll, 1) a run is bitwise
+ * reproducible. */
+typedef struct polee_em polee_em;
+/* y0_or_null: the start, f32 [n], finite, >= 0, with a positive sum (normalised on entry); NULL = 1/n (em.jl:22).  A y0 that is 0
+ * on every transcript some fragment is compatible with would give that fragment probability 0: POLEE_ERR_BAD_ARG, from
+ * polee_em_reset too (single-transcript fragments are checked against the layout's per-transcript counts; for the others a y0
+ * with zeros costs two likelihood passes, which count the fragments the pass does not skip). */
+polee_status polee_em_create(polee_loglik *ll, const float *y0_or_null, polee_em **out);
+void polee_em_destroy(polee_em *em);
+/* back to iteration 0 at a new start (as polee_em_create's); the trace is emptied */
+polee_status polee_em_reset(polee_em *em, const float *y0_or_null);
+/* Up to max_iters more iterations (em.jl:41-79).  Stop rule, em.jl:76: the run ends with the first iterate whose log-likelihood
+ * exceeds the previous one's by less than tol (the reference: 1e-6); tol < 0 switches the rule off, the call then makes exactly
+ * max_iters iterations.  lp is summed in f64 here (Float32 in the reference, which therefore stops at the first increase its sum
+ * cannot represent).  check_every >= 1 iterations are queued between two reads of the device's stop flag; once stopped the
+ * mixture is frozen, so the iterations queued behind the stop change nothing, and further calls return at once whatever their
+ * tol: to go on from there, polee_em_reset(em, the mixture polee_em_get_mixture returns), which empties the trace.  Returns after
+ * the last queued iteration has run; POLEE_ERR_NONFINITE when an iterate's log-likelihood is not finite. */
+polee_status polee_em_run(polee_em *em, int32_t max_iters, double tol, int32_t check_every);
+/* waits for the context's stream; POLEE_ERR_NONFINITE as polee_em_run */
+polee_status polee_em_sync(polee_em *em);
+/* the current iterate, normalised: y f32 [n], sums to 1 to f32 rounding */
+polee_status polee_em_get_mixture(polee_em *em, float *y);
+/* 1e6 (y / efflens) / sum(y / efflens) (em.jl:82-84); efflens_or_null == NULL (--no-efflen): 1e6 y.  tpm f32 [n] */
+polee_status polee_em_get_tpm(polee_em *em, const float *efflens_or_null, float *tpm);
+/* lp of iterates 1, 2, ... (the reference's `@show lp`, em.jl:74): the first min(capacity, *count) into lp; *count = entries held */
+polee_status polee_em_get_trace(polee_em *em, double *lp, int64_t capacity, int64_t *count);
+typedef struct {
+    int64_t n;
+    int64_t M;             /* sum of ks over the non-empty fragments (their number without ks)                          */
+    int64_t iters;         /* iterations made since creation / reset                                                      */
+    int32_t converged;     /* the stop rule has fired                                                                     */
+    int32_t nonfinite;     /* an iterate's log-likelihood was not finite                                                  */
+    double lp_start;       /* log-likelihood of the start (NaN before the first run)                                      */
+    double last_lp;        /* ... of the current iterate                                                                  */
+    double last_increase;  /* ... minus the previous iterate's                                                            */
+    double sum_y;          /* f64 sum of the iterate as the device holds it (1 up to f32 rounding)                        */
+    double kkt_max;        /* compute_kkt != 0: the fixed-point residual max_j y_j |g_j(y) / M - 1| of the mixture that          */
+                           /* polee_em_get_mixture hands out, from a gradient summed in f64 by a pass of its own over the       */
+                           /* layout (2 ms at 30 M fragments); else -1                                                           */
+} polee_em_info;
+polee_status polee_em_get_info(polee_em *em, int compute_kkt, polee_em_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1118,4 +1118,70 @@ function debug_gibbs_assignments(g::GibbsSampler, chain::Integer, m::Integer)
     return z
 end
 
+# ---- EM maximum-likelihood estimate (src/em.jl:3-87; `polee debug-optimize`, main.jl:960-988) ----------------------------------
+mutable struct EM
+    h::Ptr{Cvoid}
+    sample::AnySample   # kept alive: the handle works on the sample's X
+    n::Int
+end
+
+"mirror of `polee_em_info` (include/polee_hip.h): field order and types must stay in step with the header"
+struct EMInfo
+    n::Int64; M::Int64; iters::Int64
+    converged::Int32; nonfinite::Int32
+    lp_start::Float64; last_lp::Float64; last_increase::Float64; sum_y::Float64; kkt_max::Float64
+end
+
+"EM over the X of an existing device sample; y0 === nothing: the reference's start 1/n (em.jl:22).  While iterations run, nothing
+else may evaluate the same sample (one evaluation slot per likelihood handle)."
+function EM(s::AnySample, y0::Union{Nothing,Vector{Float32}}=nothing)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve y0 check(ccall((:polee_em_create, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ref{Ptr{Cvoid}}),
+                                s.h, y0 === nothing ? C_NULL : pointer(y0), r), s.ctx.h)
+    em = EM(r[], s, Int(s.n))
+    finalizer(x -> ccall((:polee_em_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), em)
+    return em
+end
+function reset!(em::EM, y0::Union{Nothing,Vector{Float32}}=nothing)
+    GC.@preserve y0 check(ccall((:polee_em_reset, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), em.h,
+                                y0 === nothing ? C_NULL : pointer(y0)), em.sample.ctx.h)
+end
+"up to max_iters more iterations; stops with the first iterate whose log-likelihood gains less than tol (em.jl:76; tol < 0: never)"
+run!(em::EM, max_iters::Integer=5000, tol::Real=1e-6, check_every::Integer=64) =
+    check(ccall((:polee_em_run, LIB), Cint, (Ptr{Cvoid}, Int32, Float64, Int32), em.h, max_iters, tol, check_every), em.sample.ctx.h)
+sync!(em::EM) = check(ccall((:polee_em_sync, LIB), Cint, (Ptr{Cvoid},), em.h), em.sample.ctx.h)
+function mixture(em::EM)
+    y = Vector{Float32}(undef, em.n)
+    GC.@preserve y check(ccall((:polee_em_get_mixture, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), em.h, y), em.sample.ctx.h)
+    return y
+end
+"1e6 (y / efflens) / sum(y / efflens) (em.jl:82-84); efflens === nothing: 1e6 y"
+function tpm(em::EM, efflens::Union{Nothing,Vector{Float32}})
+    out = Vector{Float32}(undef, em.n)
+    GC.@preserve efflens out check(ccall((:polee_em_get_tpm, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), em.h,
+                                         efflens === nothing ? C_NULL : pointer(efflens), out), em.sample.ctx.h)
+    return out
+end
+"log-likelihood of iterates 1, 2, ... (the reference's `@show lp`, em.jl:74)"
+function trace(em::EM)
+    k = Ref{Int64}(0)
+    check(ccall((:polee_em_get_trace, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Int64}), em.h, C_NULL, 0, k), em.sample.ctx.h)
+    lp = Vector{Float64}(undef, k[])
+    GC.@preserve lp check(ccall((:polee_em_get_trace, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Int64}), em.h, lp, length(lp), k),
+                          em.sample.ctx.h)
+    return lp
+end
+"kkt = true: the fixed-point residual max_j y_j |g_j / M - 1| of the mixture handed out, from an f64 gradient pass of its own"
+function info(em::EM; kkt::Bool=false)
+    i = Ref{EMInfo}()
+    check(ccall((:polee_em_get_info, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{EMInfo}), em.h, kkt ? 1 : 0, i), em.sample.ctx.h)
+    return i[]
+end
+"expectation_maximization (em.jl:3-87) on a device sample: the TPM vector"
+function expectation_maximization(s::AnySample, efflens::Union{Nothing,Vector{Float32}}; max_iters::Integer=5000, tol::Real=1e-6)
+    em = EM(s)
+    run!(em, max_iters, tol)
+    return tpm(em, efflens)
+end
+
 end # module

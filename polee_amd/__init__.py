@@ -14,6 +14,7 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   RNASeqLinearRegression / RNASeqTranscriptLinearRegression(...).fit         models/polee_regression.py
   build_likelihood_matrix (X from alignments, SimplisticFragModel)           src/rnaseq_sample.jl:58-121, src/fragmodel.jl
   gibbs_sampler / GibbsSampler (`polee debug-sample`)                        src/gibbs.jl, src/main.jl:925-957
+  expectation_maximization / EM (`polee debug-optimize`)                     src/em.jl, src/main.jl:960-988
 
 All numerics run in libpolee_hip.so on the GPU; nothing here computes on the CPU.
 """
@@ -41,4 +42,7 @@ def __getattr__(name):
     if name in ("GibbsSampler", "gibbs_sampler"):
         from . import gibbs
         return getattr(gibbs, name)
+    if name in ("EM", "expectation_maximization"):
+        from . import em
+        return getattr(em, name)
     raise AttributeError("module 'polee_amd' has no attribute %r" % name)

@@ -60,6 +60,8 @@
 //     slices -- the bulk of real and synthetic data, where many fragments fall into the same
 //     equivalence class -- keep their gradient contributions in registers.
 // HBM traffic per likelihood pass ~ 4.9 B/nnz at BASELINE's C2 (CSR: 8 B + row pointers), read once.
+// Two kernels decode ANY slice of these formats lane by lane: psell_tile_body (loglik.hip: stream B and the cross-check) and
+// em_g64_tiles_kernel (em.hip: the f64 gradient behind the EM fixed-point residual).  A change of a format goes into both.
 #pragma once
 #include "common.hpp"
 

@@ -1,4 +1,4 @@
-// Wave64 reductions with DPP (no LDS traffic, unlike __shfl): shared by loglik.hip and regression.hip.
+// Wave64 reductions with DPP (no LDS traffic, unlike __shfl): shared by loglik.hip, regression.hip and em.hip.
 // DPP reads of inactive lanes return 0 / stale data: call these with all 64 lanes active.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +20,24 @@ __device__ inline float wave_sum_to_lane63(float v)
     v = dpp_add<0x118, 0xf, 0xf>(v);  // row_shr:8   -> lane 15 of every row holds the row total
     v = dpp_add<0x142, 0xa, 0xf>(v);  // row_bcast:15 into rows 1 and 3
     v = dpp_add<0x143, 0xc, 0xf>(v);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
+    return v;
+}
+// the same in f64: the two halves of every value move by the same DPP controls (a lane the move leaves out adds 0.0)
+template <int CTRL, int ROW_MASK, int BANK_MASK>
+__device__ inline double dpp_add(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, BANK_MASK, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, BANK_MASK, true);
+    return v + __hiloint2double(hi, lo);
+}
+__device__ inline double wave_sum_to_lane63(double v)
+{
+    v = dpp_add<0x111, 0xf, 0xf>(v);
+    v = dpp_add<0x112, 0xf, 0xf>(v);
+    v = dpp_add<0x114, 0xf, 0xf>(v);
+    v = dpp_add<0x118, 0xf, 0xf>(v);
+    v = dpp_add<0x142, 0xa, 0xf>(v);
+    v = dpp_add<0x143, 0xc, 0xf>(v);
     return v;
 }
 // the same for N values at once, step-major so that the N dependency chains interleave
