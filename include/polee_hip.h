@@ -761,6 +761,42 @@ typedef struct {
 } polee_em_info;
 polee_status polee_em_get_info(polee_em *em, int compute_kkt, polee_em_info *info);
 
+/* ---- `polee sample` (src/main.jl:239-289 flags, :756-919 handler) ----------------------------------------------------------------
+ * A stream of draws from one fitted approximation with everything the command does after the draw: the effective-length adjustment
+ * (xs ./= efflens; xs ./= sum(xs), main.jl:850-853), the running posterior mean (:857) and prop_to_counts (:859-880), on the device.
+ * The raw draw with index d is bit for bit row d of polee_sampler_draw(..., ndraws > d, the same seed), for any split of the draws
+ * into polee_sampler_next calls.  Arithmetic (csrc/sample.hip): t_j = x_j / l_j in f32; S = sum t_j in f64;
+ * prop_j = (float)((double)t_j / S); the posterior mean is accumulated in f64 per transcript in draw order and handed out as f32;
+ * expected counts in f64: e_j = (double)prop_j l_j, counts_j = e_j / sum(e) m. */
+typedef struct polee_sampler polee_sampler;
+/* t: a single tree; mu, sigma, alpha f32 [n-1] (sigma = exp(omega)); efflens f32 [n], positive and finite; 0 <= m < 2^31.
+ * Parameters, effective lengths and all work buffers live on the device; the handle keeps the tree alive and uses its scratch. */
+polee_status polee_sampler_create(polee_ptt *t, const float *mu, const float *sigma, const float *alpha, const float *efflens,
+                                  int64_t m, uint64_t seed, polee_sampler **out);
+void polee_sampler_destroy(polee_sampler *s);
+/* The next `count` draws (the draw index continues from the previous call).  z0_or_null: f32 [count][n-1], the N(0,1) noise of these
+ * draws, or NULL = the device RNG.  Outputs, each optional, one download each: raw f32 [count][n] (the draws as polee_sampler_draw
+ * gives them), props f32 [count][n], counts f64 [count][n] = prop_to_counts of every row -- count_mode 0: expected_counts
+ * (main.jl:859-863); 1: sampled counts (--sample-counts): an exact multinomial draw of m reads with shares e_j, integers, every row
+ * sums to m, a pure function of (the draw, m, seed, draw index); see polee_multinomial_counts.  The posterior mean is accumulated
+ * whatever is asked for. */
+polee_status polee_sampler_next(polee_sampler *s, int32_t count, int32_t count_mode, const float *z0_or_null, float *raw_or_null,
+                                float *props_or_null, double *counts_or_null);
+/* draws made so far */
+polee_status polee_sampler_num_draws(polee_sampler *s, int64_t *ndraws);
+/* post_mean f32 [n]: the mean of all props so far; est_counts f64 [n] = prop_to_counts(post_mean) under count_mode (mode 1 draws
+ * under the draw index 2^64 - 1). */
+polee_status polee_sampler_mean(polee_sampler *s, float *post_mean, double *est_counts_or_null, int32_t count_mode);
+/* D exact multinomial draws of m items over n categories: p f64 [D][n], shares >= 0 and finite, need not be normalised; counts u32
+ * [D][n], every row sums to m.  0 <= m < 2^31, 1 <= n <= 2^30.  Row r is draw first_draw + r: a pure function of (its shares, m,
+ * seed, draw index) -- bitwise reproducible, independent of D and of how rows are batched.  Construction: m is split down a
+ * balanced binary tree over the categories, Binomial(c, mass of the left half / mass of the node) at every node (n - 1 variates
+ * per draw, whatever m is), exact binomial variates from counter-based Philox noise (csrc/binomial.hpp).  POLEE_ERR_BAD_ARG: a
+ * negative or non-finite share, a row that sums to 0 with m > 0, sizes out of range.  POLEE_ERR_NONFINITE (here and from the
+ * handle): a variate used up its fixed number of rejection attempts, which finite shares do not do. */
+polee_status polee_multinomial_counts(polee_ctx *ctx, const double *p, int32_t D, int64_t n, int64_t m, uint64_t seed,
+                                      uint64_t first_draw, uint32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

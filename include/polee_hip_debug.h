@@ -102,6 +102,10 @@ polee_status polee_debug_fast_exp(polee_ctx *ctx, const double *x, int64_t count
  * order; 0 = a fragment with no compatible transcript).  Recomputed by the assignment kernel on the state that sweep started from. */
 polee_status polee_debug_gibbs_assignments(polee_gibbs *g, int32_t chain, int32_t *z);
 
+/* One Binomial(N[i], p[i]) variate per entry from csrc/binomial.hpp, keyed by (seed, draw index i, node 0): 0 <= N < 2^31,
+ * 0 <= p <= 1; out i64 [count] (the goodness-of-fit tests of the multinomial sampler's nodes) */
+polee_status polee_debug_binomial(polee_ctx *ctx, const int64_t *N, const double *p, int64_t count, uint64_t seed, int64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1184,4 +1184,56 @@ function expectation_maximization(s::AnySample, efflens::Union{Nothing,Vector{Fl
     return tpm(em, efflens)
 end
 
+# ---- `polee sample` (main.jl:756-919): streamed draws, posterior mean, prop_to_counts, exact multinomial counts ------------------
+mutable struct SampleStream
+    h::Ptr{Cvoid}
+    t::PolyaTreeTransform   # kept alive: the handle uses the tree and its scratch
+    n::Int
+end
+
+"a stream of draws from one fitted approximation; sigma = exp.(omega); 0 <= m < 2^31"
+function SampleStream(t::PolyaTreeTransform, mu::Vector{Float32}, sigma::Vector{Float32}, alpha::Vector{Float32},
+                      efflens::Vector{Float32}, m::Integer; seed::Integer=123456789)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve mu sigma alpha efflens check(
+        ccall((:polee_sampler_create, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, UInt64, Ref{Ptr{Cvoid}}),
+              t.h, mu, sigma, alpha, efflens, m, seed, r), t.ctx.h)
+    s = SampleStream(r[], t, length(efflens))
+    finalizer(x -> ccall((:polee_sampler_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), s)
+    return s
+end
+"the next `count` draws: (props n x count Float32, counts n x count Float64 or nothing); sample_counts: exact multinomial counts
+(--sample-counts) instead of expected ones (main.jl:859-880).  Columns are draws."
+function next!(s::SampleStream, count::Integer; counts::Bool=true, sample_counts::Bool=false)
+    props = Matrix{Float32}(undef, s.n, count)
+    cs = counts ? Matrix{Float64}(undef, s.n, count) : nothing
+    GC.@preserve props cs check(
+        ccall((:polee_sampler_next, LIB), Cint,
+              (Ptr{Cvoid}, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}),
+              s.h, count, sample_counts ? 1 : 0, C_NULL, C_NULL, props, cs === nothing ? C_NULL : pointer(cs)), s.t.ctx.h)
+    return props, cs
+end
+function num_draws(s::SampleStream)
+    k = Ref{Int64}(0)
+    check(ccall((:polee_sampler_num_draws, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), s.h, k), s.t.ctx.h)
+    return k[]
+end
+"(post_mean, est_counts = prop_to_counts(post_mean)) of all draws so far (main.jl:857, :887)"
+function posterior_mean(s::SampleStream; sample_counts::Bool=false)
+    pm = Vector{Float32}(undef, s.n); ec = Vector{Float64}(undef, s.n)
+    GC.@preserve pm ec check(ccall((:polee_sampler_mean, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float64}, Int32),
+                                   s.h, pm, ec, sample_counts ? 1 : 0), s.t.ctx.h)
+    return pm, ec
+end
+"exact multinomial draws of m items: p is n x D (a column = the shares of one draw, >= 0, not necessarily normalised) -> n x D
+UInt32 counts, every column summing to m; column r is draw first_draw + r - 1, a pure function of (shares, m, seed, draw index)"
+function multinomial_counts(ctx::Context, p::Matrix{Float64}, m::Integer; seed::Integer=123456789, first_draw::Integer=0)
+    out = Matrix{UInt32}(undef, size(p, 1), size(p, 2))
+    GC.@preserve p out check(
+        ccall((:polee_multinomial_counts, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int64, Int64, UInt64, UInt64, Ptr{UInt32}),
+              ctx.h, p, size(p, 2), size(p, 1), m, seed, first_draw, out), ctx.h)
+    return out
+end
+
 end # module

@@ -15,6 +15,7 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   build_likelihood_matrix (X from alignments, SimplisticFragModel)           src/rnaseq_sample.jl:58-121, src/fragmodel.jl
   gibbs_sampler / GibbsSampler (`polee debug-sample`)                        src/gibbs.jl, src/main.jl:925-957
   expectation_maximization / EM (`polee debug-optimize`)                     src/em.jl, src/main.jl:960-988
+  polee_sample / ApproxSampleStream / multinomial_counts (`polee sample`)    src/main.jl:756-919
 
 All numerics run in libpolee_hip.so on the GPU; nothing here computes on the CPU.
 """
@@ -45,4 +46,7 @@ def __getattr__(name):
     if name in ("EM", "expectation_maximization"):
         from . import em
         return getattr(em, name)
+    if name in ("ApproxSampleStream", "polee_sample", "multinomial_counts"):
+        from . import sample
+        return getattr(sample, name)
     raise AttributeError("module 'polee_amd' has no attribute %r" % name)

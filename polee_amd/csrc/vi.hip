@@ -17,6 +17,7 @@
 #include "vi_fused.hpp"
 #include "comm_internal.hpp"
 #include "rng.hpp"
+#include "sampler_internal.hpp"
 
 #include <cmath>
 
@@ -139,13 +140,14 @@ __global__ void vi_inverse_nodes_kernel(PttView v, const dd *C, double *ys)
 
 // sampler: rand! (approx-sampler.jl:37-44) -- no clamp of ys
 // (y_eps > 0: the clamp of the initial-value draws, estimate.jl:443-447)
-__global__ void sampler_y_kernel(const float *mu, const float *sigma, const float *alpha, NoiseSrc noise, double y_eps,
+// (d_off: the row's place in its block of 8 draws, which keys the device RNG; caller-supplied noise is indexed by row)
+__global__ void sampler_y_kernel(const float *mu, const float *sigma, const float *alpha, NoiseSrc noise, int d_off, double y_eps,
                                  double *ys)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int d = blockIdx.y;
     if (k >= noise.nm1) return;
-    const float z0 = noise.get(1, d, k);
+    const float z0 = noise.get(1, noise.z0 ? d : d + d_off, k);
     const float zs = sinhf(alpha[k] + asinhf(z0));
     double y = (double)logistic_f32(mu[k] + zs * sigma[k]);
     if (y_eps > 0.0) y = y < y_eps ? y_eps : (y > 1 - y_eps ? 1 - y_eps : y);
@@ -396,22 +398,31 @@ static polee_status sampler_draw_device(polee_ptt *t, const float *mu, const flo
     POLEE_TRY(d_sigma.upload(ctx, sigma, nm1));
     POLEE_TRY(d_alpha.upload(ctx, alpha, nm1));
     POLEE_TRY(d_all.alloc(ctx, (size_t)ndraws * n));
-    for (int32_t b0 = 0; b0 < ndraws; b0 += 8) {
-        const int32_t B = std::min(8, ndraws - b0);
-        POLEE_TRY(t->reserve(B));
+    for (int32_t b0 = 0; b0 < ndraws; b0 += SAMPLER_BLOCK) {
+        const int32_t B = std::min(SAMPLER_BLOCK, ndraws - b0);
         if (z0) POLEE_TRY(d_z0.upload(ctx, z0 + (size_t)b0 * nm1, (size_t)B * nm1));
-        NoiseSrc noise{z0 ? d_z0.p : nullptr, seed + (uint64_t)b0 * 0x9E3779B97F4A7C15ull, B, (int64_t)nm1};
-        if (nm1 > 0) {
-            hipLaunchKernelGGL(sampler_y_kernel, dim3((unsigned)ceil_div(nm1, 256), B), dim3(256), 0, ctx->stream,
-                               d_mu.p, d_sigma.p, d_alpha.p, noise, y_eps, t->d_ys.p);
-            POLEE_KERNEL_CHECK(ctx);
-        }
-        FwdOut o;
-        o.xs = d_all.p + (size_t)b0 * n;
-        o.xs_rs = n;
-        POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
+        POLEE_TRY(sampler_block_device(t, d_mu.p, d_sigma.p, d_alpha.p, z0 ? d_z0.p : nullptr, seed, (uint64_t)b0, 0, B, y_eps,
+                                       d_all.p + (size_t)b0 * n, (int64_t)n));
     }
     return POLEE_OK;
+}
+
+polee_status sampler_block_device(polee_ptt *t, const float *d_mu, const float *d_sigma, const float *d_alpha, const float *d_z0,
+                                  uint64_t seed, uint64_t b0, int32_t r0, int32_t B, double y_eps, float *d_xs, int64_t xs_rs)
+{
+    polee_ctx *ctx = t->ctx;
+    const size_t nm1 = (size_t)t->n - 1;
+    POLEE_TRY(t->reserve(B));
+    NoiseSrc noise{d_z0, sampler_block_seed(seed, b0), B, (int64_t)nm1};
+    if (nm1 > 0) {
+        hipLaunchKernelGGL(sampler_y_kernel, dim3((unsigned)ceil_div(nm1, 256), B), dim3(256), 0, ctx->stream, d_mu, d_sigma,
+                           d_alpha, noise, (int)r0, y_eps, t->d_ys.p);
+        POLEE_KERNEL_CHECK(ctx);
+    }
+    FwdOut o;
+    o.xs = d_xs;
+    o.xs_rs = xs_rs;
+    return ptt_forward_device(t, t->d_ys.p, B, o);
 }
 
 // posterior_mean (src/approx-sampler.jl:86-117): clamp every draw to [1e-15, 0.9999999], add them in draw order in

@@ -368,3 +368,46 @@ def read_transformation(filename):
     """PTT file of `polee fit-tree` / --ptt-tree (main.jl:650-659): node_parent_idxs, node_js."""
     with File(filename) as f:
         return f.read("node_parent_idxs", np.int32), f.read("node_js", np.int32)
+
+
+def _read_variable_strings(f, name):
+    """A variable-length string dataset (what HDF5.jl writes for an Array{String}): a list of str."""
+    L = lib()
+    d = _chk(L.H5Dopen2(hid_t(f.id), name.encode(), hid_t(H5P_DEFAULT)), "dataset " + name)
+    try:
+        sp = L.H5Dget_space(hid_t(d))
+        t = L.H5Tcopy(hid_t(_g("H5T_C_S1_g")))
+        try:
+            L.H5Tset_size(hid_t(t), C.c_size_t(H5T_VARIABLE))
+            ft = L.H5Dget_type(hid_t(d))
+            L.H5Tset_cset(hid_t(t), L.H5Tget_cset(hid_t(ft)))
+            L.H5Tclose(hid_t(ft))
+            npts = int(L.H5Sget_simple_extent_npoints(hid_t(sp)))
+            buf = (C.c_char_p * max(npts, 1))()
+            if npts:
+                _chk(L.H5Dread(hid_t(d), hid_t(t), hid_t(H5S_ALL), hid_t(H5S_ALL), hid_t(H5P_DEFAULT), buf), "read " + name)
+            out = [(buf[i] or b"").decode("utf-8", "replace") for i in range(npts)]
+            if npts:
+                L.H5Dvlen_reclaim(hid_t(t), hid_t(sp), hid_t(H5P_DEFAULT), buf)  # (the library allocated the strings)
+        finally:
+            L.H5Tclose(hid_t(t))
+            L.H5Sclose(hid_t(sp))
+    finally:
+        L.H5Dclose(hid_t(d))
+    return out
+
+
+def read_transformation_ids(filename):
+    """transcript_ids of a PTT file (main.jl:776-779; written at :650-659): a list of str, whether the file stores them as
+    variable-length strings (HDF5.jl) or null-padded fixed-length ones (File.write_strings)."""
+    L = lib()
+    with File(filename) as f:
+        if not f.exists("transcript_ids"):
+            raise HDF5Error("%s holds no transcript_ids" % filename)
+        d = _chk(L.H5Dopen2(hid_t(f.id), b"transcript_ids", hid_t(H5P_DEFAULT)), "dataset transcript_ids")
+        t = L.H5Dget_type(hid_t(d))
+        variable = L.H5Tget_class(hid_t(t)) == H5T_STRING and L.H5Tis_variable_str(hid_t(t)) > 0
+        L.H5Tclose(hid_t(t))
+        L.H5Dclose(hid_t(d))
+        ids = _read_variable_strings(f, "transcript_ids") if variable else f.read_strings("transcript_ids")
+    return [ids] if isinstance(ids, str) else list(ids)
