@@ -402,12 +402,23 @@ __device__ inline void dma_builtin(const void *base_uniform, uint32_t voff, uint
 }
 __device__ inline void dma_1k(const void *b, uint32_t v, uint32_t l) { dma_builtin(b, v, l, 1); }
 __device__ inline void dma_1k_keep(const void *b, uint32_t v, uint32_t l) { dma_builtin(b, v, l, 1); }
+__device__ inline void dma_1k_next(const void *b, uint32_t v, uint32_t l) { dma_builtin(b, v, l, 1); }
 __device__ inline void dma_256(const void *b, uint32_t v, uint32_t l) { dma_builtin(b, v, l, 0); }
 #else
 __device__ inline void dma_1k(const void *base_uniform, uint32_t voff, uint32_t lds_dst_any)
 {
     const uint32_t lds_dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_dst_any);
     asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" POLEE_DMA_POLICY
+                 :
+                 : "s"(base_uniform), "v"(voff), "s"(lds_dst)
+                 : "memory");
+}
+// A further piece of a burst whose first piece went out with dma_1k in the same straight line: the base is the same SGPR pair
+// (nothing rewrites it between the pieces: the lane offset moves, a vector register), so the wait states have been served and
+// only M0 changes.  `lds_dst` must be wave-uniform as written.
+__device__ inline void dma_1k_next(const void *base_uniform, uint32_t voff, uint32_t lds_dst)
+{
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" POLEE_DMA_POLICY
                  :
                  : "s"(base_uniform), "v"(voff), "s"(lds_dst)
                  : "memory");
@@ -464,6 +475,21 @@ __device__ inline void wait_vm_outstanding(int allowed)
     }
 }
 
+// The slice loops of the matrix-core streams: with the whole ring requested ahead, `allowed` is the ring's seven pieces
+// minus the pieces the slice touches -- 3 .. 5 for sets of 4 .. 12 transcripts -- so those values are tested first (one or
+// two scalar compares instead of the ladder's four or five); everything else takes the ladder.
+__device__ inline void wait_vm_steady(int allowed)
+{
+    if (allowed == 4)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (allowed == 5)
+        asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else if (allowed == 3)
+        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    else
+        wait_vm_outstanding(allowed);
+}
+
 // This lane's index in its wave, computed where it is used (two instructions): a lane index kept in a register across
 // the tile loop is spilled under the slice loop's register pressure, and its reload comes with an s_waitcnt vmcnt(0) that
 // drains the LDS-DMA ring which has just been started.
@@ -484,6 +510,7 @@ __device__ inline void lds_barrier()
 #ifdef POLEE_STAMPS
 // diagnostic build only: where does a wave of the streaming kernel spend its cycles?
 __device__ unsigned long long g_stamps[24];
+__device__ unsigned long long g_stamps_wave[4][24];  // the same per wave index of the workgroup (wave 0 carries the schedule DMA and the ticket)
 
 #define STAMP(i)                                                          \
     do {                                                                  \
@@ -499,34 +526,47 @@ __device__ unsigned long long g_stamps[24];
 __device__ unsigned long long g_tile_cycles[1 << 17];  // per tile: wave 0's time from the previous tile's end to this tile's end
 __device__ unsigned long long g_wg_cycles[4096];       // per workgroup: wave 0's time in the kernel
 #endif
-constexpr int NSTAMP = 16;  // (diagnostic build)
+constexpr int NSTAMP = 17;  // (diagnostic build)
 
 // what a wave knows about its share of the current uniform tile
 struct WaveStream {
     uint32_t ent;         // slice offset (+ flags) of slice sb + lane, one per lane
     int nsl;              // slices owned by this wave
     int npieces;          // 1 KiB pieces of its byte range
-    int issued, islot;    // pieces requested so far; ring slot of the next one
+    int issued;           // pieces requested so far
+    uint32_t slot;        // byte offset, inside the ring, of the slot the next piece goes to
     int primed;           // pieces requested before the tile's loop started
     const uint8_t *gsrc;  // start of the byte range (wave-uniform)
 };
 
+// Requests the pieces [issued, target) of a wave's byte range, piece after piece into consecutive ring slots.  Everything here
+// is wave-uniform and the caller holds it in scalar registers: `gsrc`, the START of the range -- an SGPR pair that is not
+// advanced: a piece's position travels in the lanes' 32-bit byte offsets, one vector add per piece (a wave's share of a tile is
+// far below 4 GiB), so the wait states between a freshly read SGPR base and the first vector-memory instruction that uses it
+// are paid once per burst (dma_1k), not once per piece (dma_1k_next) --, the piece counter, and the ring offset of the next slot.
+template <uint32_t RB>
+__device__ inline void ring_issue(const uint8_t *gsrc, uint32_t ring_lds, int &issued, uint32_t &slot, int target)
+{
+    if (issued >= target) return;
+    uint32_t voff = (uint32_t)wave_lane() * 16u + (uint32_t)issued * 1024u;
+    dma_1k(gsrc, voff, ring_lds + slot);
+    for (;;) {
+        slot = slot + 1024u == RB ? 0u : slot + 1024u;
+        if (++issued >= target) break;
+        voff += 1024u;
+        dma_1k_next(gsrc, voff, ring_lds + slot);
+    }
+}
+// the same on a WaveStream (the loops that do not keep the counters in locals of their own)
 template <uint32_t RB>
 __device__ inline void ring_refill(WaveStream &ws, uint32_t ring_lds, int target)
 {
-    constexpr int RP = (int)(RB / 1024u);
-    // (wave-uniform counters: say so, or the loop below is compiled as a divergent loop on vector registers)
-    int issued = __builtin_amdgcn_readfirstlane(ws.issued), islot = __builtin_amdgcn_readfirstlane(ws.islot);
-    target = __builtin_amdgcn_readfirstlane(target);
-    const uint32_t voff = (uint32_t)wave_lane() * 16u;
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(uniform_ptr(ws.gsrc + (size_t)issued * 1024));
-    for (; issued < target; ++issued) {
-        dma_1k(src, voff, ring_lds + (uint32_t)islot * 1024u);
-        src += 1024;
-        islot = islot + 1 == RP ? 0 : islot + 1;
-    }
+    // (wave-uniform counters: say so, or the loop is compiled as a divergent loop on vector registers)
+    int issued = __builtin_amdgcn_readfirstlane(ws.issued);
+    uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)ws.slot);
+    ring_issue<RB>(reinterpret_cast<const uint8_t *>(uniform_ptr(ws.gsrc)), ring_lds, issued, slot, __builtin_amdgcn_readfirstlane(target));
     ws.issued = issued;
-    ws.islot = islot;
+    ws.slot = slot;
 }
 
 // The slice loop of one wave over its share of a tile of the WIDE stream (A2: transcript sets of 17..32; 16 x 16 x 4 matrix
@@ -621,11 +661,16 @@ __device__ inline void wide_stream(WaveStream &ws, const char *ring, int extras,
 
     uint32_t pos = 0;    // byte offset of the ring's tail inside this wave's range (a slice start, or STAGE_A behind one)
     uint32_t pos_r = 0;  // pos modulo the ring size
+    // the ring's counters and the range's start, in scalar registers for the whole tile (ring_issue)
+    int issued = __builtin_amdgcn_readfirstlane(ws.issued);
+    uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)ws.slot);
+    const int primed = __builtin_amdgcn_readfirstlane(ws.primed), npieces = __builtin_amdgcn_readfirstlane(ws.npieces);
+    const uint8_t *const gsrc = reinterpret_cast<const uint8_t *>(uniform_ptr(ws.gsrc));
     auto wait_for = [&](uint32_t upto) {  // bytes [pos, pos + upto) of the wave's range must have landed
         const int need = (int)((pos + upto + 1023u) >> 10);
-        if (ws.issued < need) ring_refill<RB>(ws, ring_lds, need);  // (only with a shortened look-ahead: experiments)
+        if (issued < need) ring_issue<RB>(gsrc, ring_lds, issued, slot, need);  // (only with a shortened look-ahead: experiments)
         // (wave-uniform: said explicitly, or the ladder below is compiled with vector compares and exec masks)
-        int allowed = ws.issued - need + (need <= ws.primed ? extras : 0);
+        int allowed = issued - need + (need <= primed ? extras : 0);
         wait_vm_outstanding(__builtin_amdgcn_readfirstlane(allowed));
     };
     auto release = [&](uint32_t nbytes) {  // the first nbytes behind the tail are consumed: the DMA for what follows goes out
@@ -633,11 +678,13 @@ __device__ inline void wide_stream(WaveStream &ws, const char *ring, int extras,
         pos += nbytes;
         pos_r += nbytes;
         pos_r = pos_r >= RB ? pos_r - RB : pos_r;
-        ring_refill<RB>(ws, ring_lds, min(ws.npieces, (int)(pos >> 10) + RP));
+        ring_issue<RB>(gsrc, ring_lds, issued, slot, min(npieces, (int)(pos >> 10) + RP));
     };
+    uint32_t e_next = (uint32_t)__builtin_amdgcn_readlane((int)ws.ent, 0);  // (a slice's end is the next one's start: one lane read per slice)
     for (int si = 0; si < ws.nsl; ++si) {
-        const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)ws.ent, si);
+        const uint32_t e0 = e_next;
         const uint32_t e1 = (uint32_t)__builtin_amdgcn_readlane((int)ws.ent, si + 1);
+        e_next = e1;
         const uint32_t off = e0 & PSELL_OFF_MASK, off_next = e1 & PSELL_OFF_MASK;
         const int flags = (int)(e0 >> 30);
         const uint32_t units = off_next - off;
@@ -933,9 +980,16 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
 
     uint32_t pos = 0;    // byte offset of the current slice inside this wave's range
     uint32_t pos_r = 0;  // pos modulo the ring size
+    // the ring's counters and the range's start, in scalar registers for the whole tile (ring_issue)
+    int issued = __builtin_amdgcn_readfirstlane(ws.issued);
+    uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)ws.slot);
+    const int primed = __builtin_amdgcn_readfirstlane(ws.primed), npieces = __builtin_amdgcn_readfirstlane(ws.npieces);
+    const uint8_t *const gsrc = reinterpret_cast<const uint8_t *>(uniform_ptr(ws.gsrc));
+    uint32_t e_next = (uint32_t)__builtin_amdgcn_readlane((int)ws.ent, 0);  // (a slice's end is the next one's start: one lane read per slice)
     for (int si = 0; si < ws.nsl; ++si) {
-        const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)ws.ent, si);
+        const uint32_t e0 = e_next;
         const uint32_t e1 = (uint32_t)__builtin_amdgcn_readlane((int)ws.ent, si + 1);
+        e_next = e1;
         const uint32_t off = e0 & PSELL_OFF_MASK, off_next = e1 & PSELL_OFF_MASK;
         const int flags = (int)(e0 >> 30);
         const uint32_t units = off_next - off;
@@ -946,8 +1000,7 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
         STAMP(1);  // slice bookkeeping
         {
             const int need = (int)((pos + bytes + 1023u) >> 10);
-            int allowed = ws.issued - need + (need <= ws.primed ? extras : 0);
-            wait_vm_outstanding(__builtin_amdgcn_readfirstlane(allowed));
+            wait_vm_steady(__builtin_amdgcn_readfirstlane(issued - need + (need <= primed ? extras : 0)));
         }
         STAMP(2);  // waiting for the DMA
         if (pend_w != 0 && !(flags & 2)) flush();
@@ -981,7 +1034,7 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
             pos += bytes;
             pos_r += bytes;
             pos_r = pos_r >= RB ? pos_r - RB : pos_r;
-            ring_refill<RB>(ws, ring_lds, min(ws.npieces, (int)(pos >> 10) + RP));
+            ring_issue<RB>(gsrc, ring_lds, issued, slot, min(npieces, (int)(pos >> 10) + RP));
             STAMP(6);  // refill
             if (!(dbg & 16)) __builtin_amdgcn_s_setprio(0);
         };
@@ -1586,6 +1639,13 @@ extern "C" int polee_debug_read_stamps(unsigned long long *out)
     unsigned long long z[24] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof z) == hipSuccess ? 0 : 1;
 }
+// the same per wave index: out[4][24]; entry 19 = the wait for the ticket (wave 0)
+extern "C" int polee_debug_read_stamps_wave(unsigned long long *out)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps_wave), sizeof(unsigned long long) * 96) != hipSuccess) return 1;
+    unsigned long long z[96] = {0};
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_stamps_wave), z, sizeof z) == hipSuccess ? 0 : 1;
+}
 #endif
 
 // x window of every tile, contiguous: xwin[e * K + k] = x[dict[e]][k] for every dictionary entry e (tiles' dictionaries
@@ -1774,6 +1834,12 @@ template <int K, bool WANT_LP, bool HAS_KS, bool DET>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((WANT_LP || HAS_KS) ? 3 : 4, (WANT_LP || HAS_KS) ? 3 : 4)))
 void loglik_stream_kernel(PsellArgs A, int dbg)
 {
+#ifndef POLEE_ABLATE
+    // The ablation switches (POLEE_DBG_ABLATE, tools/probe/time_fit.py) exist only in the diagnostic build `make ablate`: as
+    // run-time bits they were live scalar tests in every slice (four branches, four SGPR pairs of masks in a kernel that
+    // spills scalar registers); here every `dbg & ...` folds away.
+    dbg = 0;
+#endif
     extern __shared__ float lds[];
     constexpr uint32_t XWB = stream_xw_bytes<K>();
     constexpr uint32_t GWN = DET ? 4u : 1u;  // gradient windows
@@ -1801,7 +1867,7 @@ void loglik_stream_kernel(PsellArgs A, int dbg)
     uint32_t p2 = blockIdx.x + 2u * G;  // (wave 0) position of the tile after the next one
     const uint8_t *__restrict__ xwin_b = reinterpret_cast<const uint8_t *>(A.xwin);
 #ifdef POLEE_STAMPS
-    unsigned long long st_acc[NSTAMP] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long st_acc[NSTAMP] = {};
     unsigned long long st_last = __builtin_amdgcn_s_memtime();
     unsigned long long n_slices = 0, n_tiles = 0;
 #endif
@@ -1852,7 +1918,7 @@ void loglik_stream_kernel(PsellArgs A, int dbg)
     const int ahead = (dbg >> 8) & 15;  // (experiment: pieces requested ahead; 0 = the whole ring)
     auto start_ring = [&](const PosDesc &t) {
         const int kind = kind_of(t.tile);
-        ws.nsl = 0; ws.npieces = 0; ws.issued = 0; ws.islot = 0; ws.primed = 0; ws.ent = 0u; ws.gsrc = A.data;
+        ws.nsl = 0; ws.npieces = 0; ws.issued = 0; ws.slot = 0u; ws.primed = 0; ws.ent = 0u; ws.gsrc = A.data;
         uint32_t sb, se;
         share(kind, t, sb, se);
         ws.ent = entb[wave * 64 + wave_lane()];
@@ -2016,6 +2082,7 @@ void loglik_stream_kernel(PsellArgs A, int dbg)
                 p2 += G;
             }
         }
+        STAMP(16);  // wave 0: the wait for the ticket (the vmcnt(0) the compiler places in front of the read of `drawn`)
         {
             const uint32_t *dp = descb + (round & 1u) * 64u;
             nxt.tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)dp[0]);
@@ -2051,10 +2118,17 @@ void loglik_stream_kernel(PsellArgs A, int dbg)
 #ifdef POLEE_STAMPS
     STAMP(10);
     if (wave_lane() == 0) {
-        for (int i = 0; i < NSTAMP; ++i) atomicAdd(&g_stamps[i], st_acc[i]);
+        for (int i = 0; i < 16; ++i) atomicAdd(&g_stamps[i], st_acc[i]);
         atomicAdd(&g_stamps[16], n_slices);
         atomicAdd(&g_stamps[17], n_tiles);
         atomicAdd(&g_stamps[18], 1ull);
+        atomicAdd(&g_stamps[19], st_acc[16]);
+        unsigned long long *gsw = g_stamps_wave[wave & 3];
+        for (int i = 0; i < 16; ++i) atomicAdd(&gsw[i], st_acc[i]);
+        atomicAdd(&gsw[16], n_slices);
+        atomicAdd(&gsw[17], n_tiles);
+        atomicAdd(&gsw[18], 1ull);
+        atomicAdd(&gsw[19], st_acc[16]);
     }
 #endif
 }
@@ -2288,6 +2362,11 @@ static polee_status launch_variant(polee_loglik *ll, const float *d_x, float *d_
     static const bool no_ring_env = getenv("POLEE_NO_RING") != nullptr;
     const bool no_ring = no_ring_env || ll->force_mixed;
     static const int dbg = getenv("POLEE_DBG_ABLATE") ? atoi(getenv("POLEE_DBG_ABLATE")) : 0;
+#ifndef POLEE_ABLATE
+    static const bool dbg_told = dbg != 0 && (fprintf(stderr, "[loglik] POLEE_DBG_ABLATE is ignored by this build: the switches are compiled "
+                                                              "into libpolee_hip_ablate.so only (make ablate, POLEE_HIP_LIB)\n"), true);
+    (void)dbg_told;
+#endif
     const LoglikRemap *rm = ll->cur_remap;
     const uint32_t *csr_col = rm && rm->csr_col ? rm->csr_col : ll->d_csr_col.p;
     PsellArgs A{ll->d_data.p, ll->d_slice_off.p, ll->d_tile_slice.p, ll->d_tile_dict.p, rm ? rm->dict : ll->d_dict.p,

@@ -21,8 +21,14 @@ fit.run(5); fit.sync()
 out = (C.c_ulonglong * 24)()
 f = L.lib().polee_debug_read_stamps
 f(out)  # reset
+fw = getattr(L.lib(), "polee_debug_read_stamps_wave", None)  # (per wave index of the workgroup)
+outw = (C.c_ulonglong * 96)()
+if fw is not None:
+    fw(outw)
 fit.run(20); fit.sync()
 f(out)
+if fw is not None:
+    fw(outw)
 v = np.array(list(out), np.float64)
 names = {0: "prefetch issue for the next tile", 1: "slice bookkeeping", 2: "waiting for the DMA",
          3: "run change: flush + column lookup", 11: "operand reads issued and landed (lgkmcnt 0)", 6: "ring refill (DMA issue)",
@@ -33,6 +39,15 @@ names = {0: "prefetch issue for the next tile", 1: "slice bookkeeping", 2: "wait
 tot = v[:16].sum()
 for i, nm in names.items():
     print("%-52s %5.1f %%" % (nm, 100 * v[i] / tot))
+print("%-52s %5.1f %%  (inside the rows above)" % ("wave 0: wait for the ticket before `drawn` is read", 100 * v[19] / tot))
+if fw is not None:
+    # per wave index: share of THAT wave's time, and its mean cycles per tile in each row
+    w = np.array(list(outw), np.float64).reshape(4, 24)
+    print("per wave index (share of the wave's own time | memtime units per tile):")
+    print("%-52s %s" % ("", "  ".join("      wave %d      " % k for k in range(4))))
+    for i, nm in list(names.items()) + [(19, "wait for the ticket (inside the rows above)")]:
+        print("%-52s %s" % (nm, "  ".join("%5.1f %% | %8.1f" % (100 * w[k, i] / max(w[k, :16].sum(), 1), w[k, i] / max(w[k, 17], 1)) for k in range(4))))
+    print("%-52s %s" % ("slices per tile | cycles per tile", "  ".join("%7.2f | %8.1f" % (w[k, 16] / max(w[k, 17], 1), w[k, :16].sum() / max(w[k, 17], 1)) for k in range(4))))
 info = sample.info
 print("input: mean nnz %.1f, %s; shares of nnz %s; kernel %.4f ms" % (mean_nnz, "literal" if literal else "patterns",
       [round(x / info["nnz"], 3) for x in info["stream_nnz"]], fit.stats()["loglik_kernel_ms_avg"]))
