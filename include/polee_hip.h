@@ -550,6 +550,21 @@ polee_status polee_regression_eval(polee_regression *reg, const float *noise_or_
 polee_status polee_regression_set_design(polee_regression *reg, const float *design);
 polee_status polee_regression_set_trainable(polee_regression *reg, int64_t begin, int64_t end);
 polee_status polee_regression_design_grad(polee_regression *reg, float *grad);
+/* Latent design (RNASeqPCA, models/polee_pca.py:14-92): the design matrix is a trained parameter z [S][F] (F = the latent
+ * dimensionality, fixed at creation: at most 16) with a Normal(0, prior_scale) prior (latent_space_model_fn, :52-56) and a point
+ * (Deterministic) surrogate (:58-59), so every evaluation adds -log p(z) = sum z^2 / (2 sigma^2) + log sigma + log(2 pi) / 2 to the
+ * loss (polee_regression_eval and the loss trace), and polee_regression_fit trains z with an Adam of its own (the same constants,
+ * step clock and rate as the flat parameters; polee_regression_set_trainable does not govern it) inside the step: no host work
+ * between steps.
+ *   _set_latent_design  uploads z0, f32 [S][F], zeroes z's Adam moments and turns the mode on; prior_scale must be positive and
+ *                       finite.  Transcript-level model on one GPU, with a likelihood handle or point estimates (the conditions of
+ *                       polee_regression_set_design; anything else POLEE_ERR_UNSUPPORTED).
+ *                       (F is fixed by polee_regression_create, which refuses more than 16 factors with POLEE_ERR_UNSUPPORTED.)
+ *   _get_design         the current design matrix (z on a latent handle), f32 [S][F].
+ * On a latent handle polee_regression_set_design replaces z and leaves its moments alone, and polee_regression_design_grad returns
+ * the TOTAL d loss / dz, prior term z / sigma^2 included (on other handles: the observation model's term, as above). */
+polee_status polee_regression_set_latent_design(polee_regression *reg, const float *z0, float prior_scale);
+polee_status polee_regression_get_design(polee_regression *reg, float *design);
 /* niter steps of fit() (models/polee_regression.py:303-340): draw, loss + gradient, Adam(2e-3, 0.9, 0.999, 1e-7).
  * noise (optional, tests): host [niter][num_noise].  loss_trace (optional): f32 [niter]. */
 polee_status polee_regression_fit(polee_regression *reg, int32_t niter, uint64_t seed, const float *noise_or_null,

@@ -893,6 +893,18 @@ function design_gradient(r::Regression, S::Integer, F::Integer)
     GC.@preserve g check(ccall((:polee_regression_design_grad, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), r.h, g), r.ctx.h)
     return permutedims(g)
 end
+# RNASeqPCA (models/polee_pca.py:14-92), the device part: the design matrix becomes a trained latent z [S x F] with a Normal(0,
+# prior_scale) prior and a point surrogate; fit! then trains it on the device with the flat parameters, and design_gradient returns the
+# total d loss / dz (prior term included).  get_design returns the current z (any handle: its design matrix).
+function set_latent_design!(r::Regression, z0::Matrix{Float32}, prior_scale::Real=1.0)
+    z = permutedims(z0)  # C order [S][F]
+    GC.@preserve z check(ccall((:polee_regression_set_latent_design, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cfloat), r.h, z, Float32(prior_scale)), r.ctx.h)
+end
+function get_design(r::Regression, S::Integer, F::Integer)
+    d = Matrix{Float32}(undef, F, S)
+    GC.@preserve d check(ccall((:polee_regression_get_design, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), r.h, d), r.ctx.h)
+    return permutedims(d)
+end
 
 "the kernel-regression weights of the mean-variance prior, Float32 [degree*n] (models/polee_regression.py:436-460)"
 function regression_weights(r::Regression, degree::Integer=15)

@@ -12,6 +12,7 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   ApproxLikelihoodSampler / rand!                                            src/approx-sampler.jl
   RNASeqApproxLikelihood(...).log_prob, rnaseq_approx_likelihood_sampler     src/polee_approx_likelihood.py
   RNASeqLinearRegression / RNASeqTranscriptLinearRegression(...).fit         models/polee_regression.py
+  RNASeqPCA(...).fit (`polee model pca`)                                     models/polee_pca.py, models/pca.jl
   build_likelihood_matrix (X from alignments, SimplisticFragModel)           src/rnaseq_sample.jl:58-121, src/fragmodel.jl
   gibbs_sampler / GibbsSampler (`polee debug-sample`)                        src/gibbs.jl, src/main.jl:925-957
   expectation_maximization / EM (`polee debug-optimize`)                     src/em.jl, src/main.jl:960-988
@@ -33,6 +34,7 @@ from . import h5io, estimate  # noqa: F401,E402
 from .estimate import LoadedSamples, load_samples_from_specification, load_samples_hdf5, read_specification  # noqa: F401,E402
 from .regression import (RNASeqLinearRegression, RNASeqTranscriptLinearRegression, RNASeqNormalTranscriptLinearRegression, RNASeqGeneLinearRegression, RNASeqGeneIsoformLinearRegression, RNASeqJointLinearRegression, estimate_sample_scales,  # noqa: F401,E402
                          find_minimum_effect_size, write_regression_effects)
+from .pca import RNASeqPCA  # noqa: F401,E402
 from .salmon import load_salmon_likelihood, SalmonLikelihood  # noqa: F401,E402
 from .cohort import approximate_likelihood_cohort, approximate_likelihood_cohort_processes  # noqa: F401,E402
 from .xbuild import build_likelihood_matrix  # noqa: F401,E402

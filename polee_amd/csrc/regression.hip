@@ -810,6 +810,43 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_design_grad_kernel(RegView v, c
     }
 }
 
+// ---- latent design (RNASeqPCA, models/polee_pca.py:14-92): the design matrix is a parameter z [S][F] with a Normal(0, sigma) prior
+// (latent_space_model_fn, :52-56) and a Deterministic surrogate (:58-59, log q = 0).  One workgroup, behind everything that reads the
+// design in the step and behind reg_finish_kernel (which writes loss[0] and Adam's rate), in front of reg_adam_kernel (which copies
+// loss[0] to the trace):  gz = sum of the slot copies of d(-log p)/dz + z / sigma^2 (the copies are left at zero for the next step: no
+// memset between steps), loss += sum z^2 / (2 sigma^2) + log sigma + log(2 pi) / 2, and (update) Adam with reg_adam_kernel's constants
+// and the step's bias-corrected rate lr_dev[0], z in place.
+__global__ __launch_bounds__(256) void reg_latent_kernel(int SF, float *__restrict__ dz, float *__restrict__ z, float *__restrict__ m,
+                                                         float *__restrict__ vv, float *__restrict__ gz, float inv_var, float nlp0,
+                                                         const float *lr_dev, float *loss, int update)
+{
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    double l = 0.0;
+    for (int i = tid; i < SF; i += 256) {
+        float gi = 0.0f;
+        for (int k = 0; k < REG_SLOTS; ++k) {
+            gi += dz[(int64_t)k * SF + i];
+            dz[(int64_t)k * SF + i] = 0.0f;
+        }
+        const float zi = z[i];
+        gi += zi * inv_var;
+        gz[i] = gi;
+        l += (double)(0.5f * zi * zi * inv_var + nlp0);
+        if (update) {
+            const float mi = 0.9f * m[i] + 0.1f * gi;
+            const float vi = 0.999f * vv[i] + 0.001f * gi * gi;
+            m[i] = mi;
+            vv[i] = vi;
+            z[i] = zi - lr_dev[0] * mi / (sqrtf(vi) + 1e-7f);
+        }
+    }
+    l = wave_sum_to_lane63(l);
+    if ((tid & 63) == 63) red[tid >> 6] = l;
+    __syncthreads();
+    if (tid == 0) loss[0] = (float)((double)loss[0] + red[0] + red[1] + red[2] + red[3]);
+}
+
 }  // namespace polee
 
 using namespace polee;
@@ -872,6 +909,11 @@ struct polee_regression {
     // evaluation also leaves d loss / d design in d_dF, and Adam only moves the flat parameters [train_lo, train_hi)
     bool want_dgrad = false;
     DevBuf<float> d_dF;  // [REG_SLOTS][S][F]
+    // latent design (polee_regression_set_latent_design; RNASeqPCA, models/polee_pca.py:14-92): d_design is the parameter z with its own
+    // Adam moments; every evaluation leaves d loss / dz (prior term included) in d_gz and fit() trains z on the device
+    bool latent = false;
+    float prior_scale = 1.0f;
+    DevBuf<float> d_zm, d_zv, d_gz;  // [S][F]
     int64_t train_lo = 0, train_hi = -1;  // (-1: all of them)
 };
 
@@ -984,19 +1026,29 @@ polee_status reg_prior_pass(polee_regression *r)
 }
 
 // loss and gradient at the current parameters for the noise in d_eps
-polee_status reg_eval_device(polee_regression *r)
+// (update_latent: a step of fit() -- reg_latent_kernel also applies Adam to a latent design)
+polee_status reg_eval_device(polee_regression *r, bool update_latent = false)
 {
     POLEE_TRY(reg_data_pass(r));
     if (r->want_dgrad) {
         const RegView &v = r->v;
-        POLEE_HIP_TRY(r->ctx, hipMemsetAsync(r->d_dF.p, 0, sizeof(float) * (size_t)REG_SLOTS * v.S * v.F, r->ctx->stream));
+        if (!r->latent)  // (a latent handle's copies are zero here: reg_latent_kernel clears what it reads)
+            POLEE_HIP_TRY(r->ctx, hipMemsetAsync(r->d_dF.p, 0, sizeof(float) * (size_t)REG_SLOTS * v.S * v.F, r->ctx->stream));
         hipLaunchKernelGGL(reg_design_grad_kernel, dim3((unsigned)ceil_div(v.n, REG_BLOCK)), dim3(REG_BLOCK), 0, r->ctx->stream, v,
                            r->d_p.p, r->d_eps.p, r->d_design.p, r->d_W.p, r->d_ss.p, r->d_x.p, r->d_dF.p);
         POLEE_KERNEL_CHECK(r->ctx);
     }
     if (r->comm && r->comm->nranks > 1)
         POLEE_TRY(comm_allreduce_device(r->comm, r->d_stats.p, (size_t)r->num_stats(), false));
-    return reg_prior_pass(r);
+    POLEE_TRY(reg_prior_pass(r));
+    if (r->latent) {
+        const float sg = r->prior_scale;
+        hipLaunchKernelGGL(reg_latent_kernel, dim3(1), dim3(256), 0, r->ctx->stream, r->v.S * r->v.F, r->d_dF.p, r->d_design.p,
+                           r->d_zm.p, r->d_zv.p, r->d_gz.p, 1.0f / (sg * sg), logf(sg) + HALF_LOG2PI, (const float *)r->d_lr.p,
+                           r->d_loss.p, update_latent ? 1 : 0);
+        POLEE_KERNEL_CHECK(r->ctx);
+    }
+    return POLEE_OK;
 }
 
 // The latents every rank shares are drawn from (seed, step) alone, so that replicas stay identical; the noise of
@@ -1032,7 +1084,7 @@ polee_status reg_enqueue_step(polee_regression *r, const float *noise, bool want
     if (noise) {  // the caller's noise: uploaded; the clock ticks in its own launch
         hipLaunchKernelGGL(reg_tick_kernel, dim3(1), dim3(1), 0, ctx->stream, r->d_tick.p, r->d_lr.p, r->lr);
         POLEE_TRY(reg_fill_noise(r, noise, 0, 0, true));
-        POLEE_TRY(reg_eval_device(r));
+        POLEE_TRY(reg_eval_device(r, r->latent));
     } else {
         // device RNG: one launch draws every latent of the step number the clock is ABOUT to show and x with it; the clock is
         // advanced by reg_finish_kernel (in front of Adam, behind everything that reads the noise)
@@ -1048,7 +1100,7 @@ polee_status reg_enqueue_step(polee_regression *r, const float *noise, bool want
                                salt ^ 0x69736f666f726d73ull, r->d_ieps.p, 1u);
         r->tick_in_finish = true;
         r->x_drawn = with_x;
-        const polee_status es = reg_eval_device(r);
+        const polee_status es = reg_eval_device(r, r->latent);
         r->tick_in_finish = false;
         r->x_drawn = false;
         POLEE_TRY(es);
@@ -1230,6 +1282,7 @@ polee_status polee_regression_set_gene_likelihood(polee_regression *r, polee_app
     if (approx_ctx(ap) != ctx || aS != r->v.S)
         return fail(ctx, POLEE_ERR_BAD_ARG, "the approximation handle holds %d samples, the model %d", aS, r->v.S);
     if (r->v.point) return fail(ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is built without point estimates only");
+    if (r->latent) return fail(ctx, POLEE_ERR_UNSUPPORTED, "a latent design belongs to the transcript-level model only");
     if (r->comm && r->comm->nranks > 1)
         return fail(ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is not sharded over ranks");
     POLEE_TRY(approx_set_genes(ap, gene_of, r->v.n));  // the model's features are the genes
@@ -1437,6 +1490,8 @@ polee_status polee_regression_set_comm(polee_regression *r, polee_comm *comm)
     if (!r) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
     if (comm && comm->nranks > 1 && r->gene_ap)
         return fail(r->ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is not sharded over ranks");
+    if (comm && comm->nranks > 1 && r->latent)
+        return fail(r->ctx, POLEE_ERR_UNSUPPORTED, "a model with a latent design is not sharded over ranks");
     if (comm && comm->ctx != r->ctx)
         return fail(r->ctx, POLEE_ERR_BAD_ARG, "communicator and model belong to different contexts");
     if (comm) ++comm->refs;
@@ -1489,6 +1544,41 @@ polee_status polee_regression_set_design(polee_regression *r, const float *desig
     return r->d_design.upload(ctx, design, (size_t)r->v.S * r->v.F);  // (same buffer: a captured step reads the new values)
 }
 
+// ---- latent design (RNASeqPCA, models/polee_pca.py:14-92) --------------------------------------------------------------------------
+polee_status polee_regression_set_latent_design(polee_regression *r, const float *z0, float prior_scale)
+{
+    if (!r || !z0) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
+    polee_ctx *ctx = r->ctx;
+    POLEE_TRY(use_device(ctx));
+    if (r->gene_ap || r->v.fixed_ab > 0.0f || (r->comm && r->comm->nranks > 1))
+        return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_regression_set_latent_design: the transcript-level model on one GPU only");
+    if (!(prior_scale > 0.0f) || !std::isfinite(prior_scale))
+        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_latent_design: prior_scale = %g is not a positive finite number",
+                    (double)prior_scale);
+    const size_t SF = (size_t)r->v.S * r->v.F;
+    r->drop_graph();  // (the captured step loses a memset and gains the update)
+    POLEE_TRY(r->d_dF.alloc(ctx, (size_t)REG_SLOTS * SF));
+    POLEE_TRY(r->d_zm.alloc(ctx, SF));
+    POLEE_TRY(r->d_zv.alloc(ctx, SF));
+    POLEE_TRY(r->d_gz.alloc(ctx, SF));
+    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_dF.p, 0, sizeof(float) * REG_SLOTS * SF, ctx->stream));
+    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_zm.p, 0, sizeof(float) * SF, ctx->stream));
+    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_zv.p, 0, sizeof(float) * SF, ctx->stream));
+    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_gz.p, 0, sizeof(float) * SF, ctx->stream));
+    POLEE_TRY(r->d_design.upload(ctx, z0, SF));
+    r->want_dgrad = true;
+    r->latent = true;
+    r->prior_scale = prior_scale;
+    return POLEE_OK;
+}
+
+polee_status polee_regression_get_design(polee_regression *r, float *design)
+{
+    if (!r || !design) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_regression_get_design: null argument");
+    POLEE_TRY(use_device(r->ctx));
+    return r->d_design.download(r->ctx, design, (size_t)r->v.S * r->v.F);
+}
+
 polee_status polee_regression_set_trainable(polee_regression *r, int64_t begin, int64_t end)
 {
     if (!r) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
@@ -1506,6 +1596,7 @@ polee_status polee_regression_design_grad(polee_regression *r, float *grad)
     POLEE_TRY(use_device(ctx));
     if (!r->want_dgrad) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_design_grad: call polee_regression_set_design first");
     const size_t SF = (size_t)r->v.S * r->v.F;
+    if (r->latent) return r->d_gz.download(ctx, grad, SF);  // (the total, prior term included: reg_latent_kernel)
     std::vector<float> h(SF * REG_SLOTS);
     POLEE_TRY(r->d_dF.download(ctx, h.data(), h.size()));
     for (size_t i = 0; i < SF; ++i) {

@@ -54,6 +54,12 @@ def _softplus(x):
     return np.logaddexp(0.0, x).astype(np.float32)
 
 
+def choose_knots(low, high, degree):
+    """choose_knots (src/polee.py:69-76): `degree` hinges evenly inside (low, high)"""
+    low, high, degree = float(low), float(high), int(degree)
+    return np.array([low + (k + 1) * (high - low) / (degree + 1) for k in range(degree)], np.float32)
+
+
 def estimate_sample_scales(x, upper_quantile=0.95):
     """src/PoleeModel.jl:82-89: per-sample offsets from the highly expressed features; x [S, n] log expression.
     Returns [S, 1] like the reference."""
@@ -256,6 +262,22 @@ class RNASeqLinearRegression:
         check(L.lib().polee_regression_design_grad(self._h, ptr(g, f32p)), self.ctx._h)
         return g
 
+    # ---- latent design (RNASeqPCA, models/polee_pca.py:14-92)
+    def set_latent_design(self, z0, prior_scale=1.0):
+        """The design matrix becomes a parameter z [S, F] with a Normal(0, prior_scale) prior and a point surrogate: every evaluation
+        adds -log p(z), fit() trains z on the device, design_gradient() returns the total d loss / dz."""
+        z = arr(np.atleast_2d(z0), np.float32)
+        if z.shape != (self.num_samples, self.num_factors):
+            raise ValueError("z0 must be [S, F]")
+        check(L.lib().polee_regression_set_latent_design(self._h, ptr(z, f32p), C.c_float(prior_scale)), self.ctx._h)
+        self.design = z
+
+    def get_design(self):
+        """The design matrix on the device, [S, F] (the trained z after set_latent_design)."""
+        d = np.empty((self.num_samples, self.num_factors), np.float32)
+        check(L.lib().polee_regression_get_design(self._h, ptr(d, f32p)), self.ctx._h)
+        return d
+
     def _shared_size(self):
         """flat parameters in front of qx_loc: everything the samples share (the layout of include/polee_hip.h)"""
         F, n, d = self.num_factors, self.num_features, self.kernel_regression_degree
@@ -319,9 +341,8 @@ class RNASeqLinearRegression:
 
     def _default_hinges(self):
         """choose_knots (src/polee.py:69-76) over the training samples' column means, as polee_regression_create derives them"""
-        mean, d = self._ctor["x_init_mean"], self.kernel_regression_degree
-        lo, hi = float(mean.min()), float(mean.max())
-        return np.array([lo + (k + 1) * (hi - lo) / (d + 1) for k in range(d)], np.float32)
+        mean = self._ctor["x_init_mean"]
+        return choose_knots(mean.min(), mean.max(), self.kernel_regression_degree)
 
     def fit(self, niter, seed=123456789, noise=None, return_trace=False):
         """fit (models/polee_regression.py:303-340): returns (qx_loc, qw_loc, qw_scale, qx_bias_loc, qx_scale)."""
