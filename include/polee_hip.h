@@ -812,6 +812,65 @@ polee_status polee_sampler_mean(polee_sampler *s, float *post_mean, double *est_
 polee_status polee_multinomial_counts(polee_ctx *ctx, const double *p, int32_t D, int64_t n, int64_t m, uint64_t seed,
                                       uint64_t first_draw, uint32_t *counts);
 
+/* ---- `polee model classify` (models/classify.jl, models/polee_classify.py:13-114; csrc/classify.hip) ------
+ * RNASeqLogisticRegression: a multinomial logistic regression on log expression.  Parameters w [n][k], x_bias [n], z_bias [k], all
+ * zero at creation (:18-20) and all trained.  logits = (x - x_bias) w + z_bias;
+ *   loss = loss_scale sum_s CE(labels_s, softmax(logits_s)) + l1_penalty sum |w|          (:22-41; the penalty is not scaled)
+ * and with an approximation handle the mean of that loss over draws_per_step draws x = log(sampler draw) (loss_sample, :43-49), so the
+ * penalty counts once; no gradient flows through the sampler.  The penalty's gradient is l1_penalty sign(w), sign(0) = 0 (tf.abs).
+ * The draws never leave the device; all sums have a fixed order (no float atomics): every result is bitwise reproducible.
+ * Draw rule: the draw with index i uses seed + 0x9E3779B97F4A7C15 i (as polee_approx_feature_moments).  In polee_classify_fit,
+ * i = (t - 1) D + d for draw d of Adam step t, D = draws_per_step, and t is the handle's step clock, which runs on across calls:
+ * fit(2) then fit(3) equals fit(5).  polee_classify_eval and polee_classify_predict use i = their own draw number.
+ * Every `ap` must live on the handle's context and have its n (else POLEE_ERR_BAD_ARG); S is the approximation's.  Label rows must be
+ * one-hot (else POLEE_ERR_BAD_ARG).  On the point paths x [S][n] is log expression already and must be finite: POLEE_ERR_NONFINITE
+ * otherwise (the reference takes log 0 silently when a TPM is 0 and no pseudocount is given, classify.jl:141-147). */
+typedef struct polee_classify polee_classify;
+typedef struct {
+    int32_t draws_per_step; /* samples_per_iter, 5 (polee_classify.py:51) */
+    float learning_rate;    /* 1e-4 (:69, :92) */
+    float l1_penalty;       /* 1e-3 (:29-30) */
+    float loss_scale;       /* 1 (:22) */
+    float beta1, beta2, epsilon; /* tf.optimizers.Adam: 0.9, 0.999, 1e-7 */
+} polee_classify_opts;
+void polee_classify_default_opts(polee_classify_opts *opts);
+/* 2 <= k <= 16, anything else POLEE_ERR_UNSUPPORTED; opts NULL = the defaults (polee_classify.py:14-20) */
+polee_status polee_classify_create(polee_ctx *ctx, int32_t n, int32_t k, const polee_classify_opts *opts, polee_classify **out);
+void polee_classify_destroy(polee_classify *cl);
+/* new options from the next call on (fit's loss_scale, :74; fit_sample's samples_per_iter, :51); moments and clock stay */
+polee_status polee_classify_set_opts(polee_classify *cl, const polee_classify_opts *opts);
+/* w f32 [n][k], x_bias f32 [n], z_bias f32 [k] (get: each may be NULL); set leaves the Adam moments and the step clock alone */
+polee_status polee_classify_get_params(polee_classify *cl, float *w, float *x_bias, float *z_bias);
+polee_status polee_classify_set_params(polee_classify *cl, const float *w, const float *x_bias, const float *z_bias);
+/* Adam moments and step clock back to zero (a fresh tf.optimizers.Adam, :66-70) */
+polee_status polee_classify_reset(polee_classify *cl);
+/* x_bias <- the column mean over samples of the log of ONE draw (:52-55); z0_or_null f32 [S][n-1]: the draw's N(0,1) noise */
+polee_status polee_classify_init_bias(polee_classify *cl, polee_approx *ap, const float *z0_or_null, uint64_t seed);
+/* x_bias <- the column mean of x f32 [S][n] (:75) */
+polee_status polee_classify_init_bias_points(polee_classify *cl, const float *x, int32_t S);
+/* loss_sample (:43-49) and its gradient, penalty term included, no update: exactly the numbers a fit step feeds to Adam (the same
+ * kernels in the same order).  labels f32 [S][k]; z0_or_null f32 [D][S][n-1]; g_w [n][k], g_x_bias [n], g_z_bias [k], each may be NULL */
+polee_status polee_classify_eval(polee_classify *cl, polee_approx *ap, const float *labels, const float *z0_or_null, uint64_t seed,
+                                 float *loss, float *g_w, float *g_x_bias, float *g_z_bias);
+/* loss (:22-41) on a fixed x f32 [S][n] */
+polee_status polee_classify_eval_points(polee_classify *cl, const float *x, int32_t S, const float *labels, float *loss, float *g_w,
+                                        float *g_x_bias, float *g_z_bias);
+/* niter Adam steps on fresh draws (fit_sample :57-72, without the bias initialisation: polee_classify_init_bias); lr_t = lr
+ * sqrt(1 - beta2^t) / (1 - beta1^t), p -= lr_t m / (sqrt(v) + epsilon).  z0_or_null f32 [niter][D][S][n-1], uploaded once;
+ * loss_trace_or_null f32 [niter].  Nothing waits for the device until the last step is queued.  A call that fails partway keeps
+ * the updates of the steps it completed, advances the clock by those, and leaves the accumulators at zero. */
+polee_status polee_classify_fit(polee_classify *cl, polee_approx *ap, const float *labels, int32_t niter, uint64_t seed,
+                                const float *z0_or_null, float *loss_trace_or_null);
+/* fit (:74-95) on a fixed x, without the bias initialisation (polee_classify_init_bias_points) */
+polee_status polee_classify_fit_points(polee_classify *cl, const float *x, int32_t S, const float *labels, int32_t niter,
+                                       float *loss_trace_or_null);
+/* predict_sample (:105-111): the mean over ndraws draws of softmax(logits), accumulated in f64; z0_or_null f32 [ndraws][S][n-1];
+ * probs f32 [S][k] */
+polee_status polee_classify_predict(polee_classify *cl, polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0_or_null,
+                                    float *probs);
+/* predict (:113-114) */
+polee_status polee_classify_predict_points(polee_classify *cl, const float *x, int32_t S, float *probs);
+
 #ifdef __cplusplus
 }
 #endif

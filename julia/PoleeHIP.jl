@@ -1248,4 +1248,112 @@ function multinomial_counts(ctx::Context, p::Matrix{Float64}, m::Integer; seed::
     return out
 end
 
+# ---- `polee model classify` (models/classify.jl, models/polee_classify.py:13-114): logistic regression on posterior draws -----------
+"mirror of `polee_classify_opts` (include/polee_hip.h): field order and types must stay in step with the header"
+mutable struct ClassifyOpts
+    draws_per_step::Int32
+    learning_rate::Float32; l1_penalty::Float32; loss_scale::Float32
+    beta1::Float32; beta2::Float32; epsilon::Float32
+    function ClassifyOpts()
+        o = new()
+        ccall((:polee_classify_default_opts, LIB), Cvoid, (Ref{ClassifyOpts},), o)
+        return o
+    end
+end
+
+"RNASeqLogisticRegression (polee_classify.py:13-20); matrices are row-major vectors: w [n*k] (transcript by transcript), labels and
+probabilities [S*k] (sample by sample)"
+mutable struct LogisticRegression
+    h::Ptr{Cvoid}
+    ctx::Context
+    n::Int
+    k::Int
+end
+function LogisticRegression(ctx::Context, k::Integer, n::Integer; opts::ClassifyOpts=ClassifyOpts())
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:polee_classify_create, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ref{ClassifyOpts}, Ref{Ptr{Cvoid}}), ctx.h, n, k, opts, r),
+          ctx.h)
+    cl = LogisticRegression(r[], ctx, n, k)
+    finalizer(x -> ccall((:polee_classify_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), cl)
+    return cl
+end
+set_opts!(cl::LogisticRegression, opts::ClassifyOpts) =
+    check(ccall((:polee_classify_set_opts, LIB), Cint, (Ptr{Cvoid}, Ref{ClassifyOpts}), cl.h, opts), cl.ctx.h)
+"(w [n*k], x_bias [n], z_bias [k])"
+function get_params(cl::LogisticRegression)
+    w = Vector{Float32}(undef, cl.n * cl.k); xb = Vector{Float32}(undef, cl.n); zb = Vector{Float32}(undef, cl.k)
+    GC.@preserve w xb zb check(ccall((:polee_classify_get_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                                     cl.h, w, xb, zb), cl.ctx.h)
+    return w, xb, zb
+end
+function set_params!(cl::LogisticRegression, w::Vector{Float32}, x_bias::Vector{Float32}, z_bias::Vector{Float32})
+    GC.@preserve w x_bias z_bias check(ccall((:polee_classify_set_params, LIB), Cint,
+                                             (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), cl.h, w, x_bias, z_bias), cl.ctx.h)
+end
+"Adam moments and step clock back to zero"
+reset!(cl::LogisticRegression) = check(ccall((:polee_classify_reset, LIB), Cint, (Ptr{Cvoid},), cl.h), cl.ctx.h)
+"x_bias <- column mean of the log of one draw (polee_classify.py:52-55)"
+function init_bias!(cl::LogisticRegression, ap::ApproxLikelihood; seed::Integer=0, z0::Union{Nothing,Vector{Float32}}=nothing)
+    GC.@preserve z0 check(ccall((:polee_classify_init_bias, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, UInt64), cl.h, ap.h,
+                                z0 === nothing ? C_NULL : pointer(z0), seed), cl.ctx.h)
+end
+"x_bias <- column mean of x [S*n] (polee_classify.py:75)"
+function init_bias!(cl::LogisticRegression, x::Vector{Float32}, S::Integer)
+    GC.@preserve x check(ccall((:polee_classify_init_bias_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32), cl.h, x, S), cl.ctx.h)
+end
+"loss_sample (polee_classify.py:43-49) and its gradients (loss, g_w [n*k], g_x_bias [n], g_z_bias [k]); no update"
+function loss_and_gradients(cl::LogisticRegression, ap::ApproxLikelihood, labels::Vector{Float32}; seed::Integer=0,
+                            z0::Union{Nothing,Vector{Float32}}=nothing)
+    loss = Ref{Float32}(0)
+    gw = Vector{Float32}(undef, cl.n * cl.k); gxb = Vector{Float32}(undef, cl.n); gzb = Vector{Float32}(undef, cl.k)
+    GC.@preserve labels z0 gw gxb gzb check(
+        ccall((:polee_classify_eval, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, UInt64, Ref{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+              cl.h, ap.h, labels, z0 === nothing ? C_NULL : pointer(z0), seed, loss, gw, gxb, gzb), cl.ctx.h)
+    return loss[], gw, gxb, gzb
+end
+"loss (polee_classify.py:22-41) and its gradients on a fixed x [S*n]"
+function loss_and_gradients(cl::LogisticRegression, x::Vector{Float32}, S::Integer, labels::Vector{Float32})
+    loss = Ref{Float32}(0)
+    gw = Vector{Float32}(undef, cl.n * cl.k); gxb = Vector{Float32}(undef, cl.n); gzb = Vector{Float32}(undef, cl.k)
+    GC.@preserve x labels gw gxb gzb check(
+        ccall((:polee_classify_eval_points, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Float32}, Ref{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+              cl.h, x, S, labels, loss, gw, gxb, gzb), cl.ctx.h)
+    return loss[], gw, gxb, gzb
+end
+"niter Adam steps on fresh draws (fit_sample, polee_classify.py:57-72; call init_bias! first): the loss trace"
+function fit!(cl::LogisticRegression, ap::ApproxLikelihood, labels::Vector{Float32}, niter::Integer; seed::Integer=0,
+              z0::Union{Nothing,Vector{Float32}}=nothing)
+    trace = Vector{Float32}(undef, niter)
+    GC.@preserve labels z0 trace check(
+        ccall((:polee_classify_fit, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Int32, UInt64, Ptr{Float32}, Ptr{Float32}),
+              cl.h, ap.h, labels, niter, seed, z0 === nothing ? C_NULL : pointer(z0), trace), cl.ctx.h)
+    return trace
+end
+"fit (polee_classify.py:74-95) on a fixed x [S*n]"
+function fit!(cl::LogisticRegression, x::Vector{Float32}, S::Integer, labels::Vector{Float32}, niter::Integer)
+    trace = Vector{Float32}(undef, niter)
+    GC.@preserve x labels trace check(
+        ccall((:polee_classify_fit_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Float32}, Int32, Ptr{Float32}),
+              cl.h, x, S, labels, niter, trace), cl.ctx.h)
+    return trace
+end
+"predict_sample (polee_classify.py:105-111): probabilities [S*k], the mean over ndraws draws"
+function predict(cl::LogisticRegression, ap::ApproxLikelihood, ndraws::Integer; seed::Integer=0,
+                 z0::Union{Nothing,Vector{Float32}}=nothing)
+    probs = Vector{Float32}(undef, ap.S * cl.k)
+    GC.@preserve z0 probs check(
+        ccall((:polee_classify_predict, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt64, Ptr{Float32}, Ptr{Float32}),
+              cl.h, ap.h, ndraws, seed, z0 === nothing ? C_NULL : pointer(z0), probs), cl.ctx.h)
+    return probs
+end
+"predict (polee_classify.py:113-114)"
+function predict(cl::LogisticRegression, x::Vector{Float32}, S::Integer)
+    probs = Vector{Float32}(undef, S * cl.k)
+    GC.@preserve x probs check(ccall((:polee_classify_predict_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Float32}),
+                                     cl.h, x, S, probs), cl.ctx.h)
+    return probs
+end
+
 end # module

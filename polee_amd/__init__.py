@@ -13,6 +13,7 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   RNASeqApproxLikelihood(...).log_prob, rnaseq_approx_likelihood_sampler     src/polee_approx_likelihood.py
   RNASeqLinearRegression / RNASeqTranscriptLinearRegression(...).fit         models/polee_regression.py
   RNASeqPCA(...).fit (`polee model pca`)                                     models/polee_pca.py, models/pca.jl
+  RNASeqLogisticRegression (`polee model classify`)                          models/polee_classify.py, models/classify.jl
   build_likelihood_matrix (X from alignments, SimplisticFragModel)           src/rnaseq_sample.jl:58-121, src/fragmodel.jl
   gibbs_sampler / GibbsSampler (`polee debug-sample`)                        src/gibbs.jl, src/main.jl:925-957
   expectation_maximization / EM (`polee debug-optimize`)                     src/em.jl, src/main.jl:960-988
@@ -51,4 +52,7 @@ def __getattr__(name):
     if name in ("ApproxSampleStream", "polee_sample", "multinomial_counts"):
         from . import sample
         return getattr(sample, name)
+    if name in ("RNASeqLogisticRegression", "build_factor_matrix", "write_classification_probs"):
+        from . import classify
+        return getattr(classify, name)
     raise AttributeError("module 'polee_amd' has no attribute %r" % name)

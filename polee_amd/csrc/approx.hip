@@ -684,8 +684,13 @@ polee_status polee_approx_gene_logprob(polee_approx *ap, const float *x_gene, co
     return POLEE_OK;
 }
 
+}  // extern "C"
+
+namespace polee {
+const float *approx_draw_buffer(const polee_approx *ap) { return ap->d_x.p; }
+
 // one draw per sample into ap->d_x (device side of polee_approx_sample); d_z0 [S][n-1] or null
-static polee_status approx_sample_device(polee_approx *ap, const float *d_z0, uint64_t seed)
+polee_status approx_sample_device(polee_approx *ap, const float *d_z0, uint64_t seed)
 {
     polee_ctx *ctx = ap->ctx;
     polee_ptt *t = ap->t;
@@ -706,6 +711,9 @@ static polee_status approx_sample_device(polee_approx *ap, const float *d_z0, ui
     POLEE_KERNEL_CHECK(ctx);
     return POLEE_OK;
 }
+}  // namespace polee
+
+extern "C" {
 
 polee_status polee_approx_sample(polee_approx *ap, const float *z0, uint64_t seed, float *x)
 {

@@ -644,5 +644,9 @@ polee_ctx *approx_ctx(const polee_approx *ap);
 void approx_dims(const polee_approx *ap, int32_t *S, int32_t *n);
 polee_status approx_set_genes(polee_approx *ap, const int32_t *gene_of, int32_t G);
 polee_status approx_gene_logprob_device(polee_approx *ap, const float *d_xg, float *d_xi, float *d_lp, float *d_gg);
+// one draw per sample, f32 [S][n] clipped at 1e-16, into the handle's draw buffer (approx_draw_buffer), queued on the context's
+// stream; d_z0: device f32 [S][n-1], the draw's N(0,1) noise, or null = the device RNG under `seed`
+polee_status approx_sample_device(polee_approx *ap, const float *d_z0, uint64_t seed);
+const float *approx_draw_buffer(const polee_approx *ap);
 
 }  // namespace polee
