@@ -871,6 +871,34 @@ polee_status polee_classify_predict(polee_classify *cl, polee_approx *ap, int32_
 /* predict (:113-114) */
 polee_status polee_classify_predict_points(polee_classify *cl, const float *x, int32_t S, float *probs);
 
+/* ---- isoform effect sizes of `polee model regression --feature gene-isoform` (estimate_isoform_effect_sizes,
+ * src/regression.jl:761-945; csrc/effects.hip) -------------------------------------------------------------
+ * niter Monte-Carlo draws of the isoform bias x_j = zx qx_bias_scale_j + qx_bias_loc_j and of every factor's isoform coefficients
+ * w_ij = zw qw_scale_ij + qw_loc_ij; per draw e_ij = log softmax_g(x + w_i)_j - log softmax_g(x)_j over the transcripts of j's gene
+ * and a_ig = the Aitchison distance of the two compositions of gene g (= the population standard deviation of w_i over the gene).
+ * Over the draws: mean = the mean of e; prob_de = #{e > effect_size} / niter, ONE-SIDED as the reference computes it (:850);
+ * min = the k-th smallest |e|, k = clamp(round-half-even(target_coverage niter), 1, niter) (:912-915), exact.  The gene arrays are
+ * the same over a, with aitchison_prob_de = #{|a| > aitchison_effect_size} / niter (:899).  A NaN threshold: that prob_de is not
+ * computed and comes back as zeros.  Evaluated in log space with a max-subtracted log-sum-exp: finite where the reference's
+ * exp / normalise / log underflows (a gene whose x spans more than ~700).  A gene of one isoform gives exact zeros; a gene without
+ * transcripts gives zero distances.
+ * Noise: Philox4x32-10 keyed by `seed`, counter (transcript, draw, stream / 4), stream 0 = x, 1 + i = w_i: a result depends on
+ * (seed, inputs) alone, bit for bit, on any launch geometry; no float atomics.  zx_or_null f32 [niter][n] and zw_or_null f32
+ * [niter][F][n] replace it (both or neither; zx_len / zw_len are their element counts and must be exactly niter n and niter F n).
+ * POLEE_ERR_BAD_ARG: gene_of outside 0 .. G-1, niter < 1, target_coverage outside (0, 1], noise of the wrong size;
+ * POLEE_ERR_UNSUPPORTED: niter > 4096 (28 bytes of LDS per draw). */
+typedef struct polee_effects polee_effects;
+/* gene_of i32 [n], 0-based, in any order: the transcripts are segmented by gene once, here */
+polee_status polee_effects_create(polee_ctx *ctx, int32_t n, int32_t G, const int32_t *gene_of, int32_t F, polee_effects **out);
+void polee_effects_destroy(polee_effects *fx);
+/* qw_loc, qw_scale f32 [F][n]; qx_bias_loc, qx_bias_scale f32 [n]; outputs f32 [F][n] (three) and f32 [F][G] (three);
+ * kernel_ms_or_null: the kernel's time between two events on the context's stream */
+polee_status polee_effects_run(polee_effects *fx, const float *qw_loc, const float *qw_scale, const float *qx_bias_loc,
+                               const float *qx_bias_scale, int32_t niter, double target_coverage, double effect_size_or_nan,
+                               double aitchison_effect_size_or_nan, uint64_t seed, const float *zx_or_null, int64_t zx_len,
+                               const float *zw_or_null, int64_t zw_len, float *min_effect_sizes, float *mean_effect_sizes, float *prob_de,
+                               float *aitchison_min, float *aitchison_mean, float *aitchison_prob_de, double *kernel_ms_or_null);
+
 #ifdef __cplusplus
 }
 #endif

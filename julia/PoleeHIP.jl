@@ -1356,4 +1356,44 @@ function predict(cl::LogisticRegression, x::Vector{Float32}, S::Integer)
     return probs
 end
 
+# ---- isoform effect sizes (estimate_isoform_effect_sizes, src/regression.jl:761-945; csrc/effects.hip) -----------------------------
+"the transcripts of `gene_of` (0-based gene of every transcript, any order) segmented by gene once, on creation"
+mutable struct IsoformEffects
+    h::Ptr{Cvoid}
+    ctx::Context
+    n::Int
+    G::Int
+    F::Int
+end
+function IsoformEffects(ctx::Context, gene_of::Vector{Int32}, G::Integer, F::Integer)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve gene_of check(ccall((:polee_effects_create, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Int32, Ref{Ptr{Cvoid}}),
+                                     ctx.h, length(gene_of), G, gene_of, F, r), ctx.h)
+    fx = IsoformEffects(r[], ctx, length(gene_of), G, F)
+    finalizer(x -> ccall((:polee_effects_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), fx)
+    return fx
+end
+"(min_effect_sizes, mean_effect_sizes, prob_de [F*n], aitchison_min, aitchison_mean, aitchison_prob_de [F*G], kernel ms), row-major
+vectors; a threshold of `nothing` leaves its prob_de at zero; prob_de is one-sided, #{e > effect_size} / niter (:850); zx [niter*n]
+and zw [niter*F*n] replace the device's noise"
+function estimate_isoform_effect_sizes(fx::IsoformEffects, qw_loc::Vector{Float32}, qw_scale::Vector{Float32},
+                                       qx_bias_loc::Vector{Float32}, qx_bias_scale::Vector{Float32}; niter::Integer=1000,
+                                       target_coverage::Real=0.1, effect_size::Union{Nothing,Real}=nothing,
+                                       aitchison_effect_size::Union{Nothing,Real}=nothing, seed::Integer=0,
+                                       zx::Union{Nothing,Vector{Float32}}=nothing, zw::Union{Nothing,Vector{Float32}}=nothing)
+    mn = Vector{Float32}(undef, fx.F * fx.n); me = similar(mn); pr = similar(mn)
+    amn = Vector{Float32}(undef, fx.F * fx.G); ame = similar(amn); apr = similar(amn)
+    ms = Ref{Float64}(0)
+    GC.@preserve qw_loc qw_scale qx_bias_loc qx_bias_scale zx zw mn me pr amn ame apr check(
+        ccall((:polee_effects_run, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Float64, Float64, Float64, UInt64,
+               Ptr{Float32}, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
+               Ptr{Float32}, Ref{Float64}),
+              fx.h, qw_loc, qw_scale, qx_bias_loc, qx_bias_scale, niter, target_coverage,
+              effect_size === nothing ? NaN : Float64(effect_size), aitchison_effect_size === nothing ? NaN : Float64(aitchison_effect_size),
+              seed, zx === nothing ? C_NULL : pointer(zx), zx === nothing ? 0 : length(zx), zw === nothing ? C_NULL : pointer(zw),
+              zw === nothing ? 0 : length(zw), mn, me, pr, amn, ame, apr, ms), fx.ctx.h)
+    return mn, me, pr, amn, ame, apr, ms[]
+end
+
 end # module

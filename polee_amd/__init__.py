@@ -12,6 +12,8 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   ApproxLikelihoodSampler / rand!                                            src/approx-sampler.jl
   RNASeqApproxLikelihood(...).log_prob, rnaseq_approx_likelihood_sampler     src/polee_approx_likelihood.py
   RNASeqLinearRegression / RNASeqTranscriptLinearRegression(...).fit         models/polee_regression.py
+  estimate_isoform_effect_sizes, build_design_matrix, gene_map               src/regression.jl, src/PoleeModel.jl:165-263
+  (`polee model regression`: python -m polee_amd.regression)
   RNASeqPCA(...).fit (`polee model pca`)                                     models/polee_pca.py, models/pca.jl
   RNASeqLogisticRegression (`polee model classify`)                          models/polee_classify.py, models/classify.jl
   build_likelihood_matrix (X from alignments, SimplisticFragModel)           src/rnaseq_sample.jl:58-121, src/fragmodel.jl
@@ -55,4 +57,8 @@ def __getattr__(name):
     if name in ("RNASeqLogisticRegression", "build_factor_matrix", "write_classification_probs"):
         from . import classify
         return getattr(classify, name)
+    if name in ("IsoformEffects", "estimate_isoform_effect_sizes", "build_design_matrix", "gene_map", "gene_initial_values",
+                "write_isoform_regression_effects", "write_aitchison_results", "write_expression", "load_kallisto_estimates"):
+        from . import regression
+        return getattr(regression, name)
     raise AttributeError("module 'polee_amd' has no attribute %r" % name)

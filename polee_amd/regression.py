@@ -4,6 +4,18 @@ Same class names, constructor arguments and return values as the reference; the 
 joint distributions and fit_surrogate_posterior are replaced by the device step in csrc/regression.hip.
 Also: estimate_sample_scales (src/PoleeModel.jl:82-89) and the effect-size output semantics
 (src/regression.jl:604-685).
+
+`polee model regression` (src/regression.jl:19-601):
+
+    python -m polee_amd.regression experiment.yml [--feature transcript | gene | gene-isoform] [--gene-pattern REGEX | --gene-annotations
+        genes.yml] [--factors a,b] [--nonredundant] [--balanced] [--kallisto | --kallisto-bootstrap | --point-estimates KEY] ...
+
+writes regression-coefficients.csv and, for gene-isoform, regression-isoform-coefficients.csv with the isoform effect sizes of
+estimate_isoform_effect_sizes (:761-945), which run on the device (csrc/effects.hip).  Departures from the reference: factors and
+options of the design matrix come in sorted order; genes come from --gene-pattern / --gene-annotations (no GFF reader); without
+--isoform-effect-size, where the reference fails in log(abs(nothing)), prob_de is not computed and its column is left out;
+--output-expression with --feature gene-isoform, where the reference fails on an undefined qx_loc, writes the genes' expression
+(the gene block's qx_loc, labelled gene_id,gene_name); --feature splice-feature is not built.
 """
 import ctypes as C
 import math
@@ -625,3 +637,467 @@ def write_regression_effects(output_filename, factor_names, feature_names_label,
                 if write_variational_posterior_params:
                     out.write(",%f,%f,%f,%f" % (qx_bias[j], qx_scale[j], loc, sc))
                 out.write("\n")
+
+
+# ---- isoform effect sizes (src/regression.jl:761-945; csrc/effects.hip)
+EFFECT_DRAWS = 1000      # niter of estimate_isoform_effect_sizes (:766)
+MAX_EFFECT_DRAWS = 4096  # the kernel keeps 28 bytes of LDS per draw (csrc/effects.hip)
+DEFAULT_SEED = 123456789
+_MASK = (1 << 64) - 1
+
+
+class IsoformEffects:
+    """The device handle polee_effects_* (include/polee_hip.h): the transcripts of n are segmented by gene once; run() makes the
+    Monte-Carlo draws and returns the six arrays.  gene_of: the 0-based gene of every transcript, in any order."""
+
+    def __init__(self, gene_of, num_genes, num_factors, ctx=None):
+        g = arr(np.asarray(gene_of).reshape(-1), np.int32)
+        self.n, self.G, self.F = g.size, int(num_genes), int(num_factors)
+        self.ctx = ctx or default_context()
+        self._h = C.c_void_p()
+        self.kernel_ms = None
+        check(L.lib().polee_effects_create(self.ctx._h, self.n, self.G, ptr(g, L.i32p), self.F, C.byref(self._h)), self.ctx._h)
+
+    def __del__(self):
+        try:
+            if self._h:
+                f = L.lib().polee_effects_destroy
+                f.restype, f.argtypes = None, [C.c_void_p]
+                f(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def run(self, qw_loc, qw_scale, qx_bias_loc, qx_bias_scale, niter=EFFECT_DRAWS, target_coverage=0.1, effect_size=None,
+            aitchison_effect_size=None, seed=DEFAULT_SEED, zx=None, zw=None):
+        """(min_effect_sizes, mean_effect_sizes, prob_de [F, n], aitchison_min, aitchison_mean, aitchison_prob_de [F, G]), f32; a
+        prob_de whose threshold is None is None.  effect_size is compared as given (the caller takes log |S|).  zx [niter, n] and
+        zw [niter, F, n] replace the device's noise.  self.kernel_ms: the kernel's time between two stream events."""
+        F, n, G = self.F, self.n, self.G
+        wl, ws = arr(np.atleast_2d(qw_loc), np.float32), arr(np.atleast_2d(qw_scale), np.float32)
+        bl, bs = arr(qx_bias_loc, np.float32).reshape(-1), arr(qx_bias_scale, np.float32).reshape(-1)
+        if wl.shape != (F, n) or ws.shape != (F, n) or bl.size != n or bs.size != n:
+            raise ValueError("expected qw_loc and qw_scale [%d, %d], qx_bias_loc and qx_bias_scale [%d]" % (F, n, n))
+        zx = None if zx is None else arr(zx, np.float32).reshape(-1)
+        zw = None if zw is None else arr(zw, np.float32).reshape(-1)
+        out = [np.empty((F, n), np.float32) for _ in range(3)] + [np.empty((F, G), np.float32) for _ in range(3)]
+        nan = float("nan")
+        ms = C.c_double(0.0)
+        check(L.lib().polee_effects_run(
+            self._h, ptr(wl, f32p), ptr(ws, f32p), ptr(bl, f32p), ptr(bs, f32p), C.c_int32(int(niter)), C.c_double(target_coverage),
+            C.c_double(nan if effect_size is None else effect_size),
+            C.c_double(nan if aitchison_effect_size is None else aitchison_effect_size), C.c_uint64(int(seed) & _MASK),
+            ptr(zx, f32p), C.c_int64(0 if zx is None else zx.size), ptr(zw, f32p), C.c_int64(0 if zw is None else zw.size),
+            *[ptr(o, f32p) for o in out], C.byref(ms)), self.ctx._h)
+        self.kernel_ms = ms.value
+        if effect_size is None:
+            out[2] = None
+        if aitchison_effect_size is None:
+            out[5] = None
+        return tuple(out)
+
+
+def _gene_of(gene_idxs, transcript_idxs, n):
+    """the 0-based gene of every transcript from the reference's 1-based (gene, transcript) pairs"""
+    gi = np.asarray(gene_idxs, np.int64).reshape(-1) - 1
+    ti = np.asarray(transcript_idxs, np.int64).reshape(-1) - 1
+    gene_of = np.full(n, -1, np.int64)
+    gene_of[ti] = gi
+    if (gene_of < 0).any():
+        raise ValueError("every transcript must belong to a gene")
+    return gene_of
+
+
+def estimate_isoform_effect_sizes(gene_idxs, transcript_idxs, effect_size, aitchison_effect_size, qw_loc, qw_scale, qx_bias_loc,
+                                  qx_bias_scale, qx_gene_loc_factor_est=None, niter=EFFECT_DRAWS, target_coverage=0.1,
+                                  seed=DEFAULT_SEED, zx=None, zw=None, ctx=None):
+    """estimate_isoform_effect_sizes (src/regression.jl:761-945) on the device, the reference's argument order and six return values:
+    (min_effect_sizes, mean_effect_sizes, prob_de, aitchison_min_effect_sizes, aitchison_mean_effect_sizes, aitchison_prob_de).
+    gene_idxs / transcript_idxs are the 1-based pairs of gene_map.  effect_size is on the log scale already (main passes
+    log |--isoform-effect-size|); with None -- where the reference fails in log(abs(nothing)) -- prob_de is None.  prob_de is
+    one-sided, #{e > effect_size} / niter, as the reference computes it (:850).  qx_gene_loc_factor_est is accepted and IGNORED: the
+    reference only feeds two values from it that nothing reads (expr, expr_alt, :843-844).  The evaluation is in log space, so a gene
+    whose bias spans more than ~700 stays finite where the reference's exp / normalise / log gives log 0."""
+    qw_loc = np.atleast_2d(np.asarray(qw_loc, np.float32))
+    F, n = qw_loc.shape
+    num_genes = int(np.max(gene_idxs))
+    fx = IsoformEffects(_gene_of(gene_idxs, transcript_idxs, n), num_genes, F, ctx=ctx)
+    return fx.run(qw_loc, qw_scale, qx_bias_loc, qx_bias_scale, niter=niter, target_coverage=target_coverage, effect_size=effect_size,
+                  aitchison_effect_size=aitchison_effect_size, seed=seed, zx=zx, zw=zw)
+
+
+# ---- the design matrix (src/PoleeModel.jl:165-232)
+def build_design_matrix(sample_factors, factors=None, nonredundant=None, balanced=False):
+    """build_factor_matrix (src/PoleeModel.jl:165-232) for several factors: (F f32 [S, columns], factor_names), names `factor:option`.
+    The reference iterates a Dict of Sets, whose order is arbitrary; here factors and options come in SORTED order (the decision of
+    classify.build_factor_matrix).  A sample without a factor has the option "missing".  nonredundant: None keeps every option; ""
+    drops "missing" where it is an option, else the first sorted option; a name drops that option where it occurs.  balanced:
+    0 becomes -1 (src/regression.jl:254-260)."""
+    sample_factors = [{str(k): str(v) for k, v in (f or {}).items()} for f in sample_factors]
+    if factors is None:
+        factors = sorted({k for f in sample_factors for k in f})
+    else:
+        factors = sorted(set(str(f) for f in factors))
+    columns = []
+    for factor in factors:
+        options = sorted({f.get(factor, "missing") for f in sample_factors})
+        if nonredundant is not None:
+            if nonredundant != "":
+                options = [o for o in options if o != nonredundant]
+            elif "missing" in options:
+                options.remove("missing")
+            elif options:
+                options = options[1:]
+        columns += [(factor, o) for o in options]
+    F = np.zeros((len(sample_factors), len(columns)), np.float32)
+    for c, (factor, option) in enumerate(columns):
+        for i, f in enumerate(sample_factors):
+            if f.get(factor, "missing") == option:
+                F[i, c] = 1.0
+    if balanced:
+        F[F == 0] = -1.0
+    return F, ["%s:%s" % c for c in columns]
+
+
+# ---- genes without a GFF reader (src/rnaseq_sample.jl:229-250, src/transcripts.jl:956-1040)
+def gene_map(transcript_ids, pattern=None, annotations=None):
+    """populate_ts_metadata! + gene_feature_matrix: (num_genes, gene_idxs, transcript_idxs, gene_ids, gene_names), the two index lists
+    1-based and sorted by transcript, as the model classes expect.  pattern: a regular expression searched in every transcript id; the
+    gene id is its first capture group, or the whole match without one; a transcript it does not match becomes a gene of its own,
+    `unknown-gene-K`, K counting such transcripts from 1 (:244-247).  annotations: the parsed --gene-annotations file, a list of
+    {gene_name, transcripts}; a transcript no entry names is an error (the reference fails on the missing key).  Genes are numbered in
+    order of first appearance (the reference: the order of a Dict).  gene_names are empty, as in the reference without a GFF."""
+    import re
+    ids = [str(t) for t in transcript_ids]
+    if (pattern is None) == (annotations is None):
+        raise ValueError("exactly one of pattern and annotations is needed")
+    if annotations is not None:
+        by_transcript = {}
+        for entry in annotations:
+            for t in entry["transcripts"]:
+                by_transcript[str(t)] = str(entry["gene_name"])
+        missing = [t for t in ids if t not in by_transcript]
+        if missing:
+            raise ValueError("the gene annotations name no gene for %d transcripts (first: %s)" % (len(missing), missing[0]))
+        gids = [by_transcript[t] for t in ids]
+    else:
+        rx, unknown, gids = re.compile(pattern), 0, []
+        for t in ids:
+            mat = rx.search(t)
+            if mat is not None:
+                gids.append(mat.group(1) if rx.groups else mat.group(0))
+            else:
+                unknown += 1
+                gids.append("unknown-gene-%d" % unknown)
+    nums = {}
+    for gid in gids:
+        nums.setdefault(gid, len(nums) + 1)
+    gene_idxs = np.array([nums[gid] for gid in gids], np.int64)
+    transcript_idxs = np.arange(1, len(ids) + 1, dtype=np.int64)
+    gene_ids = list(nums)
+    return len(nums), gene_idxs, transcript_idxs, gene_ids, [""] * len(nums)
+
+
+def gene_initial_values(gene_idxs, transcript_idxs, x_init, num_samples, num_features, n):
+    """gene_initial_values (src/PoleeModel.jl:240-263): (x_gene_init [S, G], x_isoform_init [S, n]) in Float32 -- the log of the genes'
+    summed expression and of the isoforms' shares of it"""
+    x_init = np.asarray(x_init, np.float32)
+    gi = np.asarray(gene_idxs, np.int64).reshape(-1) - 1
+    ti = np.asarray(transcript_idxs, np.int64).reshape(-1) - 1
+    x_gene = np.zeros((int(num_samples), int(num_features)), np.float32)
+    x_iso = np.zeros((int(num_samples), int(n)), np.float32)
+    for i in range(int(num_samples)):
+        np.add.at(x_gene[i], gi, x_init[i, ti])  # (Float32 sums in the pairs' order, as the reference's loop)
+        x_iso[i, ti] = x_init[i, ti] / x_gene[i, gi]
+    with np.errstate(divide="ignore"):
+        return np.log(x_gene), np.log(x_iso)
+
+
+# ---- writers (src/regression.jl:380-419, 573-587, 688-758); print(::Float32) through pca._julia_float
+def write_isoform_regression_effects(output_filename, gene_idxs, transcript_idxs, factor_names, gene_ids, gene_names, transcript_names,
+                                     min_effect_sizes, mean_effect_sizes, prob_de, qw_isoform_loc, qx_isoform_bias_loc, qx_isoform_scale):
+    """write_isoform_regression_effects (src/regression.jl:688-729); the prob_de column is left out when prob_de is None"""
+    from .pca import _julia_float as jf
+    min_effect_sizes = np.asarray(min_effect_sizes)
+    num_factors, n = min_effect_sizes.shape
+    gene_of = _gene_of(gene_idxs, transcript_idxs, n)
+    with open(output_filename, "w") as out:
+        out.write("factor,gene_id,gene_name,transcript_id,mean_effect_size,min_effect_size")
+        if prob_de is not None:
+            out.write(",prob_de")
+        out.write(",w_mean,x_bias,x_scale\n")
+        for i in range(num_factors):
+            for j in range(n):
+                g = gene_of[j]
+                row = [str(factor_names[i]), str(gene_ids[g]), str(gene_names[g]), str(transcript_names[j]),
+                       jf(mean_effect_sizes[i][j]), jf(min_effect_sizes[i][j])]
+                if prob_de is not None:
+                    row.append(jf(prob_de[i][j]))
+                row += [jf(qw_isoform_loc[i][j]), jf(qx_isoform_bias_loc[j]), jf(qx_isoform_scale[j])]
+                out.write(",".join(row) + "\n")
+
+
+def write_aitchison_results(output_filename, factor_names, gene_ids, gene_names, min_effect_sizes, mean_effect_sizes, prob_de):
+    """write_aitchison_results (src/regression.jl:732-758)"""
+    from .pca import _julia_float as jf
+    min_effect_sizes = np.asarray(min_effect_sizes)
+    num_factors, num_genes = min_effect_sizes.shape
+    with open(output_filename, "w") as out:
+        out.write("factor,gene_id,gene_name,mean_effect_size,min_effect_size")
+        if prob_de is not None:
+            out.write(",prob_de")
+        out.write("\n")
+        for i in range(num_factors):
+            for j in range(num_genes):
+                row = [str(factor_names[i]), str(gene_ids[j]), str(gene_names[j]), jf(mean_effect_sizes[i][j]), jf(min_effect_sizes[i][j])]
+                if prob_de is not None:
+                    row.append(jf(prob_de[i][j]))
+                out.write(",".join(row) + "\n")
+
+
+def write_expression(output_filename, feature_names_label, feature_names, sample_names, qx_loc):
+    """--output-expression (src/regression.jl:573-587): TPM = 1e6 softmax(qx_loc) per sample, feature-major rows"""
+    from .pca import _julia_float as jf
+    x = np.exp(np.asarray(qx_loc, np.float32))
+    x = x / x.sum(axis=1, keepdims=True, dtype=np.float32)
+    x = (x * np.float32(1e6)).astype(np.float32)
+    with open(output_filename, "w") as out:
+        out.write("%s,sample,tpm\n" % feature_names_label)
+        for j in range(x.shape[1]):
+            for i in range(x.shape[0]):
+                out.write("%s,%s,%s\n" % (feature_names[j], sample_names[i], jf(x[i, j])))
+
+
+def write_x_init(output_filename, label, names, x_init_log):
+    """--x-isoform-init-output / --x-gene-init-output (src/regression.jl:380-419): exp of the initial values, one row per feature"""
+    from .pca import _julia_float as jf
+    x = np.exp(np.asarray(x_init_log, np.float32))
+    with open(output_filename, "w") as out:
+        out.write(label + "".join(",x%d" % (i + 1) for i in range(x.shape[0])) + "\n")
+        for j, name in enumerate(names):
+            out.write(str(name) + "".join("," + jf(v) for v in x[:, j]) + "\n")
+
+
+# ---- kallisto estimates (src/estimate.jl:66-146)
+def _kallisto_proportions(counts, efflens, pseudocount, file_ids, transcript_idx, n):
+    """kallisto_counts_to_proportions (src/estimate.jl:66-79): Float32 counts / effective lengths placed by transcript id, normalised,
+    + pseudocount / 1e6; [n]"""
+    xs = np.zeros(n, np.float32)
+    vals = (np.asarray(counts, np.float32) / np.asarray(efflens, np.float64)).astype(np.float32)
+    if file_ids is None:
+        xs[:] = vals
+    else:
+        for t, v in zip(file_ids, vals):
+            j = transcript_idx.get(t)
+            if j is not None:
+                xs[j] = v
+    xs = xs / xs.sum(dtype=np.float32)
+    return (xs + np.float32(pseudocount / np.float32(1e6))).astype(np.float32)
+
+
+def load_kallisto_estimates(filenames, pseudocount=0.0, use_bootstrap=False, transcript_ids=None):
+    """load_kallisto_estimates_from_specification (src/estimate.jl:86-146) over kallisto's abundance.h5 files: (x0 f32 [S, n],
+    log_x0_std f32 [S, n] or None).  With use_bootstrap, per transcript the mean and the standard deviation (n - 1 in the denominator,
+    Julia's std) of the log bootstrap proportions, the latter floored at 0.5, and x0 = exp(mean); these feed
+    RNASeqNormalTranscriptLinearRegression.  The bootstrap datasets are bootstrap/bs0, bs1, ... as kallisto names them.
+    transcript_ids: place the files' rows by aux/ids (transcripts a file does not name stay 0); None takes the files' own order."""
+    from . import h5io
+    idx = None if transcript_ids is None else {str(t): j for j, t in enumerate(transcript_ids)}
+    xss, stds = [], []
+    for filename in filenames:
+        with h5io.File(filename) as f:
+            efflens = f.read("aux/eff_lengths", np.float64)
+            file_ids = f.read_strings("aux/ids") if idx is not None else None
+            n = efflens.size if idx is None else len(idx)
+            if not use_bootstrap:
+                xss.append(_kallisto_proportions(f.read("est_counts", np.float64), efflens, pseudocount, file_ids, idx, n))
+                continue
+            bss, b = [], 0
+            while f.exists("bootstrap/bs%d" % b):
+                bss.append(_kallisto_proportions(f.read("bootstrap/bs%d" % b, np.float64), efflens, pseudocount, file_ids, idx, n))
+                b += 1
+            if len(bss) < 2:
+                raise ValueError("%s holds %d bootstrap samples; a standard deviation needs two" % (filename, len(bss)))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                log_bs = np.log(np.stack(bss)).astype(np.float32)
+                stds.append(np.maximum(np.float32(0.5), log_bs.std(axis=0, ddof=1, dtype=np.float64).astype(np.float32)))
+                xss.append(np.exp(log_bs.mean(axis=0, dtype=np.float64).astype(np.float32)))
+    return np.stack(xss).astype(np.float32), (np.stack(stds).astype(np.float32) if use_bootstrap else None)
+
+
+# ---- the command line (src/regression.jl:19-601)
+NUM_STEPS = {"transcript": 6000, "gene": 10000, "gene-isoform": 6000}  # (:327, :295, :433)
+
+
+def parser():
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m polee_amd.regression",
+                                 description="`polee model regression` on the GPU: a linear regression over transcript, gene or "
+                                             "gene and isoform expression (src/regression.jl)")
+    ap.add_argument("experiment", metavar="experiment.yml", help="Experiment specification")
+    ap.add_argument("--feature", default="transcript", metavar="F", help="One of transcript, gene, gene-isoform (splice-feature is not built)")
+    ap.add_argument("--point-estimates", default=None, metavar="KEY",
+                    help="Use point estimates (transcript_id,tpm CSVs) the experiment names under this key; needs --transcript-ids")
+    ap.add_argument("--kallisto-bootstrap", action="store_true", help="Use kallisto bootstrap samples (the samples' `kallisto` key)")
+    ap.add_argument("--kallisto", action="store_true", help="Use kallisto maximum likelihood estimates (the samples' `kallisto` key)")
+    ap.add_argument("--gene-pattern", default=None, metavar="regex", help="A regular expression extracting gene ids from transcript ids")
+    ap.add_argument("--gene-annotations", default=None, metavar="filename", help="YAML file assigning transcript ids to genes")
+    ap.add_argument("--pseudocount", type=float, default=None, metavar="C", help="With point estimates, add C tpm to each value")
+    ap.add_argument("--output", default="regression-coefficients.csv", metavar="filename", help="Output file for regression coefficients")
+    ap.add_argument("--isoform-output", default="regression-isoform-coefficients.csv", metavar="filename",
+                    help="Output file for isoform regression results of gene-isoform regression")
+    ap.add_argument("--aitchison-distance-output", default=None, metavar="filename",
+                    help="Output the Aitchison distances, a test for overall isoform composition changes")
+    ap.add_argument("--aitchison-distance-effect-size", type=float, default=1.0, metavar="S")
+    ap.add_argument("--extra-params-output", default=None, metavar="filename", help="Output some additional parameter values")
+    ap.add_argument("--output-expression", default=None, metavar="filename", help="Output expression estimates to the given file")
+    ap.add_argument("--lower-credible", type=float, default=0.025, metavar="L")
+    ap.add_argument("--upper-credible", type=float, default=0.975, metavar="U")
+    ap.add_argument("--min-effect-size-coverage", type=float, default=0.1, metavar="C")
+    ap.add_argument("--write-variational-posterior-params", action="store_true")
+    ap.add_argument("--effect-size", type=float, default=None, metavar="S",
+                    help="Output the posterior probability of abs fold-change greater than S")
+    ap.add_argument("--isoform-effect-size", type=float, default=None, metavar="S",
+                    help="Output the posterior probability of an isoform log-ratio greater than log S")
+    ap.add_argument("--x-isoform-init-output", default=None, metavar="filename")
+    ap.add_argument("--x-gene-init-output", default=None, metavar="filename")
+    ap.add_argument("--factors", default=None, help="Comma-separated list of factors to regress on (default: all)")
+    ap.add_argument("--no-distortion", action="store_true", help="Disable the 'distortion' model")
+    ap.add_argument("--scale-penalty", type=float, default=1e-3, help="Std. dev. of the penalty on expression vectors straying from sum 1")
+    ap.add_argument("--nonredundant", action="store_true", help="Exclude one option of each factor")
+    ap.add_argument("--redundant-factor", default="", metavar="factor", help="With --nonredundant, exclude this option")
+    ap.add_argument("--balanced", action="store_true", help="-1/1 instead of 0/1 in the design matrix")
+    ap.add_argument("--transformation", default=None, metavar="polee-transform.h5", help="A Polya tree shared by the samples")
+    ap.add_argument("--num-steps", type=int, default=None, metavar="N", help="Optimiser steps (default 6000; 10000 for --feature gene)")
+    ap.add_argument("--effect-draws", type=int, default=EFFECT_DRAWS, metavar="N", help="Monte-Carlo draws of the isoform effect sizes")
+    ap.add_argument("--seed", type=int, default=DEFAULT_SEED, metavar="N", help="RNG seed")
+    ap.add_argument("--device", type=int, default=0, metavar="D", help="GPU to run on")
+    ap.add_argument("--transcript-ids", metavar="ids.txt", help="Transcript ids, one per line (default 1..n)")
+    return ap
+
+
+def main(argv=None):
+    import sys
+    a = parser().parse_args(sys.argv[1:] if argv is None else argv)
+    feature = a.feature
+    if feature == "splice-feature":
+        raise SystemExit("--feature splice-feature is not built: it needs the reference's GFF-derived splicing features "
+                         "(DESIGN.md section 7)")
+    if feature not in NUM_STEPS:
+        raise SystemExit("%s is not a supported feature." % feature)
+    if a.gene_pattern is not None and a.gene_annotations is not None:
+        raise SystemExit("At most one of --gene-pattern and --gene-annotations can be given.")
+    if a.kallisto and a.kallisto_bootstrap:
+        raise SystemExit("Only one of '--kallisto' and '--kallisto-bootstrap' can be used.")
+    use_kallisto = a.kallisto or a.kallisto_bootstrap
+    if use_kallisto and a.point_estimates is not None:
+        raise SystemExit("'--use-point-estimates' in not compatible with '--kallisto' or '--kallisto-bootstrap'")
+    point = use_kallisto or a.point_estimates is not None
+    if a.pseudocount is not None and not point:
+        raise SystemExit("--pseudocount argument only valid with --point-estimates")
+    if feature != "transcript" and a.kallisto_bootstrap:
+        raise SystemExit("%s regression with --kallisto-bootstrap not yet implemented" % feature)
+    if feature != "transcript" and point:
+        raise SystemExit("%s regression is built on the approximate likelihood only: --point-estimates and --kallisto need "
+                         "--feature transcript" % feature)
+    if feature != "transcript" and a.gene_pattern is None and a.gene_annotations is None:
+        raise SystemExit("--feature %s needs --gene-pattern or --gene-annotations (GFF parsing is not built, DESIGN.md section 7)" % feature)
+    if a.point_estimates is not None and not a.transcript_ids:
+        raise SystemExit("--point-estimates needs --transcript-ids: the CSV rows are matched by transcript id")
+    num_steps = NUM_STEPS[feature] if a.num_steps is None else a.num_steps
+    if num_steps < 1 or a.effect_draws < 1:
+        raise SystemExit("--num-steps and --effect-draws must be positive")
+    if a.effect_draws > MAX_EFFECT_DRAWS:
+        raise SystemExit("--effect-draws: the effect-size kernel is built for at most %d draws" % MAX_EFFECT_DRAWS)
+    from . import estimate, h5io
+    from .core import Context
+    from .pca import read_experiment
+    from .sample import _read_lines, resolve_names
+    spec = read_experiment(a.experiment)
+    if not spec.get("samples"):
+        raise SystemExit("%s names no samples" % a.experiment)
+    ids_given = _read_lines(a.transcript_ids) if a.transcript_ids else None
+    ctx = Context(a.device)
+    pseudocount = 0.0 if a.pseudocount is None else a.pseudocount
+    log_x0_std, variables = None, None
+    if use_kallisto:
+        _, sample_names, sample_factors = estimate.read_specification(spec)
+        x0, log_x0_std = load_kallisto_estimates([s["kallisto"] for s in spec["samples"]], pseudocount, a.kallisto_bootstrap, ids_given)
+    elif a.point_estimates is not None:
+        from .classify import load_point_estimates
+        filenames, sample_names, sample_factors = estimate.read_specification(spec, point_estimates_key=a.point_estimates)
+        x0 = load_point_estimates(filenames, ids_given)
+        x0 = (x0 + np.float32(pseudocount / np.float32(1e6))).astype(np.float32)  # (:228-230: added whenever the mode is on)
+    else:
+        filenames, _, _ = estimate.read_specification(spec)
+        n = h5io.read_prepared_sample(filenames[0])["n"]
+        ls = estimate.load_samples_from_specification(spec, n, ptt_filename=a.transformation, ctx=ctx)
+        x0, sample_names, sample_factors, variables = ls.x0_values, ls.sample_names, ls.sample_factors, ls.variables["approx"]
+    num_samples, n = x0.shape
+    ids, _ = resolve_names(n, ids_given)
+    with np.errstate(divide="ignore"):
+        x0_log = np.log(x0).astype(np.float32)
+    if point and not np.isfinite(x0_log).all():
+        raise SystemExit("a point estimate of 0 has log -inf: give --pseudocount C")
+    F, factor_names = build_design_matrix(sample_factors, None if a.factors is None else a.factors.split(","),
+                                          a.redundant_factor if a.nonredundant else None, a.balanced)
+    if F.shape[1] < 1:
+        raise SystemExit("the design matrix has no columns: the samples name no factors (or --nonredundant removed them all)")
+    distortion = not a.no_distortion
+    if feature == "transcript":
+        sample_scales = estimate_sample_scales(x0_log)
+        if log_x0_std is not None:
+            reg = RNASeqNormalTranscriptLinearRegression(None, x0_log, log_x0_std, F, sample_scales, distortion, a.scale_penalty, ctx=ctx)
+        else:
+            reg = RNASeqTranscriptLinearRegression(variables, x0_log, F, sample_scales, distortion, a.scale_penalty, point, ctx=ctx)
+        qx_loc, qw_loc, qw_scale, qx_bias, qx_scale = reg.fit(num_steps, seed=a.seed)
+        feature_names, feature_names_label = ids, "transcript_id"
+    else:
+        annotations = None if a.gene_annotations is None else read_experiment(a.gene_annotations)
+        num_features, gene_idxs, transcript_idxs, gene_ids, gene_names = gene_map(ids, a.gene_pattern, annotations)
+        gene_sizes = np.bincount(gene_idxs - 1, minlength=num_features).astype(np.float32)
+        x_gene_init, x_isoform_init = gene_initial_values(gene_idxs, transcript_idxs, x0, num_samples, num_features, n)
+        sample_scales = estimate_sample_scales(x0_log, upper_quantile=0.95)
+        if feature == "gene":
+            reg = RNASeqGeneLinearRegression(variables, gene_idxs, transcript_idxs, x_gene_init, x_isoform_init, gene_sizes, F,
+                                             sample_scales, distortion, a.scale_penalty, False, ctx=ctx)
+            qx_loc, qw_loc, qw_scale, qx_bias, qx_scale = reg.fit(num_steps, seed=a.seed)
+            feature_names, feature_names_label = gene_ids, "gene_id"
+        else:
+            if a.x_isoform_init_output is not None:
+                write_x_init(a.x_isoform_init_output, "transcript_id", ids, x_isoform_init)
+            if a.x_gene_init_output is not None:
+                write_x_init(a.x_gene_init_output, "gene_id", gene_ids, x_gene_init)
+            reg = RNASeqGeneIsoformLinearRegression(variables, gene_idxs, transcript_idxs, x_gene_init, x_isoform_init, gene_sizes, F, F,
+                                                    sample_scales, distortion, a.scale_penalty, False, ctx=ctx)
+            (qw_loc, qw_scale, qw_isoform_loc, qw_isoform_scale, qx_isoform_bias_loc, qx_isoform_bias_scale, qx_isoform_scale,
+             qx_bias, qx_scale, qx_gene_loc_factor_est) = reg.fit(num_steps, seed=a.seed)
+            # (the reference leaves qx_loc undefined on this branch and fails at --output-expression: the genes' qx_loc is written)
+            qx_loc = reg.variables()["qx_loc"] if a.output_expression is not None else None
+            print("estimating effect sizes...")
+            # (the reference dies in log(abs(nothing)) without --isoform-effect-size; here prob_de is then not computed)
+            es = None if a.isoform_effect_size is None else math.log(abs(a.isoform_effect_size))
+            min_es, mean_es, prob_de, a_min, a_mean, a_prob = estimate_isoform_effect_sizes(
+                gene_idxs, transcript_idxs, es, a.aitchison_distance_effect_size, qw_isoform_loc, qw_isoform_scale, qx_isoform_bias_loc,
+                qx_isoform_bias_scale, qx_gene_loc_factor_est, niter=a.effect_draws, target_coverage=a.min_effect_size_coverage,
+                seed=a.seed, ctx=ctx)
+            print("done.")
+            if a.aitchison_distance_output is not None:
+                write_aitchison_results(a.aitchison_distance_output, factor_names, gene_ids, gene_names, a_min, a_mean, a_prob)
+            write_isoform_regression_effects(a.isoform_output, gene_idxs, transcript_idxs, factor_names, gene_ids, gene_names, ids,
+                                             min_es, mean_es, prob_de, qw_isoform_loc, qx_isoform_bias_loc, qx_isoform_scale)
+            if a.extra_params_output is not None:
+                reg.write_other_params(a.extra_params_output)
+            feature_names = ["%s,%s" % gn for gn in zip(gene_ids, gene_names)]
+            feature_names_label = "gene_id,gene_name"
+    if a.output_expression is not None:
+        write_expression(a.output_expression, feature_names_label, feature_names, sample_names, qx_loc)
+    write_regression_effects(a.output, factor_names, feature_names_label, feature_names, qx_bias, qx_scale, qw_loc, qw_scale,
+                             a.lower_credible, a.upper_credible, a.effect_size, a.min_effect_size_coverage,
+                             a.write_variational_posterior_params)
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())
