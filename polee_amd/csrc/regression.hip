@@ -19,130 +19,28 @@
 //   finish   : the few global parameters
 //   adam     : Keras Adam over the flat parameter vector
 // Everything is O((F + S) n) bytes per step (cache / latency bound): no roofline claim.
+//
+// Blocks: a handle holds two RegBlocks -- a RegView (the layout of a flat parameter / noise vector over n columns) with the
+// buffers that go with it: parameters, gradient, Adam moments, noise, the data pass's stats and the prior pass's accumulators.
+// `main` is the model polee_regression_create describes.  `iso` is what a polee_regression_set_*_likelihood call adds, and
+// IsoKind says which: gene (no view: a tail of isoform means and values, reg_iso_grad_kernel), gene-isoform (a view over the
+// transcripts, run through the same data / column / finish kernels) or joint (a view over the splice features followed by a
+// transcript tail, reg_joint_*_kernel).  A set-up call builds its block locally and moves it into the handle as its last act.
 #include "common.hpp"
 #include "comm_internal.hpp"
+#include "regression_device.hpp"
 #include "rng.hpp"
 #include "wave.hpp"
 
 #include <cmath>
+#include <memory>
+#include <type_traits>
 
 namespace polee {
 
-constexpr int REG_MAXF = 16;    // factors (design-matrix columns)
-constexpr int REG_MAXDEG = 32;  // kernel-regression hinges
-constexpr int REG_BLOCK = 128;
-constexpr int REG_SLOTS = 32;  // copies of every grid-wide accumulator (block b adds into copy b % 32): same-address
-                               // float atomics from ~1.5 k blocks serialise, 32-way spreading removes that
-constexpr float HALF_LOG2PI = 0.91893853320467274178f;
-
-// Layout of the flat parameter / gradient vector and of the noise vector (include/polee_hip.h documents the order).
-struct RegView {
-    int32_t S, F, n, deg;
-    int32_t use_distortion, point;
-    float bias_loc0, bias_scale0, penalty;
-    // > 0: x_scale ~ InverseGamma(fixed_ab, fixed_ab) instead of the kernel-regressed concentration / scale, and the
-    // observation model stands alone (no sample scales, no scale-drift penalty, no likelihood term of its own): the
-    // isoform block of the gene-isoform model (models/polee_regression.py:727-733), run with deg = 0
-    float fixed_ab = 0.0f;
-    // --- the joint model's variants (RNASeqJointLinearRegression, models/polee_regression.py:879-1283) ---
-    int32_t levels = 2;       // 1: a horseshoe prior (one local scale level, :1009-1024) instead of horseshoe+; the local2 arrays stay in
-                              //    the vector, unused (gradient 0)
-    int32_t no_xs = 0;        // 1: no x_scale in this block (the splice-feature block: its observation lives on the transcripts)
-    int32_t w_from_bias = 0;  // 1: the kernel-regression weights are functions of the SAMPLED bias (:1034-1035), not of x_bias_init
-    float hc_scale = 1.0f;    // scale of the HalfCauchy prior on the mean-variance coefficients (10 in the joint model, :1037-1041)
-    float bandwidth = 1.0f;
-    const float *hinges = nullptr;  // (w_from_bias) device pointer, deg values
-    __host__ __device__ int64_t Fn() const { return (int64_t)F * n; }
-    __host__ __device__ int64_t o_dist() const { return 4; }
-    __host__ __device__ int64_t o_conc() const { return 4 + (int64_t)F * deg; }
-    __host__ __device__ int64_t o_scc() const { return o_conc() + deg; }
-    __host__ __device__ int64_t o_cols() const { return o_scc() + deg; }  // 10 arrays [F][n]
-    __host__ __device__ int64_t o_bias_loc() const { return o_cols() + 10 * Fn(); }
-    __host__ __device__ int64_t o_bias_s() const { return o_bias_loc() + n; }
-    __host__ __device__ int64_t o_xs_loc() const { return o_bias_loc() + 2 * (int64_t)n; }
-    __host__ __device__ int64_t o_xs_s() const { return o_bias_loc() + 3 * (int64_t)n; }
-    __host__ __device__ int64_t o_qx_loc() const { return o_bias_loc() + 4 * (int64_t)n; }
-    __host__ __device__ int64_t o_qx_s() const { return o_qx_loc() + (int64_t)S * n; }
-    __host__ __device__ int64_t num_params() const { return o_qx_s() + (int64_t)S * n; }
-    // noise: 2 global, 5 arrays [F][n], x_bias [n], x_scale [n], x [S][n]
-    __host__ __device__ int64_t e_cols() const { return 2; }
-    __host__ __device__ int64_t e_bias() const { return 2 + 5 * Fn(); }
-    __host__ __device__ int64_t e_xs() const { return e_bias() + n; }
-    __host__ __device__ int64_t e_x() const { return e_bias() + 2 * (int64_t)n; }
-    __host__ __device__ int64_t num_noise() const { return e_x() + (int64_t)S * n; }
-    __host__ __device__ int num_red() const { return 1 + F * deg + 2 * deg; }
-};
-
-// The column kernels are VALU-bound (rocprofv3: ~7.4 k VALU instructions per thread with libm's exp / log / log1p and
-// IEEE division), so the elementwise math uses the hardware transcendentals (v_exp_f32, v_log_f32, v_rcp_f32,
-// v_sqrt_f32: 1 ulp each) -- errors of ~1e-6 relative, far inside the 1e-4 parity tolerance.
-__device__ inline float fexp(float x) { return __expf(x); }
-__device__ inline float flog(float x) { return __logf(x); }
-__device__ inline float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ inline float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
-// log1p(t), 0 <= t <= 1, with full relative accuracy for small t (log(1 + t) would round 1 + t)
-__device__ inline float flog1p01(float t) { return t < 1e-3f ? t * (1.0f - t * (0.5f - t * (1.0f / 3.0f))) : flog(1.0f + t); }
-__device__ inline float softplusf(float x) { return fmaxf(x, 0.0f) + flog1p01(fexp(-fabsf(x))); }
-__device__ inline float sigmoidf(float x) { return frcp(1.0f + fexp(-x)); }
-// lgamma(x) and psi(x), x > 0, together: the recurrences lgamma(x) = lgamma(x+1) - log x, psi(x) = psi(x+1) - 1/x up to
-// x >= 8 (one log of the running product), then the Stirling / asymptotic series (truncation < 1e-8 at x = 8)
-__device__ inline void lgamma_digamma(float x, float &lg, float &psi)
-{
-    float prod = 1.0f, r = 0.0f;
-    while (x < 8.0f) {
-        prod *= x;
-        r -= frcp(x);
-        x += 1.0f;
-    }
-    const float i = frcp(x), i2 = i * i, lx = flog(x);
-    psi = r + lx - 0.5f * i - i2 * (1.0f / 12.0f - i2 * (1.0f / 120.0f - i2 * (1.0f / 252.0f)));
-    lg = (x - 0.5f) * lx - x + HALF_LOG2PI + i * (1.0f / 12.0f - i2 * (1.0f / 360.0f - i2 * (1.0f / 1260.0f))) - flog(prod);
-}
-
-// one draw of SoftplusNormal(loc, softplus(sraw)) (src/polee.py:24-33) and its share of log q
-struct SpDraw {
-    float z, sg, eps, s, sgs, logq;
-};
-__device__ inline SpDraw sp_draw(float loc, float sraw, float eps)
-{
-    SpDraw d;
-    d.eps = eps;
-    d.s = softplusf(sraw);
-    d.sgs = sigmoidf(sraw);
-    const float u = loc + d.s * eps;
-    d.z = softplusf(u);
-    d.sg = sigmoidf(u);
-    d.logq = -0.5f * eps * eps - flog(d.s) - HALF_LOG2PI + softplusf(-u);  // - log sigmoid(u)
-    return d;
-}
-// G = d(-log p)/dz  ->  d loss / d loc, d loss / d sraw
-__device__ inline void sp_grad(const SpDraw &d, float G, float &gloc, float &gs)
-{
-    const float a = G * d.sg - (1.0f - d.sg);
-    gloc = a;
-    gs = (a * d.eps - frcp(d.s)) * d.sgs;
-}
-// -log InverseGamma(0.5, 0.5)(z), -log HalfNormal(1)(z)
-__device__ inline float nlp_ig_half(float z)
-{
-    return -(0.5f * -0.69314718055994530942f - 0.57236494292470008707f - 1.5f * flog(z) - 0.5f * frcp(z));
-}
-__device__ inline float nlp_halfnormal(float z) { return 0.22579135264472743236f + 0.5f * z * z; }  // -0.5 log(2/pi)
-
-__device__ inline float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Device-side clock of the fit, so that a whole step is one replayable hipGraph: tick[0] = Adam step t, tick[1] =
 // slot of the loss trace; seed_dev[0] = seed of the fit, lr_t[0] = Adam's step size at t.
-__global__ void reg_tick_kernel(uint32_t *tick, float *lr_t, float lr)
-{
-    const double t = (double)(++tick[0]);
-    lr_t[0] = (float)((double)lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
-}
+__global__ void reg_tick_kernel(uint32_t *tick, float *lr_t, float lr) { lr_t[0] = adam_tick(tick, lr); }
 
 // seed / step: immediates, or (tick != nullptr) read from the device clock
 __global__ void reg_noise_kernel(int64_t count, uint64_t seed, uint32_t step, const uint64_t *seed_dev,
@@ -156,7 +54,7 @@ __global__ void reg_noise_kernel(int64_t count, uint64_t seed, uint32_t step, co
     }
     seed ^= salt;
     float z[4];
-    philox_randn4(seed ^ 0x7265677265737369ull, step, (uint32_t)(q >> 32), (uint32_t)q, z);
+    philox_randn4(seed ^ REG_SEED_SALT, step, (uint32_t)(q >> 32), (uint32_t)q, z);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (q * 4 + i < count) eps[q * 4 + i] = z[i];
@@ -180,7 +78,7 @@ __global__ void reg_draw_kernel(RegView v, int64_t shared, int64_t own, const ui
     const uint64_t seed = seed_dev[0] ^ (seg1 ? salt : (uint64_t)0);
     const uint32_t step = tick[0] + 1u;
     float z[4];
-    philox_randn4(seed ^ 0x7265677265737369ull, step, (uint32_t)(q >> 32), (uint32_t)q, z);
+    philox_randn4(seed ^ REG_SEED_SALT, step, (uint32_t)(q >> 32), (uint32_t)q, z);
     float *e = eps + (seg1 ? shared : 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -297,6 +195,7 @@ __global__ __launch_bounds__(1024) void reg_normal_lik_kernel(int n, const float
 //   x_isoform_mean ~ Normal(0, 2) [nt],  x_isoform ~ Normal(x_isoform_mean, 1),  both with Normal surrogates.
 // Isoform block of parameters: mean_loc [nt], mean_softplus_scale [nt], iso_loc [S][nt], iso_softplus_scale [S][nt];
 // noise: mean [nt], iso [S][nt].
+// (also the joint model's transcript tail, which has the same layout: scale loc / s [nt], x_iso loc / s [S][nt])
 __global__ void reg_iso_sample_kernel(int S, int nt, const float *ip, const float *ieps, float *xi)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, snt = (int64_t)S * nt;
@@ -347,26 +246,16 @@ __global__ __launch_bounds__(256) void reg_iso_grad_kernel(int S, int nt, const 
 // RegView over P "columns" (levels = 1, no_xs) run through the column / finish kernels; the transcripts' part -- x_iso_scale
 // (SoftplusNormal surrogate) and x_iso (Normal surrogate) -- is the kernel below.  Transcript part of the parameter block:
 // x_iso_scale_loc [nt], x_iso_scale_softplus_scale [nt], x_iso_loc [S][nt], x_iso_softplus_scale [S][nt]; noise: scale [nt],
-// x_iso [S][nt].
-__global__ void reg_joint_sample_kernel(int S, int nt, const float *jp, const float *jeps, float *xi)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, snt = (int64_t)S * nt;
-    if (i >= snt) return;
-    xi[i] = jp[2 * (int64_t)nt + i] + softplusf(jp[2 * (int64_t)nt + snt + i]) * jeps[nt + i];
-}
+// x_iso [S][nt] (x_iso is drawn by reg_iso_sample_kernel).
 // mu[s][p] = x_splice_bias[p] + sum_f F[s][f] w_splice[f][p] at the block's draw (thread per feature)
 __global__ void reg_joint_mean_kernel(RegView vs, int S, const float *__restrict__ sp, const float *__restrict__ seps,
                                       const float *__restrict__ design, float *__restrict__ mu)
 {
     const int64_t pidx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (pidx >= vs.n) return;
-    const int64_t Fn = vs.Fn();
-    const float b = sp[vs.o_bias_loc() + pidx] + softplusf(sp[vs.o_bias_s() + pidx]) * seps[vs.e_bias() + pidx];
+    const float b = draw_bias(vs, sp, seps, pidx);
     float w[REG_MAXF];
-    for (int f = 0; f < vs.F; ++f) {
-        const int64_t idx = (int64_t)f * vs.n + pidx;
-        w[f] = sp[vs.o_cols() + 8 * Fn + idx] + softplusf(sp[vs.o_cols() + 9 * Fn + idx]) * seps[vs.e_cols() + 4 * Fn + idx];
-    }
+    for (int f = 0; f < vs.F; ++f) w[f] = draw_w(vs, sp, seps, f, pidx);
     for (int s = 0; s < S; ++s) {
         float m = b;
         for (int f = 0; f < vs.F; ++f) m += design[s * vs.F + f] * w[f];
@@ -457,23 +346,15 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_data_kernel(RegView v, const fl
     const int64_t jj = (int64_t)blockIdx.x * REG_BLOCK + tid;
     const bool live = jj < v.n;
     const int64_t j = live ? jj : v.n - 1;  // dead lanes recompute the last column and contribute nothing
-    constexpr int UF = FT ? FT : 1, UD = DT ? DT : 1;  // unroll counts
-    const int F = FT ? FT : v.F, deg = DT ? DT : v.deg, n = v.n;
-    const int64_t Fn = v.Fn();
+    constexpr int UF = FT ? FT : 1;  // unroll count
+    const int F = FT ? FT : v.F, n = v.n;
 #pragma unroll UF
     for (int f = 0; f < F; ++f) {
-        const int64_t idx = (int64_t)f * n + j;
-        const float w = p[v.o_cols() + 8 * Fn + idx] + softplusf(p[v.o_cols() + 9 * Fn + idx]) * eps[v.e_cols() + 4 * Fn + idx];
-        float wd = 0.0f;
-        if (v.use_distortion) {
-#pragma unroll UD
-            for (int d = 0; d < deg; ++d) wd += p[v.o_dist() + f * deg + d] * W[(int64_t)d * n + j];
-        }
-        s_weff[f][tid] = w + wd;
+        s_weff[f][tid] = draw_weff<DT>(v, p, eps, W, f, j);
         s_gacc[f][tid] = 0.0f;
     }
-    const float b = p[v.o_bias_loc() + j] + softplusf(p[v.o_bias_s() + j]) * eps[v.e_bias() + j];
-    const float xsz = softplusf(p[v.o_xs_loc() + j] + softplusf(p[v.o_xs_s() + j]) * eps[v.e_xs() + j]);
+    const float b = draw_bias(v, p, eps, j);
+    const float xsz = draw_xscale(v, p, eps, j);
     const float inv = frcp(xsz), inv2 = inv * inv, lxs = flog(xsz);
     const float ipen2 = 1.0f / (v.penalty * v.penalty);
     const bool sub = v.fixed_ab > 0.0f;  // (then ss, x, lse are null: x is recomputed from its surrogate)
@@ -708,10 +589,7 @@ __global__ __launch_bounds__(64) void reg_finish_kernel(RegView v, const float *
                                                         const float *extra_loss, uint32_t *tick, float *lr_t, float lr)
 {
     const int lane = threadIdx.x, nred = v.num_red();
-    if (tick && lane == 0) {  // the device clock of fit(): this step's number and Adam's bias-corrected rate (reg_tick_kernel)
-        const double t = (double)(++tick[0]);
-        lr_t[0] = (float)((double)lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
-    }
+    if (tick && lane == 0) lr_t[0] = adam_tick(tick, lr);  // the device clock of fit(): this step's number and Adam's rate
     auto slots = [&](int i) {  // sum of accumulator i over its copies
         float t = 0.0f;
         for (int k = 0; k < REG_SLOTS; ++k) {
@@ -752,20 +630,13 @@ __global__ __launch_bounds__(64) void reg_finish_kernel(RegView v, const float *
     if (lane == 0) loss_out[0] = (float)(loss + (extra_loss ? (double)extra_loss[0] : 0.0));
 }
 
-// tf.optimizers.Adam: theta -= lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps)
 __global__ void reg_adam_kernel(int64_t count, float *p, const float *g, float *m, float *vv, const float *lr_dev,
                                 const float *loss, float *trace, uint32_t *tick)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0 && trace) trace[tick[1]++] = loss[0];  // (also when nothing is trainable: count may be 0)
     if (i >= count) return;
-    const float lr_t = lr_dev[0];
-    const float gi = g[i];
-    const float mi = 0.9f * m[i] + 0.1f * gi;
-    const float vi = 0.999f * vv[i] + 0.001f * gi * gi;
-    m[i] = mi;
-    vv[i] = vi;
-    p[i] -= lr_t * mi / (sqrtf(vi) + 1e-7f);
+    p[i] -= adam_step(m[i], vv[i], g[i], lr_dev[0]);
 }
 
 // ---- classify (models/polee_regression.py:342-413): the design matrix of the testing samples is a latent variable, so the loss needs
@@ -783,18 +654,10 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_design_grad_kernel(RegView v, c
     const int64_t jj = (int64_t)blockIdx.x * REG_BLOCK + tid;
     const bool live = jj < v.n;
     const int64_t j = live ? jj : v.n - 1;
-    const int F = v.F, deg = v.deg, n = v.n;
-    const int64_t Fn = v.Fn();
-    for (int f = 0; f < F; ++f) {
-        const int64_t idx = (int64_t)f * n + j;
-        const float w = p[v.o_cols() + 8 * Fn + idx] + softplusf(p[v.o_cols() + 9 * Fn + idx]) * eps[v.e_cols() + 4 * Fn + idx];
-        float wd = 0.0f;
-        if (v.use_distortion)
-            for (int d = 0; d < deg; ++d) wd += p[v.o_dist() + f * deg + d] * W[(int64_t)d * n + j];
-        s_weff[f][tid] = w + wd;
-    }
-    const float b = p[v.o_bias_loc() + j] + softplusf(p[v.o_bias_s() + j]) * eps[v.e_bias() + j];
-    const float xsz = softplusf(p[v.o_xs_loc() + j] + softplusf(p[v.o_xs_s() + j]) * eps[v.e_xs() + j]);
+    const int F = v.F, n = v.n;
+    for (int f = 0; f < F; ++f) s_weff[f][tid] = draw_weff<0>(v, p, eps, W, f, j);
+    const float b = draw_bias(v, p, eps, j);
+    const float xsz = draw_xscale(v, p, eps, j);
     const float inv = frcp(xsz), inv2 = inv * inv;
     float *out = dF + (int64_t)(blockIdx.x % REG_SLOTS) * v.S * F;
     for (int s = 0; s < v.S; ++s) {
@@ -833,19 +696,100 @@ __global__ __launch_bounds__(256) void reg_latent_kernel(int SF, float *__restri
         gi += zi * inv_var;
         gz[i] = gi;
         l += (double)(0.5f * zi * zi * inv_var + nlp0);
-        if (update) {
-            const float mi = 0.9f * m[i] + 0.1f * gi;
-            const float vi = 0.999f * vv[i] + 0.001f * gi * gi;
-            m[i] = mi;
-            vv[i] = vi;
-            z[i] = zi - lr_dev[0] * mi / (sqrtf(vi) + 1e-7f);
-        }
+        if (update) z[i] = zi - adam_step(m[i], vv[i], gi, lr_dev[0]);
     }
     l = wave_sum_to_lane63(l);
     if ((tid & 63) == 63) red[tid >> 6] = l;
     __syncthreads();
     if (tid == 0) loss[0] = (float)((double)loss[0] + red[0] + red[1] + red[2] + red[3]);
 }
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------
+// The reference's default degree (15) with up to four factors runs the data and column kernels with fixed trip counts, everything
+// else at run-time shape <0, 0>: launch(FT, DT) is called with the pair as std::integral_constants.  fixed_ok = false forces <0, 0>.
+template <class L>
+void reg_dispatch(const RegView &v, bool fixed_ok, L &&launch)
+{
+    using std::integral_constant;
+    const int ft = fixed_ok && v.deg == 15 && v.F <= 4 ? v.F : 0;
+    if (ft == 1) launch(integral_constant<int, 1>{}, integral_constant<int, 15>{});
+    else if (ft == 2) launch(integral_constant<int, 2>{}, integral_constant<int, 15>{});
+    else if (ft == 3) launch(integral_constant<int, 3>{}, integral_constant<int, 15>{});
+    else if (ft == 4) launch(integral_constant<int, 4>{}, integral_constant<int, 15>{});
+    else launch(integral_constant<int, 0>{}, integral_constant<int, 0>{});
+}
+
+template <class T>
+polee_status reg_zero(polee_ctx *ctx, DevBuf<T> &b)
+{
+    if (b.p) POLEE_HIP_TRY(ctx, hipMemsetAsync(b.p, 0, sizeof(T) * b.n, ctx->stream));
+    return POLEE_OK;
+}
+
+// A block of variational parameters with everything a step keeps per block.  The view v lays out the front of p / g / m / vv
+// (and of eps) over v.n columns; tail_params / tail_noise values that the view does not describe follow it in the same buffers.
+// v.n == 0: no view, the block is its tail (and has no stats / small / acc / loss).
+struct RegBlock {
+    RegView v{};
+    int64_t tail_params = 0, tail_noise = 0;
+    DevBuf<float> p, g, m, vv, eps, stats, small, loss;
+    DevBuf<double> acc;
+    bool has_cols() const { return v.n > 0; }
+    int64_t view_params() const { return has_cols() ? v.num_params() : 0; }
+    int64_t view_noise() const { return has_cols() ? v.num_noise() : 0; }
+    int64_t num_params() const { return view_params() + tail_params; }
+    int64_t num_noise() const { return view_noise() + tail_noise; }
+    int64_t num_stats() const { return (int64_t)(v.F + 2) * v.n + REG_SLOTS; }
+    float *loss_slots() const { return stats.p + num_stats() - REG_SLOTS; }  // the samples' loss terms (see reg_data_kernel)
+
+    // p0: the initial values of the view's parameters and of the tail; everything else is allocated and zeroed
+    polee_status init(polee_ctx *ctx, const RegView &view, int64_t tail_p, int64_t tail_e, const std::vector<float> &p0)
+    {
+        v = view, tail_params = tail_p, tail_noise = tail_e;
+        const size_t np = p0.size();  // == num_params()
+        POLEE_TRY(p.upload(ctx, p0));
+        for (DevBuf<float> *b : {&g, &m, &vv}) POLEE_TRY(b->alloc(ctx, np));
+        POLEE_TRY(eps.alloc(ctx, (size_t)num_noise()));
+        if (has_cols()) {
+            POLEE_TRY(stats.alloc(ctx, (size_t)num_stats()));
+            POLEE_TRY(small.alloc(ctx, (size_t)REG_SLOTS * v.num_red()));
+            POLEE_TRY(acc.alloc(ctx, REG_SLOTS));
+            POLEE_TRY(loss.alloc(ctx, 1));
+        }
+        for (DevBuf<float> *b : {&g, &m, &vv, &stats, &small}) POLEE_TRY(reg_zero(ctx, *b));
+        POLEE_TRY(reg_zero(ctx, acc));
+        POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return POLEE_OK;
+    }
+    void take(RegBlock &o)  // (ownership moves here)
+    {
+        v = o.v, tail_params = o.tail_params, tail_noise = o.tail_noise;
+        p.take(o.p), g.take(o.g), m.take(o.m), vv.take(o.vv), eps.take(o.eps);
+        stats.take(o.stats), small.take(o.small), loss.take(o.loss), acc.take(o.acc);
+    }
+    // prior pass of the view: stats (summed over ranks) -> the gradients of everything its columns share and loss[0]
+    // (+ extra_loss[0]); tick != nullptr: the finish kernel also advances the device clock.  A view with w_from_bias runs <0, 0>.
+    void launch_prior(hipStream_t st, const float *W, const float *extra_loss, uint32_t *tick, float *lr_t, float lr) const
+    {
+        const dim3 grid((unsigned)ceil_div(v.n, REG_BLOCK));
+        reg_dispatch(v, !v.w_from_bias, [&](auto ft, auto dt) {
+            hipLaunchKernelGGL((reg_cols_kernel<decltype(ft)::value, decltype(dt)::value>), grid, dim3(REG_BLOCK), 0, st, v, p.p, eps.p, W,
+                               stats.p, g.p, acc.p, small.p);
+        });
+        hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(64), 0, st, v, p.p, eps.p, small.p, stats.p, acc.p, g.p, loss.p, extra_loss, tick,
+                           lr_t, lr);
+    }
+};
+
+enum class IsoKind { none, gene, gene_isoform, joint };  // what polee_regression::iso holds
+
+// What a step of fit() with the device RNG tells the passes; the default is an evaluation (polee_regression_eval, the debug hooks,
+// steps with supplied noise).
+struct RegStep {
+    bool tick_in_finish = false;  // reg_finish_kernel advances the device clock
+    bool x_drawn = false;         // reg_draw_kernel has written x: reg_data_pass skips reg_sample_x_kernel
+    bool update_latent = false;   // reg_latent_kernel also applies Adam to a latent design
+};
 
 }  // namespace polee
 
@@ -854,11 +798,12 @@ using namespace polee;
 struct polee_regression {
     polee_ctx *ctx = nullptr;
     polee_approx *ap = nullptr;
-    RegView v{};
     float lr = 2e-3f;
     int64_t step = 0;  // ADAM steps taken
-    DevBuf<float> d_p, d_g, d_m, d_v, d_eps, d_design, d_W, d_ss, d_x, d_glik, d_lp, d_lse, d_small, d_loss, d_stats;
-    DevBuf<float> d_lse_acc, d_lr, d_trace;
+    RegBlock main;     // the model of polee_regression_create
+    RegBlock iso;      // the second block, of the kind below (empty: none)
+    IsoKind kind = IsoKind::none;
+    DevBuf<float> d_design, d_W, d_ss, d_x, d_glik, d_lp, d_lse, d_lse_acc, d_lr, d_trace;
     DevBuf<uint32_t> d_tick;
     DevBuf<uint64_t> d_seed;
     hipGraphExec_t graph = nullptr;  // one step (device RNG), replayed by polee_regression_fit
@@ -867,44 +812,23 @@ struct polee_regression {
         if (graph) (void)hipGraphExecDestroy(graph);
         graph = nullptr;
     }
-    bool tick_in_finish = false;  // (per step) reg_finish_kernel advances the device clock: fit()'s steps
-    bool x_drawn = false;         // (per step) reg_draw_kernel has written x: reg_data_pass skips reg_sample_x_kernel
     bool lse_valid = false;  // d_lse holds the log-sum-exp of a nearby qx_loc (shift of the multi-block kernel)
     DevBuf<float> d_lik_loc, d_lik_scale;  // point estimates + their scale: the Normal likelihood variant
-    DevBuf<double> d_acc;
-    // gene-level model: the likelihood handle over nt transcripts and the isoform block (see reg_iso_grad_kernel)
+    // gene-level models: the likelihood handle over nt transcripts; d_xi: x_isoform [S][nt], then d lp / d x_isoform
     polee_approx *gene_ap = nullptr;
     int32_t nt = 0;
-    DevBuf<float> d_ip, d_ig, d_im, d_iv, d_ieps, d_xi;
-    // gene-isoform model (RNASeqGeneIsoformLinearRegression, models/polee_regression.py:656-877): the isoform block
-    // is a regression of its own over the transcripts -- horseshoe+ coefficients over the isoform design, x_isoform_bias
-    // ~ Normal(0, 2), x_isoform_scale ~ InverseGamma(0.001, 0.001) -- laid out as a second RegView (vi, deg = 0) and
-    // run through the same data / column / finish kernels
-    bool iso_reg = false;
-    // joint model (RNASeqJointLinearRegression): vi = the splice-feature block (P columns), the transcripts' part of the
-    // block behind it in d_ip; the feature matrix both ways
-    bool joint = false;
-    int32_t P = 0;
+    DevBuf<float> d_xi;
+    // gene-isoform model (RNASeqGeneIsoformLinearRegression, models/polee_regression.py:656-877): iso is a regression of its own
+    // over the transcripts -- horseshoe+ coefficients over the isoform design, x_isoform_bias ~ Normal(0, 2), x_isoform_scale ~
+    // InverseGamma(0.001, 0.001) -- a view with deg = 0 and no tail
+    DevBuf<float> d_idesign;
+    // joint model (RNASeqJointLinearRegression): iso.v = the splice-feature block (iso.v.n features), the transcripts' part its
+    // tail; the feature matrix both ways
     DevBuf<int32_t> d_tptr, d_tfeat, d_pptr, d_ptrans;
     DevBuf<float> d_mu, d_resid, d_hinges;
     std::vector<float> h_hinges;  // (kept from create: the joint model's weights follow the sampled bias)
     float bandwidth = 1.0f;
-    RegView vi{};
-    DevBuf<float> d_idesign, d_istats, d_ismall, d_iloss;
-    DevBuf<double> d_iacc;
-    int64_t num_iso_params() const
-    {
-        if (joint) return vi.num_params() + 2 * (int64_t)nt + 2 * (int64_t)v.S * nt;
-        return !gene_ap ? 0 : (iso_reg ? vi.num_params() : 2 * (int64_t)nt + 2 * (int64_t)v.S * nt);
-    }
-    int64_t num_iso_noise() const
-    {
-        if (joint) return vi.num_noise() + (int64_t)nt + (int64_t)v.S * nt;
-        return !gene_ap ? 0 : (iso_reg ? vi.num_noise() : (int64_t)nt + (int64_t)v.S * nt);
-    }
-    int64_t num_iso_stats() const { return (int64_t)(vi.F + 2) * vi.n + REG_SLOTS; }
-    polee_comm *comm = nullptr;  // samples sharded over ranks: one all-reduce of d_stats per step
-    int64_t num_stats() const { return (int64_t)(v.F + 2) * v.n + REG_SLOTS; }
+    polee_comm *comm = nullptr;  // samples sharded over ranks: one all-reduce of main.stats per step
     // classify (models/polee_regression.py:342-413): the design matrix is replaced per step (polee_regression_set_design), every
     // evaluation also leaves d loss / d design in d_dF, and Adam only moves the flat parameters [train_lo, train_hi)
     bool want_dgrad = false;
@@ -919,160 +843,130 @@ struct polee_regression {
 
 namespace {
 
-// data pass for the noise in d_eps: d_stats (this rank's samples) and the gradients of qx_*
-polee_status reg_data_pass(polee_regression *r)
+// data pass for the noise in the blocks' eps: main.stats (this rank's samples) and the gradients of qx_*
+polee_status reg_data_pass(polee_regression *r, const RegStep &step)
 {
     polee_ctx *ctx = r->ctx;
-    const RegView &v = r->v;
+    const RegBlock &mb = r->main, &ib = r->iso;
+    const RegView &v = mb.v;
     hipStream_t st = ctx->stream;
     const int64_t sn = (int64_t)v.S * v.n;
     if (!v.point) {
         if (r->lse_valid) {
-            hipLaunchKernelGGL(reg_lse_accum_kernel, dim3((unsigned)ceil_div(v.n, 4096), v.S), dim3(256), 0, st, v,
-                               r->d_p.p, r->d_lse.p, r->d_lse_acc.p);
-            hipLaunchKernelGGL(reg_lse_finish_kernel, dim3((unsigned)ceil_div(v.S, 64)), dim3(64), 0, st, v.S,
-                               r->d_lse.p, r->d_lse_acc.p);
+            hipLaunchKernelGGL(reg_lse_accum_kernel, dim3((unsigned)ceil_div(v.n, 4096), v.S), dim3(256), 0, st, v, mb.p.p, r->d_lse.p,
+                               r->d_lse_acc.p);
+            hipLaunchKernelGGL(reg_lse_finish_kernel, dim3((unsigned)ceil_div(v.S, 64)), dim3(64), 0, st, v.S, r->d_lse.p, r->d_lse_acc.p);
         } else
-            hipLaunchKernelGGL(reg_lse_kernel, dim3(v.S), dim3(1024), 0, st, v, r->d_p.p, r->d_lse.p);
+            hipLaunchKernelGGL(reg_lse_kernel, dim3(v.S), dim3(1024), 0, st, v, mb.p.p, r->d_lse.p);
         r->lse_valid = true;
-        if (!r->x_drawn)
-            hipLaunchKernelGGL(reg_sample_x_kernel, dim3((unsigned)ceil_div(sn, 256)), dim3(256), 0, st, v, r->d_p.p,
-                               r->d_eps.p, r->d_x.p);
+        if (!step.x_drawn)
+            hipLaunchKernelGGL(reg_sample_x_kernel, dim3((unsigned)ceil_div(sn, 256)), dim3(256), 0, st, v, mb.p.p, mb.eps.p, r->d_x.p);
         POLEE_KERNEL_CHECK(ctx);
         if (r->gene_ap) {
-            if (r->joint)
-                hipLaunchKernelGGL(reg_joint_sample_kernel, dim3((unsigned)ceil_div((int64_t)v.S * r->nt, 256)), dim3(256), 0,
-                                   st, v.S, r->nt, (const float *)(r->d_ip.p + r->vi.num_params()),
-                                   (const float *)(r->d_ieps.p + r->vi.num_noise()), r->d_xi.p);
-            else if (r->iso_reg)
-                hipLaunchKernelGGL(reg_sample_x_kernel, dim3((unsigned)ceil_div((int64_t)v.S * r->nt, 256)), dim3(256), 0,
-                                   st, r->vi, r->d_ip.p, r->d_ieps.p, r->d_xi.p);
-            else
-                hipLaunchKernelGGL(reg_iso_sample_kernel, dim3((unsigned)ceil_div((int64_t)v.S * r->nt, 256)), dim3(256),
-                                   0, st, v.S, r->nt, r->d_ip.p, r->d_ieps.p, r->d_xi.p);
+            const dim3 grid((unsigned)ceil_div((int64_t)v.S * r->nt, 256));
+            if (r->kind == IsoKind::gene_isoform)
+                hipLaunchKernelGGL(reg_sample_x_kernel, grid, dim3(256), 0, st, ib.v, ib.p.p, ib.eps.p, r->d_xi.p);
+            else  // the block's tail: all of it (gene), or what follows the splice view (joint)
+                hipLaunchKernelGGL(reg_iso_sample_kernel, grid, dim3(256), 0, st, v.S, r->nt, ib.p.p + ib.view_params(),
+                                   ib.eps.p + ib.view_noise(), r->d_xi.p);
             POLEE_KERNEL_CHECK(ctx);
             POLEE_TRY(approx_gene_logprob_device(r->gene_ap, r->d_x.p, r->d_xi.p, r->d_lp.p, r->d_glik.p));
         } else if (r->d_lik_loc.p) {
-            hipLaunchKernelGGL(reg_normal_lik_kernel, dim3(v.S), dim3(1024), 0, st, v.n, r->d_x.p, r->d_lik_loc.p,
-                               r->d_lik_scale.p, r->d_lp.p, r->d_glik.p);
+            hipLaunchKernelGGL(reg_normal_lik_kernel, dim3(v.S), dim3(1024), 0, st, v.n, r->d_x.p, r->d_lik_loc.p, r->d_lik_scale.p, r->d_lp.p,
+                               r->d_glik.p);
             POLEE_KERNEL_CHECK(ctx);
         } else if (r->ap)
             POLEE_TRY(polee_approx_logprob_device(r->ap, r->d_x.p, r->d_lp.p, r->d_glik.p));
     }
-    // (the loss slots of d_stats, d_acc and d_small are zero here: reg_finish_kernel clears what it reads)
-    const float *lp = (!v.point && (r->ap || r->d_lik_loc.p || r->gene_ap)) ? r->d_lp.p : nullptr;
-    const dim3 grid((unsigned)ceil_div(v.n, REG_BLOCK));
-#define POLEE_REG_DATA(FT, DT)                                                                                          \
-    hipLaunchKernelGGL((reg_data_kernel<FT, DT>), grid, dim3(REG_BLOCK), 0, st, v, r->d_p.p, r->d_eps.p, r->d_design.p, \
-                       r->d_W.p, r->d_ss.p, r->d_x.p, r->d_glik.p, r->d_lse.p, lp, r->d_g.p, r->d_stats.p)
-    // the reference's default degree (15) with up to four factors runs with fixed trip counts
-    if (v.deg == 15 && v.F == 1) POLEE_REG_DATA(1, 15);
-    else if (v.deg == 15 && v.F == 2) POLEE_REG_DATA(2, 15);
-    else if (v.deg == 15 && v.F == 3) POLEE_REG_DATA(3, 15);
-    else if (v.deg == 15 && v.F == 4) POLEE_REG_DATA(4, 15);
-    else POLEE_REG_DATA(0, 0);
-#undef POLEE_REG_DATA
-    if (r->gene_ap && r->joint) {  // (d_xi now holds d lp / d x_iso): the splice block's predictor, the transcripts, back to the features
-        const RegView &vs = r->vi;
-        hipLaunchKernelGGL(reg_joint_mean_kernel, dim3((unsigned)ceil_div(vs.n, 128)), dim3(128), 0, st, vs, v.S, r->d_ip.p,
-                           r->d_ieps.p, r->d_design.p, r->d_mu.p);
-        hipLaunchKernelGGL(reg_joint_iso_kernel, dim3((unsigned)ceil_div(r->nt, 256)), dim3(256), 0, st, v.S, r->nt, r->P,
-                           (const float *)(r->d_ip.p + vs.num_params()), (const float *)(r->d_ieps.p + vs.num_noise()),
-                           (const float *)r->d_xi.p, (const float *)r->d_mu.p, r->d_tptr.p, r->d_tfeat.p,
-                           r->d_ig.p + vs.num_params(), r->d_resid.p, r->d_stats.p + r->num_stats() - REG_SLOTS);
-        hipLaunchKernelGGL(reg_joint_agg_kernel, dim3((unsigned)ceil_div(r->P, 128)), dim3(128), 0, st, v.S, r->nt, r->P, vs.F,
-                           (const float *)r->d_resid.p, r->d_design.p, r->d_pptr.p, r->d_ptrans.p, r->d_istats.p);
-    } else if (r->gene_ap && r->iso_reg)  // (d_xi now holds d lp / d x_isoform): the isoform block's own data pass
-        hipLaunchKernelGGL((reg_data_kernel<0, 0>), dim3((unsigned)ceil_div(r->nt, REG_BLOCK)), dim3(REG_BLOCK), 0, st,
-                           r->vi, r->d_ip.p, r->d_ieps.p, r->d_idesign.p, (const float *)nullptr, (const float *)nullptr,
-                           (const float *)nullptr, r->d_xi.p, (const float *)nullptr, (const float *)nullptr, r->d_ig.p,
-                           r->d_istats.p);
-    else if (r->gene_ap)
-        hipLaunchKernelGGL(reg_iso_grad_kernel, dim3((unsigned)ceil_div(r->nt, 256)), dim3(256), 0, st, v.S, r->nt,
-                           r->d_ip.p, r->d_ieps.p, r->d_xi.p, r->d_ig.p, r->d_stats.p + r->num_stats() - REG_SLOTS);
+    // (the loss slots of stats, acc and small are zero here: reg_finish_kernel clears what it reads)
+    const float *lp = (!v.point && (r->ap || r->d_lik_loc.p || r->gene_ap)) ? r->d_lp.p : nullptr, *none = nullptr;
+    reg_dispatch(v, true, [&](auto ft, auto dt) {
+        hipLaunchKernelGGL((reg_data_kernel<decltype(ft)::value, decltype(dt)::value>), dim3((unsigned)ceil_div(v.n, REG_BLOCK)), dim3(REG_BLOCK),
+                           0, st, v, mb.p.p, mb.eps.p, r->d_design.p, r->d_W.p, r->d_ss.p, r->d_x.p, r->d_glik.p, r->d_lse.p, lp, mb.g.p, mb.stats.p);
+    });
+    // (d_xi now holds d lp / d x_isoform)
+    if (r->kind == IsoKind::joint) {  // the splice block's predictor, the transcripts, back to the features
+        const RegView &vs = ib.v;
+        const int P = vs.n;
+        hipLaunchKernelGGL(reg_joint_mean_kernel, dim3((unsigned)ceil_div(P, 128)), dim3(128), 0, st, vs, v.S, ib.p.p, ib.eps.p, r->d_design.p,
+                           r->d_mu.p);
+        hipLaunchKernelGGL(reg_joint_iso_kernel, dim3((unsigned)ceil_div(r->nt, 256)), dim3(256), 0, st, v.S, r->nt, P, ib.p.p + vs.num_params(),
+                           ib.eps.p + vs.num_noise(), r->d_xi.p, r->d_mu.p, r->d_tptr.p, r->d_tfeat.p, ib.g.p + vs.num_params(), r->d_resid.p,
+                           mb.loss_slots());
+        hipLaunchKernelGGL(reg_joint_agg_kernel, dim3((unsigned)ceil_div(P, 128)), dim3(128), 0, st, v.S, r->nt, P, vs.F, r->d_resid.p,
+                           r->d_design.p, r->d_pptr.p, r->d_ptrans.p, ib.stats.p);
+    } else if (r->kind == IsoKind::gene_isoform)  // the isoform block's own data pass
+        hipLaunchKernelGGL((reg_data_kernel<0, 0>), dim3((unsigned)ceil_div(r->nt, REG_BLOCK)), dim3(REG_BLOCK), 0, st, ib.v, ib.p.p, ib.eps.p,
+                           r->d_idesign.p, none, none, none, r->d_xi.p, none, none, ib.g.p, ib.stats.p);
+    else if (r->kind == IsoKind::gene)
+        hipLaunchKernelGGL(reg_iso_grad_kernel, dim3((unsigned)ceil_div(r->nt, 256)), dim3(256), 0, st, v.S, r->nt, ib.p.p, ib.eps.p, r->d_xi.p,
+                           ib.g.p, mb.loss_slots());
     POLEE_KERNEL_CHECK(ctx);
     return POLEE_OK;
 }
 
-// prior pass: d_stats (summed over ranks) -> loss and the gradients of everything the ranks share
-polee_status reg_prior_pass(polee_regression *r)
+// prior pass: stats (summed over ranks) -> loss and the gradients of everything the ranks share: the second block if it has
+// columns (its loss joins the model's), then the main one
+polee_status reg_prior_pass(polee_regression *r, const RegStep &step)
+{
+    const bool second = r->iso.has_cols();
+    if (second) r->iso.launch_prior(r->ctx->stream, nullptr, nullptr, nullptr, nullptr, 0.0f);
+    r->main.launch_prior(r->ctx->stream, r->d_W.p, second ? r->iso.loss.p : nullptr, step.tick_in_finish ? r->d_tick.p : nullptr, r->d_lr.p,
+                         r->lr);
+    POLEE_KERNEL_CHECK(r->ctx);
+    return POLEE_OK;
+}
+
+// loss and gradient at the current parameters for the noise in the blocks' eps
+polee_status reg_eval_device(polee_regression *r, const RegStep &step = RegStep{})
 {
     polee_ctx *ctx = r->ctx;
-    const RegView &v = r->v;
-    hipStream_t st = ctx->stream;
-    const dim3 grid((unsigned)ceil_div(v.n, REG_BLOCK));
-#define POLEE_REG_COLS(FT, DT)                                                                                     \
-    hipLaunchKernelGGL((reg_cols_kernel<FT, DT>), grid, dim3(REG_BLOCK), 0, st, v, r->d_p.p, r->d_eps.p, r->d_W.p, \
-                       r->d_stats.p, r->d_g.p, r->d_acc.p, r->d_small.p)
-    if (v.w_from_bias) POLEE_REG_COLS(0, 0);
-    else if (v.deg == 15 && v.F == 1) POLEE_REG_COLS(1, 15);
-    else if (v.deg == 15 && v.F == 2) POLEE_REG_COLS(2, 15);
-    else if (v.deg == 15 && v.F == 3) POLEE_REG_COLS(3, 15);
-    else if (v.deg == 15 && v.F == 4) POLEE_REG_COLS(4, 15);
-    else POLEE_REG_COLS(0, 0);
-#undef POLEE_REG_COLS
-    if (r->iso_reg || r->joint) {  // the isoform / splice block's columns and its global scale; its loss joins the model's below
-        hipLaunchKernelGGL((reg_cols_kernel<0, 0>), dim3((unsigned)ceil_div(r->vi.n, REG_BLOCK)), dim3(REG_BLOCK), 0, st,
-                           r->vi, r->d_ip.p, r->d_ieps.p, (const float *)nullptr, r->d_istats.p, r->d_ig.p, r->d_iacc.p,
-                           r->d_ismall.p);
-        hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(64), 0, st, r->vi, r->d_ip.p, r->d_ieps.p, r->d_ismall.p,
-                           r->d_istats.p, r->d_iacc.p, r->d_ig.p, r->d_iloss.p, (const float *)nullptr, (uint32_t *)nullptr, (float *)nullptr, 0.0f);
-    }
-    hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(64), 0, st, v, r->d_p.p, r->d_eps.p, r->d_small.p,
-                       r->d_stats.p, r->d_acc.p, r->d_g.p, r->d_loss.p, (r->iso_reg || r->joint) ? r->d_iloss.p : (const float *)nullptr,
-                       r->tick_in_finish ? r->d_tick.p : (uint32_t *)nullptr, r->d_lr.p, r->lr);
-    POLEE_KERNEL_CHECK(ctx);
-    return POLEE_OK;
-}
-
-// loss and gradient at the current parameters for the noise in d_eps
-// (update_latent: a step of fit() -- reg_latent_kernel also applies Adam to a latent design)
-polee_status reg_eval_device(polee_regression *r, bool update_latent = false)
-{
-    POLEE_TRY(reg_data_pass(r));
+    const RegBlock &mb = r->main;
+    const RegView &v = mb.v;
+    POLEE_TRY(reg_data_pass(r, step));
     if (r->want_dgrad) {
-        const RegView &v = r->v;
         if (!r->latent)  // (a latent handle's copies are zero here: reg_latent_kernel clears what it reads)
-            POLEE_HIP_TRY(r->ctx, hipMemsetAsync(r->d_dF.p, 0, sizeof(float) * (size_t)REG_SLOTS * v.S * v.F, r->ctx->stream));
-        hipLaunchKernelGGL(reg_design_grad_kernel, dim3((unsigned)ceil_div(v.n, REG_BLOCK)), dim3(REG_BLOCK), 0, r->ctx->stream, v,
-                           r->d_p.p, r->d_eps.p, r->d_design.p, r->d_W.p, r->d_ss.p, r->d_x.p, r->d_dF.p);
-        POLEE_KERNEL_CHECK(r->ctx);
+            POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_dF.p, 0, sizeof(float) * (size_t)REG_SLOTS * v.S * v.F, ctx->stream));
+        hipLaunchKernelGGL(reg_design_grad_kernel, dim3((unsigned)ceil_div(v.n, REG_BLOCK)), dim3(REG_BLOCK), 0, ctx->stream, v, mb.p.p,
+                           mb.eps.p, r->d_design.p, r->d_W.p, r->d_ss.p, r->d_x.p, r->d_dF.p);
+        POLEE_KERNEL_CHECK(ctx);
     }
-    if (r->comm && r->comm->nranks > 1)
-        POLEE_TRY(comm_allreduce_device(r->comm, r->d_stats.p, (size_t)r->num_stats(), false));
-    POLEE_TRY(reg_prior_pass(r));
+    if (r->comm && r->comm->nranks > 1) POLEE_TRY(comm_allreduce_device(r->comm, mb.stats.p, (size_t)mb.num_stats(), false));
+    POLEE_TRY(reg_prior_pass(r, step));
     if (r->latent) {
         const float sg = r->prior_scale;
-        hipLaunchKernelGGL(reg_latent_kernel, dim3(1), dim3(256), 0, r->ctx->stream, r->v.S * r->v.F, r->d_dF.p, r->d_design.p,
-                           r->d_zm.p, r->d_zv.p, r->d_gz.p, 1.0f / (sg * sg), logf(sg) + HALF_LOG2PI, (const float *)r->d_lr.p,
-                           r->d_loss.p, update_latent ? 1 : 0);
-        POLEE_KERNEL_CHECK(r->ctx);
+        hipLaunchKernelGGL(reg_latent_kernel, dim3(1), dim3(256), 0, ctx->stream, v.S * v.F, r->d_dF.p, r->d_design.p, r->d_zm.p, r->d_zv.p,
+                           r->d_gz.p, 1.0f / (sg * sg), logf(sg) + HALF_LOG2PI, r->d_lr.p, mb.loss.p, step.update_latent ? 1 : 0);
+        POLEE_KERNEL_CHECK(ctx);
     }
     return POLEE_OK;
 }
 
-// The latents every rank shares are drawn from (seed, step) alone, so that replicas stay identical; the noise of
-// x belongs to a rank's own samples and is salted with the rank.
+// The latents every rank shares are drawn from (seed, step) alone, so that replicas stay identical; the noise of x belongs to a
+// rank's own samples and is salted with the rank.
+uint64_t rank_salt(const polee_regression *r) { return REG_RANK_SALT * (uint64_t)(r->comm ? r->comm->rank + 1 : 1); }
+
+// seed / step: immediates, or (device_clock) the fit's seed and the clock's value + tick_ahead
+void reg_launch_noise(polee_regression *r, int64_t count, uint64_t seed, uint32_t step, bool device_clock, uint64_t salt, float *eps,
+                      uint32_t tick_ahead = 0u)
+{
+    hipLaunchKernelGGL(reg_noise_kernel, dim3((unsigned)ceil_div(ceil_div(count, 4), 256)), dim3(256), 0, r->ctx->stream, count, seed, step,
+                       device_clock ? r->d_seed.p : nullptr, device_clock ? r->d_tick.p : nullptr, salt, eps, tick_ahead);
+}
+
 polee_status reg_fill_noise(polee_regression *r, const float *noise, uint64_t seed, uint32_t step, bool device_clock)
 {
-    polee_ctx *ctx = r->ctx;
-    const int64_t ne = r->v.num_noise(), shared = r->v.e_x(), own = ne - shared;
+    RegBlock &mb = r->main, &ib = r->iso;
+    const int64_t ne = mb.num_noise(), shared = mb.v.e_x(), own = ne - shared;
     if (noise) {
-        POLEE_TRY(r->d_eps.upload(ctx, noise, (size_t)ne));
-        if (r->gene_ap) POLEE_TRY(r->d_ieps.upload(ctx, noise + ne, (size_t)r->num_iso_noise()));
+        POLEE_TRY(mb.eps.upload(r->ctx, noise, (size_t)ne));
+        if (r->gene_ap) POLEE_TRY(ib.eps.upload(r->ctx, noise + ne, (size_t)ib.num_noise()));
         return POLEE_OK;
     }
-    const uint64_t salt = 0xD1B54A32D192ED03ull * (uint64_t)(r->comm ? r->comm->rank + 1 : 1);
-    const uint64_t *sd = device_clock ? r->d_seed.p : nullptr;
-    const uint32_t *tk = device_clock ? r->d_tick.p : nullptr;
-    hipLaunchKernelGGL(reg_noise_kernel, dim3((unsigned)ceil_div(ceil_div(shared, 4), 256)), dim3(256), 0, ctx->stream,
-                       shared, seed, step, sd, tk, (uint64_t)0, r->d_eps.p);
-    hipLaunchKernelGGL(reg_noise_kernel, dim3((unsigned)ceil_div(ceil_div(own, 4), 256)), dim3(256), 0, ctx->stream, own,
-                       seed, step, sd, tk, salt, r->d_eps.p + shared);
-    if (r->gene_ap)
-        hipLaunchKernelGGL(reg_noise_kernel, dim3((unsigned)ceil_div(ceil_div(r->num_iso_noise(), 4), 256)), dim3(256), 0,
-                           ctx->stream, r->num_iso_noise(), seed, step, sd, tk, salt ^ 0x69736f666f726d73ull, r->d_ieps.p);
-    POLEE_KERNEL_CHECK(ctx);
+    reg_launch_noise(r, shared, seed, step, device_clock, 0, mb.eps.p);
+    reg_launch_noise(r, own, seed, step, device_clock, rank_salt(r), mb.eps.p + shared);
+    if (r->gene_ap) reg_launch_noise(r, ib.num_noise(), seed, step, device_clock, rank_salt(r) ^ REG_ISO_SALT, ib.eps.p);
+    POLEE_KERNEL_CHECK(r->ctx);
     return POLEE_OK;
 }
 
@@ -1080,41 +974,103 @@ polee_status reg_fill_noise(polee_regression *r, const float *noise, uint64_t se
 polee_status reg_enqueue_step(polee_regression *r, const float *noise, bool want_trace)
 {
     polee_ctx *ctx = r->ctx;
-    const int64_t P = r->v.num_params();
+    const RegBlock &mb = r->main, &ib = r->iso;
+    const RegView &v = mb.v;
+    RegStep step;
+    step.update_latent = r->latent;
     if (noise) {  // the caller's noise: uploaded; the clock ticks in its own launch
         hipLaunchKernelGGL(reg_tick_kernel, dim3(1), dim3(1), 0, ctx->stream, r->d_tick.p, r->d_lr.p, r->lr);
         POLEE_TRY(reg_fill_noise(r, noise, 0, 0, true));
-        POLEE_TRY(reg_eval_device(r, r->latent));
     } else {
         // device RNG: one launch draws every latent of the step number the clock is ABOUT to show and x with it; the clock is
         // advanced by reg_finish_kernel (in front of Adam, behind everything that reads the noise)
-        const int64_t ne = r->v.num_noise(), shared = r->v.e_x(), own = ne - shared;
-        const uint64_t salt = 0xD1B54A32D192ED03ull * (uint64_t)(r->comm ? r->comm->rank + 1 : 1);
-        const bool with_x = !r->v.point && own == (int64_t)r->v.S * r->v.n;
-        hipLaunchKernelGGL(reg_draw_kernel, dim3((unsigned)ceil_div((shared + 3) / 4 + (own + 3) / 4, 256)), dim3(256), 0, ctx->stream, r->v,
-                           shared, own, (const uint64_t *)r->d_seed.p, (const uint32_t *)r->d_tick.p, salt, (const float *)r->d_p.p, r->d_eps.p,
-                           with_x ? r->d_x.p : (float *)nullptr);
-        if (r->gene_ap)
-            hipLaunchKernelGGL(reg_noise_kernel, dim3((unsigned)ceil_div(ceil_div(r->num_iso_noise(), 4), 256)), dim3(256), 0,
-                               ctx->stream, r->num_iso_noise(), (uint64_t)0, 0u, (const uint64_t *)r->d_seed.p, (const uint32_t *)r->d_tick.p,
-                               salt ^ 0x69736f666f726d73ull, r->d_ieps.p, 1u);
-        r->tick_in_finish = true;
-        r->x_drawn = with_x;
-        const polee_status es = reg_eval_device(r, r->latent);
-        r->tick_in_finish = false;
-        r->x_drawn = false;
-        POLEE_TRY(es);
+        const int64_t shared = v.e_x(), own = v.num_noise() - shared;
+        step.tick_in_finish = true;
+        step.x_drawn = !v.point && own == (int64_t)v.S * v.n;
+        hipLaunchKernelGGL(reg_draw_kernel, dim3((unsigned)ceil_div((shared + 3) / 4 + (own + 3) / 4, 256)), dim3(256), 0, ctx->stream, v, shared,
+                           own, r->d_seed.p, r->d_tick.p, rank_salt(r), mb.p.p, mb.eps.p, step.x_drawn ? r->d_x.p : nullptr);
+        if (r->gene_ap) reg_launch_noise(r, ib.num_noise(), 0, 0u, true, rank_salt(r) ^ REG_ISO_SALT, ib.eps.p, 1u);
     }
-    const int64_t lo = r->train_hi < 0 ? 0 : r->train_lo, cnt = r->train_hi < 0 ? P : r->train_hi - r->train_lo;
-    hipLaunchKernelGGL(reg_adam_kernel, dim3((unsigned)std::max<int64_t>(ceil_div(cnt, 256), 1)), dim3(256), 0, ctx->stream, cnt,
-                       r->d_p.p + lo, r->d_g.p + lo, r->d_m.p + lo, r->d_v.p + lo, r->d_lr.p, r->d_loss.p,
-                       want_trace ? r->d_trace.p : nullptr, r->d_tick.p);
+    POLEE_TRY(reg_eval_device(r, step));
+    const int64_t lo = r->train_hi < 0 ? 0 : r->train_lo, cnt = r->train_hi < 0 ? v.num_params() : r->train_hi - r->train_lo;
+    hipLaunchKernelGGL(reg_adam_kernel, dim3((unsigned)std::max<int64_t>(ceil_div(cnt, 256), 1)), dim3(256), 0, ctx->stream, cnt, mb.p.p + lo,
+                       mb.g.p + lo, mb.m.p + lo, mb.vv.p + lo, r->d_lr.p, mb.loss.p, want_trace ? r->d_trace.p : nullptr, r->d_tick.p);
     if (r->gene_ap)
-        hipLaunchKernelGGL(reg_adam_kernel, dim3((unsigned)ceil_div(r->num_iso_params(), 256)), dim3(256), 0, ctx->stream,
-                           r->num_iso_params(), r->d_ip.p, r->d_ig.p, r->d_im.p, r->d_iv.p, r->d_lr.p, r->d_loss.p,
-                           (float *)nullptr, r->d_tick.p);
+        hipLaunchKernelGGL(reg_adam_kernel, dim3((unsigned)ceil_div(ib.num_params(), 256)), dim3(256), 0, ctx->stream, ib.num_params(), ib.p.p,
+                           ib.g.p, ib.m.p, ib.vv.p, r->d_lr.p, mb.loss.p, (float *)nullptr, r->d_tick.p);
     POLEE_KERNEL_CHECK(ctx);
     return POLEE_OK;
+}
+
+// Every entry point that works on a handle: the arguments are there, the calling thread is on the handle's device, and nothing
+// unwinds through the C ABI.
+template <class F>
+polee_status reg_entry(polee_regression *r, bool args_ok, const char *what, F &&f)
+{
+    if (!r || !args_ok) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "%s: null argument", what);
+    return guarded(r->ctx, what, [&]() -> polee_status {
+        POLEE_TRY(use_device(r->ctx));
+        return f();
+    });
+}
+
+// column means over the S rows of x [S][n]
+std::vector<double> column_means(const float *x, int S, int n)
+{
+    std::vector<double> mean((size_t)n, 0.0);
+    for (int s = 0; s < S; ++s)
+        for (int j = 0; j < n; ++j) mean[(size_t)j] += x[(size_t)s * n + j];
+    for (auto &m : mean) m /= S;
+    return mean;
+}
+
+// Initial values of the horseshoe part of a view and of its bias and x_scale rows (models/polee_regression.py:49-119, :740-775,
+// :925-1010) into p (zeros): every loc 0 and every softplus scale -1, but qw_softplus_scale = w_s, the bias loc = bias_loc
+// (null: 0) and the x_scale loc = xs_loc (a view without x_scale keeps both of its rows at 0)
+void init_view_params(const RegView &v, std::vector<float> &p, float w_s, const double *bias_loc, float xs_loc)
+{
+    const int64_t Fn = v.Fn();
+    p[1] = p[3] = -1.0f;
+    for (int a = 1; a < 8; a += 2) std::fill_n(p.begin() + v.o_cols() + a * Fn, Fn, -1.0f);
+    std::fill_n(p.begin() + v.o_cols() + 9 * Fn, Fn, w_s);
+    for (int j = 0; j < v.n; ++j) {
+        p[(size_t)(v.o_bias_loc() + j)] = bias_loc ? (float)bias_loc[j] : 0.0f;
+        p[(size_t)(v.o_bias_s() + j)] = -1.0f;
+        p[(size_t)(v.o_xs_loc() + j)] = v.no_xs ? 0.0f : xs_loc;
+        p[(size_t)(v.o_xs_s() + j)] = v.no_xs ? 0.0f : -1.0f;
+    }
+}
+
+// What the three gene-level likelihoods share.  First their checks of the handle and of ap (nt: its transcripts) ...
+polee_status gene_likelihood_check(polee_regression *r, polee_approx *ap, int32_t *nt)
+{
+    polee_ctx *ctx = r->ctx;
+    int32_t aS;
+    approx_dims(ap, &aS, nt);
+    if (approx_ctx(ap) != ctx || aS != r->main.v.S)
+        return fail(ctx, POLEE_ERR_BAD_ARG, "the approximation handle holds %d samples, the model %d", aS, r->main.v.S);
+    if (r->main.v.point) return fail(ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is built without point estimates only");
+    if (r->latent) return fail(ctx, POLEE_ERR_UNSUPPORTED, "a latent design belongs to the transcript-level model only");
+    if (r->comm && r->comm->nranks > 1) return fail(ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is not sharded over ranks");
+    return POLEE_OK;
+}
+// ... then, with the second block built, their last steps that can fail -- x_isoform's buffer, and the caller's approximation
+// handle learns the genes (the model's features) ...
+polee_status gene_likelihood_prepare(polee_regression *r, polee_approx *ap, const int32_t *gene_of, int32_t nt, DevBuf<float> &xi)
+{
+    POLEE_TRY(xi.alloc(r->ctx, (size_t)r->main.v.S * nt));
+    return approx_set_genes(ap, gene_of, r->main.v.n);
+}
+// ... and only then the handle changes: nothing here can fail.
+void gene_likelihood_attach(polee_regression *r, polee_approx *ap, int32_t nt, IsoKind kind, RegBlock &blk, DevBuf<float> &xi)
+{
+    r->drop_graph();
+    r->gene_ap = ap;
+    r->nt = nt;
+    r->ap = nullptr;
+    r->kind = kind;
+    r->iso.take(blk);
+    r->d_xi.take(xi);
 }
 
 }  // namespace
@@ -1127,96 +1083,72 @@ polee_status polee_regression_create(polee_ctx *ctx, polee_approx *ap, int32_t S
                                      float x_bias_scale0, int use_distortion, float scale_penalty,
                                      int use_point_estimates, polee_regression **out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!out || !design || !x_init || !sample_scales || S < 1 || F < 1 || n < 1 || degree < 1)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_create: bad argument");
-    if (F > REG_MAXF || degree > REG_MAXDEG)
-        return fail(ctx, POLEE_ERR_UNSUPPORTED, "at most %d factors and %d hinges (got %d, %d)", REG_MAXF, REG_MAXDEG, F,
-                    degree);
-    if (!(bandwidth > 0.0f) || !(x_bias_scale0 > 0.0f) || (!use_point_estimates && !(scale_penalty > 0.0f)))
-        return fail(ctx, POLEE_ERR_BAD_ARG, "bandwidth, x_bias_scale0 and scale_penalty must be positive");
-    if (ap) {
-        int32_t aS, an;
-        approx_dims(ap, &aS, &an);
-        if (approx_ctx(ap) != ctx || aS != S || an != n)
-            return fail(ctx, POLEE_ERR_BAD_ARG, "the approximation handle holds %d x %d, the model %d x %d", aS, an, S, n);
-    }
-    polee_regression *r = new (std::nothrow) polee_regression();
-    if (!r) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
-    r->ctx = ctx;
-    ctx_retain(ctx);
-    r->ap = use_point_estimates ? nullptr : ap;
-    RegView &v = r->v;
-    v = RegView{S, F, n, degree, use_distortion ? 1 : 0, use_point_estimates ? 1 : 0, x_bias_loc0, x_bias_scale0,
-                use_point_estimates ? 1.0f : scale_penalty};
-    const int64_t P = v.num_params(), sn = (int64_t)S * n, Fn = v.Fn();
-    // initial values (models/polee_regression.py:49-119)
-    std::vector<float> p((size_t)P, 0.0f);
-    std::vector<double> mean((size_t)n, 0.0);
-    if (x_init_mean)  // the column means over ALL samples when this handle holds a shard of them
-        for (int j = 0; j < n; ++j) mean[(size_t)j] = x_init_mean[j];
-    else {
-        for (int s = 0; s < S; ++s)
-            for (int j = 0; j < n; ++j) mean[(size_t)j] += x_init[(size_t)s * n + j];
-        for (auto &m : mean) m /= S;
-    }
-    p[1] = p[3] = -1.0f;
-    for (int d = 0; d < degree; ++d) p[(size_t)(v.o_conc() + d)] = p[(size_t)(v.o_scc() + d)] = 1.0f;
-    for (int a = 1; a < 8; a += 2) std::fill_n(p.begin() + v.o_cols() + a * Fn, Fn, -1.0f);
-    for (int j = 0; j < n; ++j) {
-        p[(size_t)(v.o_bias_loc() + j)] = (float)mean[(size_t)j];
-        p[(size_t)(v.o_bias_s() + j)] = -1.0f;
-        p[(size_t)(v.o_xs_loc() + j)] = -0.5f;
-        p[(size_t)(v.o_xs_s() + j)] = -1.0f;
-    }
-    std::copy_n(x_init, sn, p.begin() + v.o_qx_loc());
-    std::fill_n(p.begin() + v.o_qx_s(), sn, -1.0f);
-    // hinges (choose_knots, src/polee.py:69-76) and kernel-regression weights (:36-47)
-    std::vector<double> hg((size_t)degree);
-    if (hinges)
-        for (int d = 0; d < degree; ++d) hg[(size_t)d] = hinges[d];
-    else {
-        const double lo = *std::min_element(mean.begin(), mean.end()), hi = *std::max_element(mean.begin(), mean.end());
-        const double step = (hi - lo) / (degree + 1);
-        for (int d = 0; d < degree; ++d) hg[(size_t)d] = lo + (d + 1) * step;
-    }
-    r->h_hinges.assign(hg.begin(), hg.end());
-    r->bandwidth = bandwidth;
-    std::vector<float> W((size_t)degree * n);
-    for (int j = 0; j < n; ++j) {
-        double tot = 0.0, col[REG_MAXDEG];
-        for (int d = 0; d < degree; ++d) {
-            const double u = ((double)(float)mean[(size_t)j] - hg[(size_t)d]) / bandwidth;
-            col[d] = std::min(std::max(std::exp(-u * u), 1e-10), 1.0);
-            tot += col[d];
+    return guarded(ctx, "polee_regression_create", [&]() -> polee_status {
+        POLEE_TRY(use_device(ctx));
+        if (!out || !design || !x_init || !sample_scales || S < 1 || F < 1 || n < 1 || degree < 1)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_create: bad argument");
+        if (F > REG_MAXF || degree > REG_MAXDEG)
+            return fail(ctx, POLEE_ERR_UNSUPPORTED, "at most %d factors and %d hinges (got %d, %d)", REG_MAXF, REG_MAXDEG, F, degree);
+        if (!(bandwidth > 0.0f) || !(x_bias_scale0 > 0.0f) || (!use_point_estimates && !(scale_penalty > 0.0f)))
+            return fail(ctx, POLEE_ERR_BAD_ARG, "bandwidth, x_bias_scale0 and scale_penalty must be positive");
+        if (ap) {
+            int32_t aS, an;
+            approx_dims(ap, &aS, &an);
+            if (approx_ctx(ap) != ctx || aS != S || an != n)
+                return fail(ctx, POLEE_ERR_BAD_ARG, "the approximation handle holds %d x %d, the model %d x %d", aS, an, S, n);
         }
-        for (int d = 0; d < degree; ++d) W[(size_t)d * n + j] = (float)(col[d] / tot);
-    }
-    polee_status st = POLEE_OK;
-    auto ok = [&](polee_status s) { return st == POLEE_OK ? (st = s) == POLEE_OK : false; };
-    if (ok(r->d_p.upload(ctx, p)) && ok(r->d_W.upload(ctx, W)) && ok(r->d_design.upload(ctx, design, (size_t)S * F)) &&
-        ok(r->d_ss.upload(ctx, sample_scales, (size_t)S)) && ok(r->d_g.alloc(ctx, (size_t)P)) &&
-        ok(r->d_m.alloc(ctx, (size_t)P)) && ok(r->d_v.alloc(ctx, (size_t)P)) &&
-        ok(r->d_eps.alloc(ctx, (size_t)v.num_noise())) && ok(r->d_x.alloc(ctx, (size_t)sn)) &&
-        ok(r->d_glik.alloc(ctx, (size_t)sn)) && ok(r->d_lp.alloc(ctx, (size_t)S)) && ok(r->d_lse.alloc(ctx, (size_t)S)) && ok(r->d_lse_acc.alloc(ctx, (size_t)S)) && ok(r->d_lr.alloc(ctx, 1)) && ok(r->d_tick.alloc(ctx, 2)) && ok(r->d_seed.alloc(ctx, 1)) &&
-        ok(r->d_small.alloc(ctx, (size_t)REG_SLOTS * v.num_red())) && ok(r->d_stats.alloc(ctx, (size_t)r->num_stats())) && ok(r->d_loss.alloc(ctx, 1)) && ok(r->d_acc.alloc(ctx, REG_SLOTS))) {
-        hipError_t e = hipMemsetAsync(r->d_m.p, 0, sizeof(float) * P, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_v.p, 0, sizeof(float) * P, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_glik.p, 0, sizeof(float) * sn, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_lse.p, 0, sizeof(float) * S, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_lse_acc.p, 0, sizeof(float) * S, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_acc.p, 0, sizeof(double) * REG_SLOTS, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_small.p, 0, sizeof(float) * REG_SLOTS * v.num_red(), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(r->d_stats.p, 0, sizeof(float) * r->num_stats(), ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) st = fail(ctx, POLEE_ERR_HIP, "memset failed: %s", hipGetErrorString(e));
-    }
-    if (st != POLEE_OK) {
-        polee_regression_destroy(r);
-        return st;
-    }
-    *out = r;
-    return POLEE_OK;
+        // (the handle is destroyed on every early return and when something below throws)
+        std::unique_ptr<polee_regression, void (*)(polee_regression *)> handle(new polee_regression(), polee_regression_destroy);
+        polee_regression *r = handle.get();
+        r->ctx = ctx;
+        ctx_retain(ctx);
+        r->ap = use_point_estimates ? nullptr : ap;
+        const RegView v{S, F, n, degree, use_distortion ? 1 : 0, use_point_estimates ? 1 : 0, x_bias_loc0, x_bias_scale0,
+                        use_point_estimates ? 1.0f : scale_penalty};
+        const size_t sn = (size_t)S * n;
+        // initial values (models/polee_regression.py:49-119); x_init_mean: the column means over ALL samples when this handle
+        // holds a shard of them
+        const std::vector<double> mean = x_init_mean ? std::vector<double>(x_init_mean, x_init_mean + n) : column_means(x_init, S, n);
+        std::vector<float> p((size_t)v.num_params(), 0.0f);
+        init_view_params(v, p, 0.0f, mean.data(), -0.5f);
+        for (int d = 0; d < degree; ++d) p[(size_t)(v.o_conc() + d)] = p[(size_t)(v.o_scc() + d)] = 1.0f;
+        std::copy_n(x_init, sn, p.begin() + v.o_qx_loc());
+        std::fill_n(p.begin() + v.o_qx_s(), sn, -1.0f);
+        // hinges (choose_knots, src/polee.py:69-76) and kernel-regression weights (:36-47)
+        std::vector<double> hg((size_t)degree);
+        if (hinges)
+            for (int d = 0; d < degree; ++d) hg[(size_t)d] = hinges[d];
+        else {
+            const double lo = *std::min_element(mean.begin(), mean.end()), hi = *std::max_element(mean.begin(), mean.end());
+            const double step = (hi - lo) / (degree + 1);
+            for (int d = 0; d < degree; ++d) hg[(size_t)d] = lo + (d + 1) * step;
+        }
+        r->h_hinges.assign(hg.begin(), hg.end());
+        r->bandwidth = bandwidth;
+        std::vector<float> W((size_t)degree * n);
+        for (int j = 0; j < n; ++j) {
+            double tot = 0.0, col[REG_MAXDEG];
+            for (int d = 0; d < degree; ++d) {
+                const double u = ((double)(float)mean[(size_t)j] - hg[(size_t)d]) / bandwidth;
+                col[d] = std::min(std::max(std::exp(-u * u), 1e-10), 1.0);
+                tot += col[d];
+            }
+            for (int d = 0; d < degree; ++d) W[(size_t)d * n + j] = (float)(col[d] / tot);
+        }
+        POLEE_TRY(r->main.init(ctx, v, 0, 0, p));
+        POLEE_TRY(r->d_W.upload(ctx, W));
+        POLEE_TRY(r->d_design.upload(ctx, design, (size_t)S * F));
+        POLEE_TRY(r->d_ss.upload(ctx, sample_scales, (size_t)S));
+        for (DevBuf<float> *b : {&r->d_x, &r->d_glik}) POLEE_TRY(b->alloc(ctx, sn));
+        for (DevBuf<float> *b : {&r->d_lp, &r->d_lse, &r->d_lse_acc}) POLEE_TRY(b->alloc(ctx, (size_t)S));
+        POLEE_TRY(r->d_lr.alloc(ctx, 1));
+        POLEE_TRY(r->d_tick.alloc(ctx, 2));
+        POLEE_TRY(r->d_seed.alloc(ctx, 1));
+        for (DevBuf<float> *b : {&r->d_glik, &r->d_lse, &r->d_lse_acc}) POLEE_TRY(reg_zero(ctx, *b));
+        POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *out = handle.release();
+        return POLEE_OK;
+    });
 }
 
 void polee_regression_destroy(polee_regression *r)
@@ -1230,229 +1162,169 @@ void polee_regression_destroy(polee_regression *r)
     ctx_release(ctx);
 }
 
-int64_t polee_regression_num_params(const polee_regression *r) { return r ? r->v.num_params() : 0; }
-int64_t polee_regression_num_noise(const polee_regression *r) { return r ? r->v.num_noise() + r->num_iso_noise() : 0; }
-int64_t polee_regression_num_isoform_params(const polee_regression *r) { return r ? r->num_iso_params() : 0; }
-int64_t polee_debug_regression_num_stats(const polee_regression *r) { return r ? r->num_stats() : 0; }
+int64_t polee_regression_num_params(const polee_regression *r) { return r ? r->main.num_params() : 0; }
+int64_t polee_regression_num_noise(const polee_regression *r) { return r ? r->main.num_noise() + r->iso.num_noise() : 0; }
+int64_t polee_regression_num_isoform_params(const polee_regression *r) { return r ? r->iso.num_params() : 0; }
+int64_t polee_debug_regression_num_stats(const polee_regression *r) { return r ? r->main.num_stats() : 0; }
 
 polee_status polee_regression_get_params(polee_regression *r, float *params)
 {
-    if (!r || !params) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    POLEE_TRY(use_device(r->ctx));
-    return r->d_p.download(r->ctx, params, (size_t)r->v.num_params());
+    return reg_entry(r, params, "polee_regression_get_params",
+                     [&] { return r->main.p.download(r->ctx, params, (size_t)r->main.num_params()); });
 }
 
 polee_status polee_regression_set_params(polee_regression *r, const float *params)
 {
-    if (!r || !params) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    POLEE_TRY(use_device(r->ctx));
-    r->lse_valid = false;
-    return r->d_p.upload(r->ctx, params, (size_t)r->v.num_params());
+    return reg_entry(r, params, "polee_regression_set_params", [&] {
+        r->lse_valid = false;
+        return r->main.p.upload(r->ctx, params, (size_t)r->main.num_params());
+    });
 }
 
 polee_status polee_regression_weights(polee_regression *r, float *weights)
 {
-    if (!r || !weights) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    POLEE_TRY(use_device(r->ctx));
-    return r->d_W.download(r->ctx, weights, (size_t)r->v.deg * r->v.n);
+    return reg_entry(r, weights, "polee_regression_weights",
+                     [&] { return r->d_W.download(r->ctx, weights, (size_t)r->main.v.deg * r->main.v.n); });
 }
 
 polee_status polee_regression_set_normal_likelihood(polee_regression *r, const float *loc, const float *scale)
 {
-    if (!r || !loc || !scale) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (r->v.point) return fail(ctx, POLEE_ERR_BAD_ARG, "a model with point estimates has no likelihood term");
-    const size_t sn = (size_t)r->v.S * r->v.n;
-    for (size_t i = 0; i < sn; ++i)
-        if (!(scale[i] > 0.0f)) return fail(ctx, POLEE_ERR_BAD_ARG, "scale[%zu] = %g is not positive", i, (double)scale[i]);
-    r->drop_graph();
-    POLEE_TRY(r->d_lik_loc.upload(ctx, loc, sn));
-    return r->d_lik_scale.upload(ctx, scale, sn);
+    return reg_entry(r, loc && scale, "polee_regression_set_normal_likelihood", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        if (r->main.v.point) return fail(ctx, POLEE_ERR_BAD_ARG, "a model with point estimates has no likelihood term");
+        const size_t sn = (size_t)r->main.v.S * r->main.v.n;
+        for (size_t i = 0; i < sn; ++i)
+            if (!(scale[i] > 0.0f)) return fail(ctx, POLEE_ERR_BAD_ARG, "scale[%zu] = %g is not positive", i, (double)scale[i]);
+        r->drop_graph();
+        POLEE_TRY(r->d_lik_loc.upload(ctx, loc, sn));
+        return r->d_lik_scale.upload(ctx, scale, sn);
+    });
 }
 
 polee_status polee_regression_set_gene_likelihood(polee_regression *r, polee_approx *ap, const int32_t *gene_of,
                                                   const float *x_isoform_init)
 {
-    if (!r || !ap || !gene_of || !x_isoform_init) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    POLEE_TRY(use_device(ctx));
-    int32_t aS, nt;
-    approx_dims(ap, &aS, &nt);
-    if (approx_ctx(ap) != ctx || aS != r->v.S)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "the approximation handle holds %d samples, the model %d", aS, r->v.S);
-    if (r->v.point) return fail(ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is built without point estimates only");
-    if (r->latent) return fail(ctx, POLEE_ERR_UNSUPPORTED, "a latent design belongs to the transcript-level model only");
-    if (r->comm && r->comm->nranks > 1)
-        return fail(ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is not sharded over ranks");
-    POLEE_TRY(approx_set_genes(ap, gene_of, r->v.n));  // the model's features are the genes
-    const int S = r->v.S;
-    const size_t snt = (size_t)S * nt;
-    std::vector<float> ip(2 * (size_t)nt + 2 * snt);
-    for (int i = 0; i < nt; ++i) {  // models/polee_regression.py:573-577
-        double m = 0.0;
-        for (int s = 0; s < S; ++s) m += x_isoform_init[(size_t)s * nt + i];
-        ip[(size_t)i] = (float)(m / S);
-        ip[(size_t)nt + i] = -2.0f;
-    }
-    std::copy_n(x_isoform_init, snt, ip.begin() + 2 * (size_t)nt);
-    std::fill_n(ip.begin() + 2 * (size_t)nt + snt, snt, -2.0f);
-    r->drop_graph();
-    r->gene_ap = ap;
-    r->nt = nt;
-    r->ap = nullptr;
-    const size_t np = ip.size();
-    POLEE_TRY(r->d_ip.upload(ctx, ip));
-    POLEE_TRY(r->d_ig.alloc(ctx, np));
-    POLEE_TRY(r->d_im.alloc(ctx, np));
-    POLEE_TRY(r->d_iv.alloc(ctx, np));
-    POLEE_TRY(r->d_ieps.alloc(ctx, (size_t)nt + snt));
-    POLEE_TRY(r->d_xi.alloc(ctx, snt));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_im.p, 0, sizeof(float) * np, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_iv.p, 0, sizeof(float) * np, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return POLEE_OK;
+    return reg_entry(r, ap && gene_of && x_isoform_init, "polee_regression_set_gene_likelihood", [&]() -> polee_status {
+        int32_t nt;
+        POLEE_TRY(gene_likelihood_check(r, ap, &nt));
+        const int S = r->main.v.S;
+        const size_t snt = (size_t)S * nt;
+        // the block is all tail: mean loc / s [nt], x_isoform loc / s [S][nt]; every s = -2 (models/polee_regression.py:573-577)
+        std::vector<float> ip(2 * (size_t)nt + 2 * snt, -2.0f);
+        const std::vector<double> mean = column_means(x_isoform_init, S, nt);
+        for (int i = 0; i < nt; ++i) ip[(size_t)i] = (float)mean[(size_t)i];
+        std::copy_n(x_isoform_init, snt, ip.begin() + 2 * (size_t)nt);
+        RegBlock blk;
+        DevBuf<float> xi;
+        POLEE_TRY(blk.init(r->ctx, RegView{}, (int64_t)ip.size(), (int64_t)(nt + snt), ip));
+        POLEE_TRY(gene_likelihood_prepare(r, ap, gene_of, nt, xi));
+        gene_likelihood_attach(r, ap, nt, IsoKind::gene, blk, xi);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_regression_set_gene_isoform_likelihood(polee_regression *r, polee_approx *ap, const int32_t *gene_of,
                                                           const float *x_isoform_init, const float *design_isoform,
                                                           int32_t num_isoform_factors)
 {
-    if (!r || !design_isoform) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    if (num_isoform_factors < 1 || num_isoform_factors > REG_MAXF)
-        return fail(ctx, POLEE_ERR_UNSUPPORTED, "1..%d isoform factors (got %d)", REG_MAXF, num_isoform_factors);
-    POLEE_TRY(polee_regression_set_gene_likelihood(r, ap, gene_of, x_isoform_init));
-    const int S = r->v.S, nt = r->nt, Fi = num_isoform_factors;
-    RegView &vi = r->vi;
-    vi = RegView{S, Fi, nt, 0, 0, 0, 0.0f, 2.0f, 1.0f};
-    vi.fixed_ab = 0.001f;
-    const int64_t P = vi.num_params(), Fn = vi.Fn(), snt = (int64_t)S * nt;
-    // initial values (models/polee_regression.py:740-775)
-    std::vector<float> p((size_t)P, 0.0f);
-    p[1] = p[3] = -1.0f;
-    for (int a = 1; a < 10; a += 2) std::fill_n(p.begin() + vi.o_cols() + a * Fn, Fn, -1.0f);
-    for (int i = 0; i < nt; ++i) {
-        double m = 0.0;
-        for (int s = 0; s < S; ++s) m += x_isoform_init[(size_t)s * nt + i];
-        p[(size_t)(vi.o_bias_loc() + i)] = (float)(m / S);
-        p[(size_t)(vi.o_bias_s() + i)] = -1.0f;
-        p[(size_t)(vi.o_xs_loc() + i)] = 1.0f;
-        p[(size_t)(vi.o_xs_s() + i)] = -1.0f;
-    }
-    std::copy_n(x_isoform_init, snt, p.begin() + vi.o_qx_loc());
-    std::fill_n(p.begin() + vi.o_qx_s(), snt, -2.0f);
-    r->iso_reg = true;
-    POLEE_TRY(r->d_ip.upload(ctx, p));
-    POLEE_TRY(r->d_idesign.upload(ctx, design_isoform, (size_t)S * Fi));
-    POLEE_TRY(r->d_ig.alloc(ctx, (size_t)P));
-    POLEE_TRY(r->d_im.alloc(ctx, (size_t)P));
-    POLEE_TRY(r->d_iv.alloc(ctx, (size_t)P));
-    POLEE_TRY(r->d_ieps.alloc(ctx, (size_t)vi.num_noise()));
-    POLEE_TRY(r->d_istats.alloc(ctx, (size_t)r->num_iso_stats()));
-    POLEE_TRY(r->d_ismall.alloc(ctx, (size_t)REG_SLOTS * vi.num_red()));
-    POLEE_TRY(r->d_iacc.alloc(ctx, REG_SLOTS));
-    POLEE_TRY(r->d_iloss.alloc(ctx, 1));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_im.p, 0, sizeof(float) * P, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_iv.p, 0, sizeof(float) * P, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_istats.p, 0, sizeof(float) * r->num_iso_stats(), ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_ismall.p, 0, sizeof(float) * REG_SLOTS * vi.num_red(), ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_iacc.p, 0, sizeof(double) * REG_SLOTS, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return POLEE_OK;
+    return reg_entry(r, ap && gene_of && x_isoform_init && design_isoform, "polee_regression_set_gene_isoform_likelihood", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        const int S = r->main.v.S, Fi = num_isoform_factors;
+        int32_t nt;
+        if (Fi < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "at least one isoform factor (got %d)", Fi);
+        if (Fi > REG_MAXF) return fail(ctx, POLEE_ERR_UNSUPPORTED, "1..%d isoform factors (got %d)", REG_MAXF, Fi);
+        POLEE_TRY(gene_likelihood_check(r, ap, &nt));
+        // the isoform regression: Fi factors over nt columns, no hinges, bias ~ Normal(0, 2), x_scale ~ InverseGamma(0.001, 0.001);
+        // initial values (models/polee_regression.py:740-775)
+        RegView vi{S, Fi, nt, 0, 0, 0, 0.0f, 2.0f, 1.0f};
+        vi.fixed_ab = 0.001f;
+        const size_t snt = (size_t)S * nt;
+        std::vector<float> p((size_t)vi.num_params(), 0.0f);
+        init_view_params(vi, p, -1.0f, column_means(x_isoform_init, S, nt).data(), 1.0f);
+        std::copy_n(x_isoform_init, snt, p.begin() + vi.o_qx_loc());
+        std::fill_n(p.begin() + vi.o_qx_s(), snt, -2.0f);
+        RegBlock blk;
+        DevBuf<float> idesign, xi;
+        POLEE_TRY(blk.init(ctx, vi, 0, 0, p));
+        POLEE_TRY(idesign.upload(ctx, design_isoform, (size_t)S * Fi));
+        POLEE_TRY(gene_likelihood_prepare(r, ap, gene_of, nt, xi));
+        gene_likelihood_attach(r, ap, nt, IsoKind::gene_isoform, blk, xi);
+        r->d_idesign.take(idesign);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_regression_set_joint_likelihood(polee_regression *r, polee_approx *ap, const int32_t *gene_of,
                                                    const float *x_isoform_init, int32_t num_splice_features,
                                                    const int32_t *pair_transcript, const int32_t *pair_feature, int64_t num_pairs)
 {
-    if (!r || !pair_transcript || !pair_feature) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    if (num_splice_features < 1 || num_pairs < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad splice-feature matrix");
-    if (r->v.use_distortion) return fail(ctx, POLEE_ERR_BAD_ARG, "the joint model has no distortion term: create the gene block with use_distortion = 0");
-    POLEE_TRY(polee_regression_set_gene_likelihood(r, ap, gene_of, x_isoform_init));  // (gene_ap, nt, d_xi; its isoform block is replaced below)
-    const int S = r->v.S, nt = r->nt, P = num_splice_features, F = r->v.F;
-    for (int64_t q = 0; q < num_pairs; ++q)
-        if (pair_transcript[q] < 0 || pair_transcript[q] >= nt || pair_feature[q] < 0 || pair_feature[q] >= P)
-            return fail(ctx, POLEE_ERR_BAD_ARG, "splice-feature pair %lld out of range", (long long)q);
-    // the feature matrix both ways (CSR by transcript, CSR by feature)
-    std::vector<int32_t> tptr((size_t)nt + 1, 0), tfeat((size_t)num_pairs), pptr((size_t)P + 1, 0), ptrans((size_t)num_pairs);
-    for (int64_t q = 0; q < num_pairs; ++q) {
-        ++tptr[(size_t)pair_transcript[q] + 1];
-        ++pptr[(size_t)pair_feature[q] + 1];
-    }
-    for (int i = 0; i < nt; ++i) tptr[(size_t)i + 1] += tptr[(size_t)i];
-    for (int i = 0; i < P; ++i) pptr[(size_t)i + 1] += pptr[(size_t)i];
-    {
-        std::vector<int32_t> ct(tptr.begin(), tptr.end() - 1), cp(pptr.begin(), pptr.end() - 1);
+    return reg_entry(r, ap && gene_of && x_isoform_init && pair_transcript && pair_feature, "polee_regression_set_joint_likelihood", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        RegView &v = r->main.v;
+        const int S = v.S, P = num_splice_features;
+        int32_t nt;
+        if (P < 1 || num_pairs < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad splice-feature matrix");
+        if (v.use_distortion)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "the joint model has no distortion term: create the gene block with use_distortion = 0");
+        POLEE_TRY(gene_likelihood_check(r, ap, &nt));
+        for (int64_t q = 0; q < num_pairs; ++q)
+            if (pair_transcript[q] < 0 || pair_transcript[q] >= nt || pair_feature[q] < 0 || pair_feature[q] >= P)
+                return fail(ctx, POLEE_ERR_BAD_ARG, "splice-feature pair %lld out of range", (long long)q);
+        // the feature matrix both ways (CSR by transcript, CSR by feature); without pairs the index arrays still have to exist
+        const size_t np = (size_t)std::max<int64_t>(num_pairs, 1);
+        std::vector<int32_t> tptr((size_t)nt + 1, 0), tfeat(np, 0), pptr((size_t)P + 1, 0), ptrans(np, 0);
         for (int64_t q = 0; q < num_pairs; ++q) {
-            tfeat[(size_t)ct[(size_t)pair_transcript[q]]++] = pair_feature[q];
-            ptrans[(size_t)cp[(size_t)pair_feature[q]]++] = pair_transcript[q];
+            ++tptr[(size_t)pair_transcript[q] + 1];
+            ++pptr[(size_t)pair_feature[q] + 1];
         }
-    }
-    // the gene block becomes the joint model's: a horseshoe (one local level), weights from the sampled bias, HalfCauchy(0, 10)
-    // on the mean-variance coefficients, qw_gene_softplus_scale = -2 (:1009-1041, :936-937), Adam(1e-3) (:1215)
-    RegView &v = r->v;
-    v.levels = 1;
-    v.w_from_bias = 1;
-    v.hc_scale = 10.0f;
-    v.bandwidth = r->bandwidth;
-    POLEE_TRY(r->d_hinges.upload(ctx, r->h_hinges));
-    v.hinges = r->d_hinges.p;
-    r->lr = 1e-3f;
-    {
-        std::vector<float> qs((size_t)v.Fn(), -2.0f);
-        POLEE_HIP_TRY(ctx, hipMemcpy(r->d_p.p + v.o_cols() + 9 * v.Fn(), qs.data(), sizeof(float) * qs.size(), hipMemcpyHostToDevice));
-    }
-    // the splice block: P columns, horseshoe, bias ~ Normal(0, 10), no x_scale of its own (:1062-1087, surrogates :1172-1203)
-    RegView &vs = r->vi;
-    vs = RegView{0, F, P, 0, 0, 0, 0.0f, 10.0f, 1.0f};
-    vs.levels = 1;
-    vs.no_xs = 1;
-    const int64_t PS = vs.num_params(), Fp = vs.Fn(), snt = (int64_t)S * nt, PJ = PS + 2 * (int64_t)nt + 2 * snt;
-    std::vector<float> p((size_t)PJ, 0.0f);
-    p[1] = p[3] = -1.0f;
-    for (int a = 1; a < 8; a += 2) std::fill_n(p.begin() + vs.o_cols() + a * Fp, Fp, -1.0f);
-    std::fill_n(p.begin() + vs.o_cols() + 9 * Fp, Fp, -2.0f);           // qw_splice_softplus_scale
-    for (int i = 0; i < P; ++i) p[(size_t)(vs.o_bias_s() + i)] = -1.0f;  // qx_splice_bias: loc 0, softplus scale -1
-    for (int i = 0; i < nt; ++i) {
-        p[(size_t)(PS + i)] = 3.0f;        // qx_iso_scale_loc (:1004-1005)
-        p[(size_t)(PS + nt + i)] = -1.0f;  // qx_iso_scale_softplus_scale
-    }
-    std::copy_n(x_isoform_init, snt, p.begin() + PS + 2 * (int64_t)nt);
-    std::fill_n(p.begin() + PS + 2 * (int64_t)nt + snt, snt, -3.0f);  // qx_iso_softplus_scale (:1009-1010)
-    r->joint = true;
-    r->iso_reg = false;
-    r->P = P;
-    r->drop_graph();
-    POLEE_TRY(r->d_ip.upload(ctx, p));
-    POLEE_TRY(r->d_ig.alloc(ctx, (size_t)PJ));
-    POLEE_TRY(r->d_im.alloc(ctx, (size_t)PJ));
-    POLEE_TRY(r->d_iv.alloc(ctx, (size_t)PJ));
-    POLEE_TRY(r->d_ieps.alloc(ctx, (size_t)r->num_iso_noise()));
-    POLEE_TRY(r->d_istats.alloc(ctx, (size_t)r->num_iso_stats()));
-    POLEE_TRY(r->d_ismall.alloc(ctx, (size_t)REG_SLOTS * vs.num_red()));
-    POLEE_TRY(r->d_iacc.alloc(ctx, REG_SLOTS));
-    POLEE_TRY(r->d_iloss.alloc(ctx, 1));
-    POLEE_TRY(r->d_mu.alloc(ctx, (size_t)S * P));
-    POLEE_TRY(r->d_resid.alloc(ctx, (size_t)snt));
-    POLEE_TRY(r->d_tptr.upload(ctx, tptr));
-    POLEE_TRY(r->d_pptr.upload(ctx, pptr));
-    if (num_pairs > 0) {
-        POLEE_TRY(r->d_tfeat.upload(ctx, tfeat));
-        POLEE_TRY(r->d_ptrans.upload(ctx, ptrans));
-    } else {
-        POLEE_TRY(r->d_tfeat.alloc(ctx, 1));
-        POLEE_TRY(r->d_ptrans.alloc(ctx, 1));
-    }
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_ig.p, 0, sizeof(float) * PJ, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_im.p, 0, sizeof(float) * PJ, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_iv.p, 0, sizeof(float) * PJ, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_istats.p, 0, sizeof(float) * r->num_iso_stats(), ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_ismall.p, 0, sizeof(float) * REG_SLOTS * vs.num_red(), ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_iacc.p, 0, sizeof(double) * REG_SLOTS, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return POLEE_OK;
+        for (int i = 0; i < nt; ++i) tptr[(size_t)i + 1] += tptr[(size_t)i];
+        for (int i = 0; i < P; ++i) pptr[(size_t)i + 1] += pptr[(size_t)i];
+        {
+            std::vector<int32_t> ct(tptr.begin(), tptr.end() - 1), cp(pptr.begin(), pptr.end() - 1);
+            for (int64_t q = 0; q < num_pairs; ++q) {
+                tfeat[(size_t)ct[(size_t)pair_transcript[q]]++] = pair_feature[q];
+                ptrans[(size_t)cp[(size_t)pair_feature[q]]++] = pair_transcript[q];
+            }
+        }
+        // the splice block: P columns, horseshoe, bias ~ Normal(0, 10), no x_scale of its own, qw_splice_softplus_scale = -2 (:1062-1087,
+        // surrogates :1172-1203); its tail, the transcripts: qx_iso_scale loc 3 / s -1 (:1004-1005), qx_iso loc / s -3 (:1009-1010)
+        RegView vs{0, v.F, P, 0, 0, 0, 0.0f, 10.0f, 1.0f};
+        vs.levels = 1;
+        vs.no_xs = 1;
+        const int64_t PS = vs.num_params(), snt = (int64_t)S * nt, tail = 2 * (int64_t)nt + 2 * snt;
+        std::vector<float> p((size_t)(PS + tail), 0.0f);
+        init_view_params(vs, p, -2.0f, nullptr, 0.0f);
+        std::fill_n(p.begin() + PS, nt, 3.0f);
+        std::fill_n(p.begin() + PS + nt, nt, -1.0f);
+        std::copy_n(x_isoform_init, snt, p.begin() + PS + 2 * (int64_t)nt);
+        std::fill_n(p.begin() + PS + 2 * (int64_t)nt + snt, snt, -3.0f);
+        RegBlock blk;
+        DevBuf<int32_t> d_tptr, d_tfeat, d_pptr, d_ptrans;
+        DevBuf<float> d_mu, d_resid, d_hinges, xi;
+        POLEE_TRY(blk.init(ctx, vs, tail, nt + snt, p));
+        POLEE_TRY(d_mu.alloc(ctx, (size_t)S * P));
+        POLEE_TRY(d_resid.alloc(ctx, (size_t)snt));
+        POLEE_TRY(d_tptr.upload(ctx, tptr));
+        POLEE_TRY(d_pptr.upload(ctx, pptr));
+        POLEE_TRY(d_tfeat.upload(ctx, tfeat));
+        POLEE_TRY(d_ptrans.upload(ctx, ptrans));
+        POLEE_TRY(d_hinges.upload(ctx, r->h_hinges));
+        POLEE_TRY(gene_likelihood_prepare(r, ap, gene_of, nt, xi));
+        // the gene block becomes the joint model's: a horseshoe (one local level), weights from the sampled bias, HalfCauchy(0, 10)
+        // on the mean-variance coefficients, qw_gene_softplus_scale = -2 (:1009-1041, :936-937), Adam(1e-3) (:1215)
+        const std::vector<float> qs((size_t)v.Fn(), -2.0f);
+        POLEE_HIP_TRY(ctx, hipMemcpy(r->main.p.p + v.o_cols() + 9 * v.Fn(), qs.data(), sizeof(float) * qs.size(), hipMemcpyHostToDevice));
+        gene_likelihood_attach(r, ap, nt, IsoKind::joint, blk, xi);
+        r->d_mu.take(d_mu), r->d_resid.take(d_resid), r->d_hinges.take(d_hinges);
+        r->d_tptr.take(d_tptr), r->d_tfeat.take(d_tfeat), r->d_pptr.take(d_pptr), r->d_ptrans.take(d_ptrans);
+        v.levels = 1;
+        v.w_from_bias = 1;
+        v.hc_scale = 10.0f;
+        v.bandwidth = r->bandwidth;
+        v.hinges = r->d_hinges.p;
+        r->lr = 1e-3f;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_regression_set_learning_rate(polee_regression *r, float lr)
@@ -1465,24 +1337,24 @@ polee_status polee_regression_set_learning_rate(polee_regression *r, float lr)
 
 polee_status polee_regression_get_isoform_params(polee_regression *r, float *params)
 {
-    if (!r || !params || !r->gene_ap) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "no isoform block");
-    POLEE_TRY(use_device(r->ctx));
-    return r->d_ip.download(r->ctx, params, (size_t)r->num_iso_params());
+    return reg_entry(r, params, "polee_regression_get_isoform_params", [&] {
+        return r->gene_ap ? r->iso.p.download(r->ctx, params, (size_t)r->iso.num_params()) : fail(r->ctx, POLEE_ERR_BAD_ARG, "no isoform block");
+    });
 }
 
 polee_status polee_regression_set_isoform_params(polee_regression *r, const float *params)
 {
-    if (!r || !params || !r->gene_ap) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "no isoform block");
-    POLEE_TRY(use_device(r->ctx));
-    return r->d_ip.upload(r->ctx, params, (size_t)r->num_iso_params());
+    return reg_entry(r, params, "polee_regression_set_isoform_params", [&] {
+        return r->gene_ap ? r->iso.p.upload(r->ctx, params, (size_t)r->iso.num_params()) : fail(r->ctx, POLEE_ERR_BAD_ARG, "no isoform block");
+    });
 }
 
 // gradient of the isoform block left by the last polee_regression_eval
 polee_status polee_regression_get_isoform_grad(polee_regression *r, float *grad)
 {
-    if (!r || !grad || !r->gene_ap) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "no isoform block");
-    POLEE_TRY(use_device(r->ctx));
-    return r->d_ig.download(r->ctx, grad, (size_t)r->num_iso_params());
+    return reg_entry(r, grad, "polee_regression_get_isoform_grad", [&] {
+        return r->gene_ap ? r->iso.g.download(r->ctx, grad, (size_t)r->iso.num_params()) : fail(r->ctx, POLEE_ERR_BAD_ARG, "no isoform block");
+    });
 }
 
 polee_status polee_regression_set_comm(polee_regression *r, polee_comm *comm)
@@ -1504,85 +1376,84 @@ polee_status polee_regression_set_comm(polee_regression *r, polee_comm *comm)
 // test hooks (include/polee_hip_debug.h): the two halves of a step, with the exchange left to the caller
 polee_status polee_debug_regression_data_pass(polee_regression *r, const float *noise, float *stats)
 {
-    if (!r || !noise || !stats) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    POLEE_TRY(use_device(r->ctx));
-    POLEE_TRY(reg_fill_noise(r, noise, 0, 0, false));
-    POLEE_HIP_TRY(r->ctx, hipMemsetAsync(r->d_stats.p + r->num_stats() - REG_SLOTS, 0, sizeof(float) * REG_SLOTS,
-                                         r->ctx->stream));
-    POLEE_TRY(reg_data_pass(r));
-    POLEE_TRY(r->d_stats.download(r->ctx, stats, (size_t)r->num_stats()));
-    // no finish kernel follows a bare data pass: leave the loss slots clean for the next step
-    POLEE_HIP_TRY(r->ctx, hipMemsetAsync(r->d_stats.p + r->num_stats() - REG_SLOTS, 0, sizeof(float) * REG_SLOTS,
-                                         r->ctx->stream));
-    return POLEE_OK;
+    return reg_entry(r, noise && stats, "polee_debug_regression_data_pass", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        const RegBlock &mb = r->main;
+        POLEE_TRY(reg_fill_noise(r, noise, 0, 0, false));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(mb.loss_slots(), 0, sizeof(float) * REG_SLOTS, ctx->stream));
+        POLEE_TRY(reg_data_pass(r, RegStep{}));
+        POLEE_TRY(mb.stats.download(ctx, stats, (size_t)mb.num_stats()));
+        // no finish kernel follows a bare data pass: leave the loss slots clean for the next step
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(mb.loss_slots(), 0, sizeof(float) * REG_SLOTS, ctx->stream));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_debug_regression_prior_pass(polee_regression *r, const float *stats, float *loss, float *grad)
 {
-    if (!r || !stats || !loss) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    POLEE_TRY(use_device(r->ctx));
-    POLEE_TRY(r->d_stats.upload(r->ctx, stats, (size_t)r->num_stats()));
-    POLEE_TRY(reg_prior_pass(r));
-    POLEE_TRY(r->d_loss.download(r->ctx, loss, 1));
-    if (grad) POLEE_TRY(r->d_g.download(r->ctx, grad, (size_t)r->v.num_params()));
-    return POLEE_OK;
+    return reg_entry(r, stats && loss, "polee_debug_regression_prior_pass", [&]() -> polee_status {
+        POLEE_TRY(r->main.stats.upload(r->ctx, stats, (size_t)r->main.num_stats()));
+        POLEE_TRY(reg_prior_pass(r, RegStep{}));
+        POLEE_TRY(r->main.loss.download(r->ctx, loss, 1));
+        if (grad) POLEE_TRY(r->main.g.download(r->ctx, grad, (size_t)r->main.num_params()));
+        return POLEE_OK;
+    });
 }
 
 // ---- classify (models/polee_regression.py:342-413) ---------------------------------------------------------------------------------
 polee_status polee_regression_set_design(polee_regression *r, const float *design)
 {
-    if (!r || !design) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (r->gene_ap || r->v.fixed_ab > 0.0f || (r->comm && r->comm->nranks > 1))
-        return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_regression_set_design: the transcript-level model on one GPU only");
-    if (!r->want_dgrad) {
-        POLEE_TRY(r->d_dF.alloc(ctx, (size_t)REG_SLOTS * r->v.S * r->v.F));
-        r->want_dgrad = true;
-        r->drop_graph();  // (the captured step gains a kernel)
-    }
-    return r->d_design.upload(ctx, design, (size_t)r->v.S * r->v.F);  // (same buffer: a captured step reads the new values)
+    return reg_entry(r, design, "polee_regression_set_design", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        const RegView &v = r->main.v;
+        if (r->gene_ap || v.fixed_ab > 0.0f || (r->comm && r->comm->nranks > 1))
+            return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_regression_set_design: the transcript-level model on one GPU only");
+        if (!r->want_dgrad) {
+            POLEE_TRY(r->d_dF.alloc(ctx, (size_t)REG_SLOTS * v.S * v.F));
+            r->want_dgrad = true;
+            r->drop_graph();  // (the captured step gains a kernel)
+        }
+        return r->d_design.upload(ctx, design, (size_t)v.S * v.F);  // (same buffer: a captured step reads the new values)
+    });
 }
 
 // ---- latent design (RNASeqPCA, models/polee_pca.py:14-92) --------------------------------------------------------------------------
 polee_status polee_regression_set_latent_design(polee_regression *r, const float *z0, float prior_scale)
 {
-    if (!r || !z0) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (r->gene_ap || r->v.fixed_ab > 0.0f || (r->comm && r->comm->nranks > 1))
-        return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_regression_set_latent_design: the transcript-level model on one GPU only");
-    if (!(prior_scale > 0.0f) || !std::isfinite(prior_scale))
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_latent_design: prior_scale = %g is not a positive finite number",
-                    (double)prior_scale);
-    const size_t SF = (size_t)r->v.S * r->v.F;
-    r->drop_graph();  // (the captured step loses a memset and gains the update)
-    POLEE_TRY(r->d_dF.alloc(ctx, (size_t)REG_SLOTS * SF));
-    POLEE_TRY(r->d_zm.alloc(ctx, SF));
-    POLEE_TRY(r->d_zv.alloc(ctx, SF));
-    POLEE_TRY(r->d_gz.alloc(ctx, SF));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_dF.p, 0, sizeof(float) * REG_SLOTS * SF, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_zm.p, 0, sizeof(float) * SF, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_zv.p, 0, sizeof(float) * SF, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(r->d_gz.p, 0, sizeof(float) * SF, ctx->stream));
-    POLEE_TRY(r->d_design.upload(ctx, z0, SF));
-    r->want_dgrad = true;
-    r->latent = true;
-    r->prior_scale = prior_scale;
-    return POLEE_OK;
+    return reg_entry(r, z0, "polee_regression_set_latent_design", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        const RegView &v = r->main.v;
+        if (r->gene_ap || v.fixed_ab > 0.0f || (r->comm && r->comm->nranks > 1))
+            return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_regression_set_latent_design: the transcript-level model on one GPU only");
+        if (!(prior_scale > 0.0f) || !std::isfinite(prior_scale))
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_latent_design: prior_scale = %g is not a positive finite number",
+                        (double)prior_scale);
+        const size_t SF = (size_t)v.S * v.F;
+        r->drop_graph();  // (the captured step loses a memset and gains the update)
+        POLEE_TRY(r->d_dF.alloc(ctx, (size_t)REG_SLOTS * SF));
+        for (DevBuf<float> *b : {&r->d_zm, &r->d_zv, &r->d_gz}) POLEE_TRY(b->alloc(ctx, SF));
+        for (DevBuf<float> *b : {&r->d_dF, &r->d_zm, &r->d_zv, &r->d_gz}) POLEE_TRY(reg_zero(ctx, *b));
+        POLEE_TRY(r->d_design.upload(ctx, z0, SF));
+        r->want_dgrad = true;
+        r->latent = true;
+        r->prior_scale = prior_scale;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_regression_get_design(polee_regression *r, float *design)
 {
-    if (!r || !design) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_regression_get_design: null argument");
-    POLEE_TRY(use_device(r->ctx));
-    return r->d_design.download(r->ctx, design, (size_t)r->v.S * r->v.F);
+    return reg_entry(r, design, "polee_regression_get_design",
+                     [&] { return r->d_design.download(r->ctx, design, (size_t)r->main.v.S * r->main.v.F); });
 }
 
 polee_status polee_regression_set_trainable(polee_regression *r, int64_t begin, int64_t end)
 {
     if (!r) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    if (begin < 0 || end < begin || end > r->v.num_params()) return fail(r->ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_trainable: [%lld, %lld) of %lld parameters", (long long)begin, (long long)end, (long long)r->v.num_params());
+    const int64_t P = r->main.num_params();
+    if (begin < 0 || end < begin || end > P)
+        return fail(r->ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_trainable: [%lld, %lld) of %lld parameters", (long long)begin,
+                    (long long)end, (long long)P);
     r->train_lo = begin;
     r->train_hi = end;
     r->drop_graph();
@@ -1591,85 +1462,83 @@ polee_status polee_regression_set_trainable(polee_regression *r, int64_t begin, 
 
 polee_status polee_regression_design_grad(polee_regression *r, float *grad)
 {
-    if (!r || !grad) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!r->want_dgrad) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_design_grad: call polee_regression_set_design first");
-    const size_t SF = (size_t)r->v.S * r->v.F;
-    if (r->latent) return r->d_gz.download(ctx, grad, SF);  // (the total, prior term included: reg_latent_kernel)
-    std::vector<float> h(SF * REG_SLOTS);
-    POLEE_TRY(r->d_dF.download(ctx, h.data(), h.size()));
-    for (size_t i = 0; i < SF; ++i) {
-        double acc = 0.0;
-        for (int c = 0; c < REG_SLOTS; ++c) acc += (double)h[(size_t)c * SF + i];
-        grad[i] = (float)acc;
-    }
-    return POLEE_OK;
+    return reg_entry(r, grad, "polee_regression_design_grad", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        if (!r->want_dgrad) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_design_grad: call polee_regression_set_design first");
+        const size_t SF = (size_t)r->main.v.S * r->main.v.F;
+        if (r->latent) return r->d_gz.download(ctx, grad, SF);  // (the total, prior term included: reg_latent_kernel)
+        std::vector<float> h(SF * REG_SLOTS);
+        POLEE_TRY(r->d_dF.download(ctx, h.data(), h.size()));
+        for (size_t i = 0; i < SF; ++i) {
+            double acc = 0.0;
+            for (int c = 0; c < REG_SLOTS; ++c) acc += (double)h[(size_t)c * SF + i];
+            grad[i] = (float)acc;
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_regression_eval(polee_regression *r, const float *noise, uint64_t seed, float *loss, float *grad)
 {
-    if (!r || !loss) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = r->ctx;
-    POLEE_TRY(use_device(ctx));
-    POLEE_TRY(reg_fill_noise(r, noise, seed, (uint32_t)(r->step + 1), false));
-    POLEE_TRY(reg_eval_device(r));
-    POLEE_TRY(r->d_loss.download(ctx, loss, 1));
-    if (grad) POLEE_TRY(r->d_g.download(ctx, grad, (size_t)r->v.num_params()));
-    return POLEE_OK;
+    return reg_entry(r, loss, "polee_regression_eval", [&]() -> polee_status {
+        POLEE_TRY(reg_fill_noise(r, noise, seed, (uint32_t)(r->step + 1), false));
+        POLEE_TRY(reg_eval_device(r));
+        POLEE_TRY(r->main.loss.download(r->ctx, loss, 1));
+        if (grad) POLEE_TRY(r->main.g.download(r->ctx, grad, (size_t)r->main.num_params()));
+        return POLEE_OK;
+    });
 }
 
-polee_status polee_regression_fit(polee_regression *r, int32_t niter, uint64_t seed, const float *noise,
-                                  float *loss_trace)
+polee_status polee_regression_fit(polee_regression *r, int32_t niter, uint64_t seed, const float *noise, float *loss_trace)
 {
-    if (!r || niter < 0) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "bad argument");
-    polee_ctx *ctx = r->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (niter == 0) return POLEE_OK;
-    hipStream_t st = ctx->stream;
-    const int64_t ne = r->v.num_noise() + r->num_iso_noise();
-    if (r->d_trace.n < (size_t)niter) {  // (the trace's address is part of the captured step)
-        r->drop_graph();
-        POLEE_TRY(r->d_trace.alloc(ctx, std::max<size_t>((size_t)niter, 8192)));
-    }
-    const uint32_t clock[2] = {(uint32_t)r->step, 0u};
-    POLEE_TRY(r->d_tick.upload(ctx, clock, 2));
-    POLEE_TRY(r->d_seed.upload(ctx, &seed, 1));
-    // Steps with the device RNG are replayed from a hipGraph (about 25 launches per step otherwise bound the step on
-    // the host); supplied noise, a multi-rank communicator (RCCL inside a capture) or POLEE_REG_NO_GRAPH=1 enqueue
-    // directly.  The first step always runs directly: it computes the exact log-sum-exp the later ones start from.
-    const bool use_graph = !noise && !(r->comm && r->comm->nranks > 1) && !std::getenv("POLEE_REG_NO_GRAPH");
-    int32_t it = 0;
-    if (!use_graph || !r->lse_valid) {
-        POLEE_TRY(reg_enqueue_step(r, noise, true));
-        it = 1;
-    }
-    if (use_graph && it < niter && !r->graph) {
-        hipGraph_t g = nullptr;
-        POLEE_HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        const polee_status cs = reg_enqueue_step(r, nullptr, true);
-        const hipError_t ce = hipStreamEndCapture(st, &g);
-        if (cs != POLEE_OK || ce != hipSuccess) {
-            if (g) (void)hipGraphDestroy(g);
-            return cs != POLEE_OK ? cs : fail(ctx, POLEE_ERR_HIP, "graph capture failed: %s", hipGetErrorString(ce));
+    return reg_entry(r, niter >= 0, "polee_regression_fit", [&]() -> polee_status {
+        polee_ctx *ctx = r->ctx;
+        if (niter == 0) return POLEE_OK;
+        hipStream_t st = ctx->stream;
+        const int64_t ne = r->main.num_noise() + r->iso.num_noise();
+        if (r->d_trace.n < (size_t)niter) {  // (the trace's address is part of the captured step)
+            r->drop_graph();
+            POLEE_TRY(r->d_trace.alloc(ctx, std::max<size_t>((size_t)niter, 8192)));
         }
-        const hipError_t ie = hipGraphInstantiate(&r->graph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ie != hipSuccess) {
-            r->graph = nullptr;
-            return fail(ctx, POLEE_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+        const uint32_t clock[2] = {(uint32_t)r->step, 0u};
+        POLEE_TRY(r->d_tick.upload(ctx, clock, 2));
+        POLEE_TRY(r->d_seed.upload(ctx, &seed, 1));
+        // Steps with the device RNG are replayed from a hipGraph (about 25 launches per step otherwise bound the step on
+        // the host); supplied noise, a multi-rank communicator (RCCL inside a capture) or POLEE_REG_NO_GRAPH=1 enqueue
+        // directly.  The first step always runs directly: it computes the exact log-sum-exp the later ones start from.
+        const bool use_graph = !noise && !(r->comm && r->comm->nranks > 1) && !std::getenv("POLEE_REG_NO_GRAPH");
+        int32_t it = 0;
+        if (!use_graph || !r->lse_valid) {
+            POLEE_TRY(reg_enqueue_step(r, noise, true));
+            it = 1;
         }
-    }
-    for (; it < niter; ++it) {
-        if (use_graph)
-            POLEE_HIP_TRY(ctx, hipGraphLaunch(r->graph, st));
-        else
-            POLEE_TRY(reg_enqueue_step(r, noise ? noise + (size_t)it * ne : nullptr, true));
-    }
-    r->step += niter;
-    if (loss_trace) POLEE_TRY(r->d_trace.download(ctx, loss_trace, (size_t)niter));
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(st));
-    return POLEE_OK;
+        if (use_graph && it < niter && !r->graph) {
+            hipGraph_t g = nullptr;
+            POLEE_HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            const polee_status cs = reg_enqueue_step(r, nullptr, true);
+            const hipError_t ce = hipStreamEndCapture(st, &g);
+            if (cs != POLEE_OK || ce != hipSuccess) {
+                if (g) (void)hipGraphDestroy(g);
+                return cs != POLEE_OK ? cs : fail(ctx, POLEE_ERR_HIP, "graph capture failed: %s", hipGetErrorString(ce));
+            }
+            const hipError_t ie = hipGraphInstantiate(&r->graph, g, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(g);
+            if (ie != hipSuccess) {
+                r->graph = nullptr;
+                return fail(ctx, POLEE_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+            }
+        }
+        for (; it < niter; ++it) {
+            if (use_graph)
+                POLEE_HIP_TRY(ctx, hipGraphLaunch(r->graph, st));
+            else
+                POLEE_TRY(reg_enqueue_step(r, noise ? noise + (size_t)it * ne : nullptr, true));
+        }
+        r->step += niter;
+        if (loss_trace) POLEE_TRY(r->d_trace.download(ctx, loss_trace, (size_t)niter));
+        POLEE_HIP_TRY(ctx, hipStreamSynchronize(st));
+        return POLEE_OK;
+    });
 }
 
 }  // extern "C"

@@ -693,3 +693,115 @@ def test_joint_model_matches_restatement(P, ctx):
     assert len(out) == 5 and np.all(np.isfinite(out[-1])) and out[-1][-10:].mean() < out[-1][:10].mean()
     assert out[0].shape == (F, G) and out[1].shape == (F, G) and out[2].shape == (F, Pf) and out[3].shape == (F, Pf)
     assert not np.allclose(reg.get_isoform_params(), itheta)
+
+
+# ---- the step's plumbing: device RNG, graph replay, failed set-up calls --------------------------------------------
+def _fresh_model(P, ctx, kind):
+    """A fresh handle of one of the four models, at the shape of that model's *_matches_restatement test (the
+    transcript model: at the trajectory test's).  The same inputs on every call."""
+    if kind == "transcript":
+        rng = np.random.default_rng(32)
+        S, F, n, deg = 3, 2, 60, 4
+        vars_, design, x_init = _problem(rng, S, F, n)
+        return P.RNASeqTranscriptLinearRegression(vars_, x_init, design, np.zeros((S, 1), np.float32), True, 0.5, False,
+                                                  kernel_regression_degree=deg, ctx=ctx)
+    seed, S, F, nt, G, deg = {"gene": (38, 3, 2, 160, 45, 5), "gene_isoform": (41, 4, 2, 120, 30, 5),
+                              "joint": (53, 4, 2, 90, 25, 5)}[kind]
+    rng = np.random.default_rng(seed)
+    vars_, design, _ = _problem(rng, S, F, nt)
+    gene_of = np.concatenate([np.arange(G), rng.integers(0, G, nt - G)])
+    rng.shuffle(gene_of)
+    x_gene_init = (rng.normal(-np.log(G), 1.2, size=(1, G)) + rng.normal(0, 0.3, size=(S, G))).astype(np.float32)
+    x_iso_init = rng.normal(0, 1.0, size=(S, nt)).astype(np.float32)
+    ss = P.estimate_sample_scales(x_gene_init, upper_quantile=0.7)
+    if kind == "gene":
+        return P.RNASeqGeneLinearRegression(vars_, gene_of + 1, np.arange(1, nt + 1), x_gene_init, x_iso_init, None, design,
+                                            ss, True, 0.8, False, kernel_regression_degree=deg, ctx=ctx)
+    if kind == "gene_isoform":
+        design_iso = np.concatenate([np.ones((S, 1)), rng.normal(0, 1, size=(S, 2))], axis=1).astype(np.float32)
+        return P.RNASeqGeneIsoformLinearRegression(vars_, gene_of + 1, np.arange(1, nt + 1), x_gene_init, x_iso_init, None,
+                                                   design, design_iso, ss, True, 0.8, False,
+                                                   kernel_regression_degree=deg, ctx=ctx)
+    Pf = 30
+    pt = np.concatenate([np.arange(nt), rng.integers(0, nt, Pf)])  # every transcript in one feature, every feature used
+    pf = np.concatenate([rng.integers(0, Pf, nt), np.arange(Pf)])
+    return P.RNASeqJointLinearRegression(vars_, np.arange(1, nt + 1), gene_of + 1, G, pt + 1, pf + 1, Pf, None, x_gene_init,
+                                         x_iso_init, design, ss, False, kernel_regression_degree=deg, ctx=ctx)
+
+
+@pytest.mark.parametrize("kind", ["transcript", "gene", "gene_isoform", "joint"])
+def test_device_rng_first_fit_step_is_the_evaluation_of_the_same_seed(P, ctx, kind):
+    """The first step of fit() with the device RNG draws what an evaluation with the same seed draws: the fused draw
+    kernel against the two noise launches, the isoform noise's step (the clock is advanced later in the step), the
+    clock hand-over between the two calls.  rtol 2e-5: the trajectory test's tolerance for a step's loss."""
+    reg = _fresh_model(P, ctx, kind)
+    l0, _ = reg.loss_and_gradients(seed=977)
+    trace = reg.fit(1, seed=977, return_trace=True)[-1]
+    print(kind, "eval", l0, "fit", trace[0], "rel", abs(trace[0] - l0) / abs(l0))
+    assert np.isfinite(l0)
+    np.testing.assert_allclose(trace[0], l0, rtol=2e-5)
+
+
+@pytest.mark.parametrize("kind", ["transcript", "joint"])
+def test_graph_replay_matches_direct_enqueue(P, ctx, kind):
+    """Six steps of fit() replayed from the captured graph against six steps enqueued directly (POLEE_REG_NO_GRAPH=1):
+    the direct first step, the capture, replays on the multi-block log-sum-exp path.  The float atomics make bitwise
+    equality the wrong claim: the trajectory test's tolerances."""
+    import os
+    graph = _fresh_model(P, ctx, kind)
+    direct = _fresh_model(P, ctx, kind)
+    t_graph = graph.fit(6, seed=4411, return_trace=True)[-1]
+    saved = os.environ.get("POLEE_REG_NO_GRAPH")
+    os.environ["POLEE_REG_NO_GRAPH"] = "1"
+    try:
+        t_direct = direct.fit(6, seed=4411, return_trace=True)[-1]
+    finally:
+        if saved is None:
+            del os.environ["POLEE_REG_NO_GRAPH"]
+        else:
+            os.environ["POLEE_REG_NO_GRAPH"] = saved
+    print(kind, "graph", t_graph, "direct", t_direct)
+    assert np.all(np.isfinite(t_graph))
+    np.testing.assert_allclose(t_graph, t_direct, rtol=2e-5)
+    np.testing.assert_allclose(graph.get_flat_params(), direct.get_flat_params(), rtol=2e-4, atol=2e-5)
+
+
+def test_failed_likelihood_setup_leaves_the_handle_as_it_was(P, ctx):
+    """polee_regression_set_joint_likelihood with a splice pair out of range and polee_regression_set_gene_isoform_likelihood
+    without isoform factors fail with POLEE_ERR_BAD_ARG and change nothing: the counts stay, and so does the loss for a
+    fixed noise vector (rtol 2e-5, a step's loss between two runs)."""
+    import ctypes as C
+    from polee_amd._lib import f32p, i32p, ptr
+    rng = np.random.default_rng(61)
+    S, F, n = 3, 2, 60
+    vars_, design, x_init = _problem(rng, S, F, n)
+    reg = P.RNASeqTranscriptLinearRegression(vars_, x_init, design, np.zeros((S, 1), np.float32), False, 0.5, False,
+                                             kernel_regression_degree=4, ctx=ctx)
+    lib = P.lib()
+    for f in (lib.polee_regression_num_params, lib.polee_regression_num_noise):
+        f.restype, f.argtypes = C.c_int64, [C.c_void_p]
+    counts = lambda: (int(lib.polee_regression_num_noise(reg._h)), int(lib.polee_regression_num_params(reg._h)))
+    before = counts()
+    assert before == (reg.num_noise, reg.num_params)
+    eps = rng.normal(size=reg.num_noise).astype(np.float32)
+    loss0, _ = reg.loss_and_gradients(noise=eps)
+    gene_of = np.arange(n, dtype=np.int32)  # every transcript its own gene: the handle's n features
+    xi0 = np.ascontiguousarray(x_init, np.float32)
+    BAD_ARG = 1
+    num_splice = 5
+    pt, pf = np.array([0], np.int32), np.array([num_splice], np.int32)
+    st = lib.polee_regression_set_joint_likelihood(reg._h, reg.likelihood_model._h, ptr(gene_of, i32p), ptr(xi0, f32p),
+                                                   C.c_int32(num_splice), ptr(pt, i32p), ptr(pf, i32p), C.c_int64(1))
+    assert st == BAD_ARG, st
+    assert counts() == before  # (first: a handle with an isoform block would read more noise than eps holds)
+    loss1, _ = reg.loss_and_gradients(noise=eps)
+    print("joint set-up refused: loss", loss0, "->", loss1)
+    np.testing.assert_allclose(loss1, loss0, rtol=2e-5)
+    design_iso = np.ones((S, 1), np.float32)
+    st = lib.polee_regression_set_gene_isoform_likelihood(reg._h, reg.likelihood_model._h, ptr(gene_of, i32p), ptr(xi0, f32p),
+                                                          ptr(design_iso, f32p), C.c_int32(0))
+    assert st == BAD_ARG, st
+    assert counts() == before
+    loss2, _ = reg.loss_and_gradients(noise=eps)
+    print("gene-isoform set-up refused: loss", loss0, "->", loss2)
+    np.testing.assert_allclose(loss2, loss0, rtol=2e-5)
