@@ -7,10 +7,6 @@
 #include "ptt_internal.hpp"
 #include "psell_device.hpp"
 
-namespace polee {
-std::string csc_to_csr(int64_t m, int64_t n, const void *colptr, int colptr_bytes, const uint32_t *rowval,
-                       const float *nzval, BVec<uint64_t> &rowptr, RawVec<uint32_t> &col, RawVec<float> &val);
-}
 using namespace polee;
 
 struct polee_psell_debug {

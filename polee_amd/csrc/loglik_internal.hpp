@@ -272,4 +272,14 @@ void loglik_release(polee_loglik *ll);
 // the VI loop's forward kernel does, saving the gather launch)
 polee_status loglik_eval_device(polee_loglik *ll, const float *d_x, int K, float *d_g, double *d_lp, bool xwin_ready = false,
                                 const LoglikRemap *remap = nullptr);
+// What the creation of a handle (loglik_create.cpp) needs from the kernels' side (loglik.hip):
+constexpr int SINGLE_THREADS = 256;     // single_rows_kernel's workgroup: one partial lp sum per workgroup and draw (d_single_part)
+constexpr uint32_t GWIN_HEAVY = 32;     // deterministic mode: a transcript present in more tiles is summed by gwin_reduce_heavy_kernel
+// every tile's relative cost and the waves' shares of its slices (tile_cost, tile_cut), while the slice metadata is on the host
+void loglik_prepare_tiles(polee_loglik *ll);
+// the static schedule for a grid of G workgroups (and, once, the dynamic schedule's list and counter), uploaded
+polee_status loglik_ensure_schedule(polee_loglik *ll, int G);
+// CSC (1-based, colptr of 4 or 8 bytes) -> CSR (0-based); "" or an error message (loglik_create.cpp)
+std::string csc_to_csr(int64_t m, int64_t n, const void *colptr, int colptr_bytes, const uint32_t *rowval, const float *nzval,
+                       BVec<uint64_t> &rowptr, RawVec<uint32_t> &col, RawVec<float> &val);
 }  // namespace polee
