@@ -299,11 +299,13 @@ struct WaveStream {
 // advanced: a piece's position travels in the lanes' 32-bit byte offsets, one vector add per piece (a wave's share of a tile is
 // far below 4 GiB), so the wait states between a freshly read SGPR base and the first vector-memory instruction that uses it
 // are paid once per burst (dma_1k), not once per piece (dma_1k_next) --, the piece counter, and the ring offset of the next slot.
-template <uint32_t RB>
-__device__ inline void ring_issue(const uint8_t *gsrc, uint32_t ring_lds, int &issued, uint32_t &slot, int target)
+// `lane_word`: ring_lds + 4 x lane where the caller holds that lane constant in a register anyway (the lanes' offsets are then one
+// shift-and-add on it per burst), 0 where it does not (the lane index is computed here: wave_lane).
+template <uint32_t RB, bool LANE_WORD = false>
+__device__ inline void ring_issue(const uint8_t *gsrc, uint32_t ring_lds, int &issued, uint32_t &slot, int target, uint32_t lane_word = 0u)
 {
     if (issued >= target) return;
-    uint32_t voff = (uint32_t)wave_lane() * 16u + (uint32_t)issued * 1024u;
+    uint32_t voff = LANE_WORD ? (lane_word << 2) + ((uint32_t)issued * 1024u - 4u * ring_lds) : (uint32_t)wave_lane() * 16u + (uint32_t)issued * 1024u;
     dma_1k(gsrc, voff, ring_lds + slot);
     for (;;) {
         slot = slot + 1024u == RB ? 0u : slot + 1024u;
@@ -335,10 +337,11 @@ __device__ inline uint32_t wrap_u(uint32_t a)  // uniform ring offset a < 2 RB
 // `extras` = vector-memory operations issued AFTER the primed ring pieces and before the first refill (the previous tile's flush,
 // the next tile's prefetch): they are younger than the primed pieces and older than every other piece, so only waits for primed
 // pieces have to allow for them.
-template <uint32_t RB>
+template <uint32_t RB, bool LANE_WORD = false>
 struct RingCursor {
     static constexpr int RP = (int)(RB / 1024u);
     const uint32_t ring_lds;
+    const uint32_t lane_word;  // (LANE_WORD) see ring_issue
     const int extras;
     int issued;
     uint32_t slot;
@@ -346,8 +349,8 @@ struct RingCursor {
     const uint8_t *const gsrc;
     uint32_t pos = 0;    // byte offset of the ring's tail inside this wave's range
     uint32_t pos_r = 0;  // pos modulo the ring size
-    __device__ inline RingCursor(const WaveStream &ws, uint32_t ring_lds_, int extras_)
-        : ring_lds(ring_lds_), extras(extras_), issued(__builtin_amdgcn_readfirstlane(ws.issued)),
+    __device__ inline RingCursor(const WaveStream &ws, uint32_t ring_lds_, int extras_, uint32_t lane_word_ = 0u)
+        : ring_lds(ring_lds_), lane_word(lane_word_), extras(extras_), issued(__builtin_amdgcn_readfirstlane(ws.issued)),
           slot((uint32_t)__builtin_amdgcn_readfirstlane((int)ws.slot)), primed(__builtin_amdgcn_readfirstlane(ws.primed)),
           npieces(__builtin_amdgcn_readfirstlane(ws.npieces)), gsrc(reinterpret_cast<const uint8_t *>(uniform_ptr(ws.gsrc)))
     {
@@ -357,7 +360,7 @@ struct RingCursor {
     __device__ inline void wait_for(uint32_t upto)  // bytes [pos, pos + upto) of the wave's range must have landed
     {
         const int need = (int)((pos + upto + 1023u) >> 10);
-        if (issued < need) ring_issue<RB>(gsrc, ring_lds, issued, slot, need);  // (only with a shortened look-ahead: experiments)
+        if (issued < need) ring_issue<RB, LANE_WORD>(gsrc, ring_lds, issued, slot, need, lane_word);  // (only with a shortened look-ahead: experiments)
         wait_vm_outstanding(allowed(need));
     }
     __device__ inline void wait_for_steady(uint32_t upto)  // the same with the whole ring requested ahead (wait_vm_steady)
@@ -369,7 +372,7 @@ struct RingCursor {
         pos += nbytes;
         pos_r += nbytes;
         pos_r = pos_r >= RB ? pos_r - RB : pos_r;
-        ring_issue<RB>(gsrc, ring_lds, issued, slot, min(npieces, (int)(pos >> 10) + RP));
+        ring_issue<RB, LANE_WORD>(gsrc, ring_lds, issued, slot, min(npieces, (int)(pos >> 10) + RP), lane_word);
     }
     __device__ inline void release(uint32_t nbytes)  // the first nbytes behind the tail are consumed
     {
@@ -715,19 +718,17 @@ struct QuadLp {
     }
 };
 
-// Flush of group g of four transcripts (lane t < 16 of `gav`: the LDS address of transcript t's gradient row).  The
+// Flush of a group of four transcripts.  The
 // four registers v are first added across the wave's four rows of 16 lanes and scattered (gfx950 lane swaps: row r
 // is left with transcript VROW[r]'s sums, block by block), then across a row's four blocks (DPP): lanes 12..15 of
 // every row hold one finished sum each and ONE LDS add per (group, draw group) writes 16 different addresses.
 // (Adding the rows' partial sums to the same addresses instead -- four-way conflicts in four times as many LDS
 // atomics -- cost a quarter of the kernel's time.)
+// `ga`: in lanes 12 + j of every row of 16 lanes, the LDS address of draw j of the gradient row of the transcript that row is
+// left with.
 template <int K>
-__device__ inline void quad_flush_group(f32x4 (&acc)[(K + 3) / 4], uint32_t gav, int g, int lane, int j, uint32_t j4, int dbg)
+__device__ inline void quad_flush_sums(f32x4 (&acc)[(K + 3) / 4], uint32_t ga, int lane, int j, int dbg)
 {
-    const uint32_t ga0 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 0), ga2 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 2);
-    const uint32_t ga1 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 1), ga3 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 3);
-    // row 0: transcript 4 g, row 1: 4 g + 2, row 2: 4 g + 1, row 3: 4 g + 3
-    const uint32_t ga = ((lane & 32) ? ((lane & 16) ? ga3 : ga1) : ((lane & 16) ? ga2 : ga0)) + j4;
 #pragma unroll
     for (int kg = 0; kg < (K + 3) / 4; ++kg) {
         auto r1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[kg][0]), __float_as_uint(acc[kg][1]), false, false);
@@ -744,6 +745,38 @@ __device__ inline void quad_flush_group(f32x4 (&acc)[(K + 3) / 4], uint32_t gav,
         acc[kg] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 }
+// The rows' transcripts: row 0: transcript 4 g, row 1: 4 g + 2, row 2: 4 g + 1, row 3: 4 g + 3.
+// The flush of a loop that flushes every slice (wide_masked_stream): lane t < 16 of `gav` holds the LDS address of transcript
+// t's gradient row; group g's addresses by lane reads and selects.
+template <int K>
+__device__ inline void quad_flush_group(f32x4 (&acc)[(K + 3) / 4], uint32_t gav, int g, int lane, int j, uint32_t j4, int dbg)
+{
+    const uint32_t ga0 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 0), ga2 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 2);
+    const uint32_t ga1 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 1), ga3 = (uint32_t)__builtin_amdgcn_readlane((int)gav, 4 * g + 3);
+    const uint32_t ga = ((lane & 32) ? ((lane & 16) ? ga3 : ga1) : ((lane & 16) ? ga2 : ga0)) + j4;
+    quad_flush_sums<K>(acc, ga, lane, j, dbg);
+}
+// The flush of a loop that keeps its sums for a run of slices (narrow_stream): the addresses are a property of the run, so its
+// start spreads them ONCE -- `gal`: every row of 16 lanes holds transcript t's address in lane t; result: lane (row r, quad q,
+// j) holds draw j of transcript 4 q + (0, 2, 1, 3)[r], i.e. group q's address for this row -- by four quad broadcasts under row
+// masks, and the flush of group g moves quad g to the row's last quad with one DPP row shift (none for g = 3) instead of four
+// lane reads, four moves and three selects per group and flush.
+__device__ inline uint32_t quad_spread_rows(uint32_t gal, uint32_t j4)
+{
+    const int v = (int)gal;
+    int o = __builtin_amdgcn_update_dpp(0, v, 0x00, 0xf, 0xf, true);  // quad_perm:[0,0,0,0], every row
+    o = __builtin_amdgcn_update_dpp(o, v, 0xaa, 0x2, 0xf, false);     // quad_perm:[2,2,2,2], row 1
+    o = __builtin_amdgcn_update_dpp(o, v, 0x55, 0x4, 0xf, false);     // quad_perm:[1,1,1,1], row 2
+    o = __builtin_amdgcn_update_dpp(o, v, 0xff, 0x8, 0xf, false);     // quad_perm:[3,3,3,3], row 3
+    return (uint32_t)o + j4;
+}
+template <int K, int G>
+__device__ inline void quad_flush_spread(f32x4 (&acc)[(K + 3) / 4], uint32_t gaq, int lane, int j, int dbg)
+{
+    // lanes 12 + j of a row read lanes 4 G + j of it (the other lanes' values are not used)
+    const uint32_t ga = G == 3 ? gaq : (uint32_t)__builtin_amdgcn_update_dpp(0, (int)gaq, 0x110 + (12 - 4 * G), 0xf, 0xf, true);  // row_shr:12 - 4 G
+    quad_flush_sums<K>(acc, ga, lane, j, dbg);
+}
 // x[c_t][4 kg + j] of transcripts 4 g .. 4 g + 3 (lane t < 16 of `xav`: the LDS address of transcript t's x row)
 template <int KG>
 __device__ inline void quad_load_x_group(uint32_t xav, int g, uint32_t j4, float (*dst)[KG])
@@ -754,6 +787,17 @@ __device__ inline void quad_load_x_group(uint32_t xav, int g, uint32_t j4, float
         dst[u][0] = lds_f(a);
         if (KG > 1) dst[u][KG > 1 ? 1 : 0] = lds_f(a + 16u);  // (draws >= K: a neighbour's values, in columns that are never used)
     }
+}
+// the first group of a slice: the chains start from `c0` (the row sums' floor), which stays in its registers
+template <int KG>
+__device__ inline void quad_phase1_first(f32x4 (&d1)[KG], const f32x4 &c0, const float *p4, const float (*x4)[KG])
+{
+#pragma unroll
+    for (int kg = 0; kg < KG; ++kg) d1[kg] = __builtin_amdgcn_mfma_f32_4x4x1f32(p4[0], x4[0][kg], c0, 0, 0, 0);
+#pragma unroll
+    for (int u = 1; u < 4; ++u)
+#pragma unroll
+        for (int kg = 0; kg < KG; ++kg) d1[kg] = __builtin_amdgcn_mfma_f32_4x4x1f32(p4[u], x4[u][kg], d1[kg], 0, 0, 0);
 }
 template <int KG>
 __device__ inline void quad_phase1(f32x4 (&d1)[KG], const float *p4, const float (*x4)[KG])
@@ -841,20 +885,25 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
     for (int t = 0; t < 8; ++t)
 #pragma unroll
         for (int kg = 0; kg < KG; ++kg) xq[t][kg] = 0.0f;
-    uint32_t xav = aux_lds, gav = aux_lds + 32u;  // lane t < 16: LDS addresses of the x row / gradient row of the run's transcript t
+    uint32_t xav = aux_lds;         // lane t < 16: LDS address of the x row of the run's transcript t
+    uint32_t gaq = aux_lds + 32u;  // the gradient rows' addresses, spread for the flush (quad_spread_rows)
     int pend_w = 0;
     int run_w = 0;  // (MASKED) transcripts of the current run's union
     QuadLp<KG> lp;  // (WANT_LP)
+    // the row sums' start value, as the C operand of each chain's first matrix instruction: four registers held across the loop
+    // instead of moves into every chain's accumulator in every slice (the addend and the order of the sums are the same)
+    f32x4 floorq = f32x4{ROWSUM_FLOOR, ROWSUM_FLOOR, ROWSUM_FLOOR, ROWSUM_FLOOR};
+    asm volatile("" : "+v"(floorq));  // (opaque: not rematerialised per slice)
 
     auto flush = [&]() {
-        quad_flush_group<K>(acc[0], gav, 0, lane, j, j4, dbg);
-        if (pend_w > 4) quad_flush_group<K>(acc[1], gav, 1, lane, j, j4, dbg);
-        if (pend_w > 8) quad_flush_group<K>(acc[2], gav, 2, lane, j, j4, dbg);
-        if (pend_w > 12) quad_flush_group<K>(acc[3], gav, 3, lane, j, j4, dbg);
+        quad_flush_spread<K, 0>(acc[0], gaq, lane, j, dbg);
+        if (pend_w > 4) quad_flush_spread<K, 1>(acc[1], gaq, lane, j, dbg);
+        if (pend_w > 8) quad_flush_spread<K, 2>(acc[2], gaq, lane, j, dbg);
+        if (pend_w > 12) quad_flush_spread<K, 3>(acc[3], gaq, lane, j, dbg);
         pend_w = 0;
     };
 
-    RingCursor<RB> rc(ws, ring_lds, extras);  // (the tail stands at the current slice)
+    RingCursor<RB, true> rc(ws, ring_lds, extras, lc1[0]);  // (the tail stands at the current slice; lc1[0] = ring_lds + 4 x lane)
     uint32_t e_next = (uint32_t)__builtin_amdgcn_readlane((int)ws.ent, 0);  // (a slice's end is the next one's start: one lane read per slice)
     for (int si = 0; si < ws.nsl; ++si) {
         const uint32_t e0 = e_next;
@@ -881,16 +930,14 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
                 w = run_w;
             }
             xav = live ? xw_lds + cid * (uint32_t)(K * 4) : aux_lds;
-            gav = live ? gw_lds + cid * (uint32_t)(K * 4) : aux_lds + 32u;
+            gaq = quad_spread_rows(live ? gw_lds + cid * (uint32_t)(K * 4) : aux_lds + 32u, j4);
             quad_load_x_group(xav, 0, j4, xq);
             if (w > 4) quad_load_x_group(xav, 1, j4, xq + 4);
         }
         STAMP(3);  // run change: flush + column lookup
 
         const uint32_t row0 = wrap_u<RB>(rc.pos_r + 256u);
-        f32x4 d1[KG];
-#pragma unroll
-        for (int kg = 0; kg < KG; ++kg) d1[kg] = f32x4{ROWSUM_FLOOR, ROWSUM_FLOOR, ROWSUM_FLOOR, ROWSUM_FLOOR};
+        f32x4 d1[KG];  // (every chain starts from floorq: quad_phase1_first)
         f32x4 kv = f32x4{1.f, 1.f, 1.f, 1.f};
         // NG = groups of four transcripts of the slice; FAST = its bytes do not wrap around the ring's end
         auto body = [&](auto NGc, auto FASTc) {
@@ -950,7 +997,7 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
                 slice_consumed([&] { rc.advance(bytes); }, st, dbg);
 #pragma unroll
                 for (int t = 0; t < 4 * NG; ++t) mv[t] = __uint_as_float(__float_as_uint(mv[t]) & (uint32_t)(((int)(mk << (31 - t))) >> 31));
-                quad_phase1(d1, mv, xq);
+                quad_phase1_first(d1, floorq, mv, xq);
                 if (NG > 1) quad_phase1(d1, mv + 4, xq + 4);
                 if (NG > 2) {  // (registers hold the x rows of eight transcripts: the others' are re-read per slice)
                     float xr[8][KG];
@@ -970,7 +1017,7 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
                 read_p(0, NG);
                 read_q(0, NG);
                 slice_consumed([&] { rc.advance(bytes); }, st, dbg);
-                quad_phase1(d1, pv, xq);
+                quad_phase1_first(d1, floorq, pv, xq);
                 if (NG > 1) quad_phase1(d1, pv + 4, xq + 4);
                 quad_weights<K, WANT_LP, HAS_KS>(d1, kv, j, lp);
                 quad_phase2(acc[0], d1, qv[0]);
@@ -995,7 +1042,7 @@ __device__ inline void narrow_stream(WaveStream &ws, const char *ring, int extra
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (!(dbg & 16)) __builtin_amdgcn_s_setprio(0);
-                quad_phase1(d1, pw, xq);
+                quad_phase1_first(d1, floorq, pw, xq);
                 quad_phase1(d1, pw + 4, xq + 4);
                 quad_phase1(d1, pv, xr);
                 if (NG > 3) quad_phase1(d1, pv + 4, xr + 4);
