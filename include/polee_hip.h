@@ -339,6 +339,39 @@ polee_status polee_hclust_parallel(int64_t m, int64_t n, const void *colptr, int
 polee_status polee_hclust_parallel_device(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes,
                                           const uint32_t *rowval, int32_t *node_parent_idxs, int32_t *node_js);
 
+/* ---- tree from transcript sequences: polee fit-tree (src/main.jl:638-660) ------------------
+ * The definition is this project's own: upstream's k-mer hash is Julia's and its merge order among equal
+ * similarities depends on heap positions.  Upstream's constants are kept (src/constants.jl:88-89). */
+#define POLEE_KMER_K 32
+#define POLEE_KMER_H 200
+/* most transcripts a tree is built for (n * 200 sketch entries are indexed with 32 bits) */
+#define POLEE_KMER_MAX_N 10000000LL
+/* most co-occurring pairs of transcripts the candidate-edge step emits (8 bytes each, sorted out of place): a k-mer that r
+ * transcripts share gives r (r - 1) / 2 pairs, so repeat-derived k-mers shared by thousands of transcripts grow quadratically.
+ * Counted before anything is allocated; above the limit the builders return POLEE_ERR_BAD_ARG. */
+#define POLEE_KMER_MAX_PAIRS (1LL << 30)
+/* windows (k-mer start positions) one workgroup of the sketch kernel covers: a longer transcript is split over several */
+#define POLEE_KMER_SKETCH_CHUNK 8192
+/* One-permutation MinHash sketches of the transcripts' canonical 32-mers (replaces KmerSketch(seq), src/kmersketch.jl:7-40,
+ * with the hash and the bin rule of DESIGN.md 3.12).  bases: the transcripts' ASCII bytes concatenated (A C G T in either
+ * case; any other byte breaks the windows that touch it), transcript t = bases[offsets[t] .. offsets[t+1]), offsets[0] = 0.
+ * sketches: uint64 [n][200], 0 = empty bin.  Bitwise reproducible (a minimum does not depend on order). */
+polee_status polee_kmer_sketch(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, uint64_t *sketches);
+/* the same sketches on the host threads, no context (what `fit_tree --host` uses) */
+polee_status polee_kmer_sketch_host(int64_t n, const int64_t *offsets, const uint8_t *bases, uint64_t *sketches);
+/* The tree of n sketches (replaces build_polya_tree_transformation / cluster, src/kmercluster.jl:96-262, and order_nodes,
+ * :69-93; similarity and union as src/kmersketch.jl:43-67): greedy joining by approximate Jaccard, ties by smaller node numbers,
+ * the rest joined Huffman-fashion, nodes in DFS pre-order, right child first.  Outputs int32 [2n-1] each, the arrays
+ * polee_ptt_create takes.  Host only, no context; POLEE_ERR_BAD_ARG for a sketch value outside its bin. */
+polee_status polee_kmer_tree_host(int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js);
+/* the same tree, node for node: the candidate edges (every pair of sketches that shares a bin value, with the number of shared
+ * and of jointly empty bins) come from the device -- one sort of the sketch entries, one of the pair keys -- the merge loop
+ * runs on the host (replaces the index / queue set-up, src/kmercluster.jl:107-190) */
+polee_status polee_kmer_tree(polee_ctx *ctx, int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js);
+/* polee_kmer_sketch + polee_kmer_tree with the sketches left on the device in between (polee fit-tree, src/main.jl:638-649) */
+polee_status polee_fit_tree(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, int32_t *node_parent_idxs,
+                            int32_t *node_js);
+
 /* ---- one sample over several GPUs -----------------------------------
  * X's rows (fragments) are sharded over the ranks in contiguous blocks; every rank creates its
  * polee_loglik from its block and runs the same polee_vi (same seed => identical state); per

@@ -1,6 +1,6 @@
 /*
  * polee_hip_debug.h -- host-only introspection of the device layouts libpolee_hip builds.
- * These entry points never touch the GPU; the CPU test-suite uses them to check the tree
+ * These entry points never touch the GPU (but for the few that take a context); the CPU test-suite uses them to check the tree
  * plan (Euler tour, leaf ranges) and the PSELL matrix layout against the oracle by
  * emulating the kernels in NumPy.  Not part of the drop-in boundary.
  */
@@ -105,6 +105,13 @@ polee_status polee_debug_gibbs_assignments(polee_gibbs *g, int32_t chain, int32_
 /* One Binomial(N[i], p[i]) variate per entry from csrc/binomial.hpp, keyed by (seed, draw index i, node 0): 0 <= N < 2^31,
  * 0 <= p <= 1; out i64 [count] (the goodness-of-fit tests of the multinomial sampler's nodes) */
 polee_status polee_debug_binomial(polee_ctx *ctx, const int64_t *N, const double *p, int64_t count, uint64_t seed, int64_t *out);
+
+/* The candidate edges of polee_kmer_tree: every pair u < v (1-based) of the n sketches with mat > 0 shared bin values, and empt,
+ * the bins empty in both, sorted by (u, v).  Count, then fill arrays of that many entries (capacity: what the caller
+ * allocated; POLEE_ERR_BAD_ARG when it is too small).  ctx: the device's edges; NULL: the host builder's. */
+polee_status polee_debug_kmer_edges_count(polee_ctx *ctx_or_null, int64_t n, const uint64_t *sketches, int64_t *count);
+polee_status polee_debug_kmer_edges_fill(polee_ctx *ctx_or_null, int64_t n, const uint64_t *sketches, int64_t capacity,
+                                         uint32_t *u, uint32_t *v, uint32_t *mat, uint32_t *empt);
 
 #ifdef __cplusplus
 }

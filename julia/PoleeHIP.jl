@@ -330,6 +330,61 @@ function hclust(m::Integer, n::Integer, colptr::Union{Vector{UInt32},Vector{UInt
     return parents, js
 end
 
+# ---- tree from transcript sequences: polee fit-tree (src/main.jl:638-660, src/kmersketch.jl, src/kmercluster.jl) ----
+"(offsets, bases) of sequences given as strings or byte vectors: the layout polee_kmer_sketch takes"
+function concat_sequences(seqs)
+    offsets = Vector{Int64}(undef, length(seqs) + 1)
+    offsets[1] = 0
+    for (i, s) in enumerate(seqs)
+        offsets[i + 1] = offsets[i] + ncodeunits(String(s))
+    end
+    bases = Vector{UInt8}(undef, max(offsets[end], 1))
+    for (i, s) in enumerate(seqs)
+        copyto!(bases, offsets[i] + 1, codeunits(String(s)), 1, offsets[i + 1] - offsets[i])
+    end
+    return offsets, bases
+end
+
+"MinHash sketches of the canonical 32-mers, UInt64 [200, n] (column t = transcript t); ctx = nothing: on the host threads"
+function kmer_sketches(seqs; ctx::Union{Nothing,Context}=nothing)
+    offsets, bases = concat_sequences(seqs)
+    n = length(seqs)
+    sk = zeros(UInt64, 200, n)
+    if ctx === nothing
+        GC.@preserve offsets bases sk check(
+            ccall((:polee_kmer_sketch_host, LIB), Cint, (Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{UInt64}), n, offsets, bases, sk))
+    else
+        GC.@preserve offsets bases sk check(
+            ccall((:polee_kmer_sketch, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{UInt64}), ctx.h, n, offsets, bases, sk), ctx.h)
+    end
+    return sk
+end
+
+"sketches UInt64 [200, n] -> (node_parent_idxs, node_js); ctx = nothing: host only, else the candidate edges come from the GPU"
+function kmer_tree(sk::Matrix{UInt64}; ctx::Union{Nothing,Context}=nothing)
+    n = size(sk, 2)
+    parents, js = Vector{Int32}(undef, 2n - 1), Vector{Int32}(undef, 2n - 1)
+    if ctx === nothing
+        GC.@preserve sk parents js check(
+            ccall((:polee_kmer_tree_host, LIB), Cint, (Int64, Ptr{UInt64}, Ptr{Int32}, Ptr{Int32}), n, sk, parents, js))
+    else
+        GC.@preserve sk parents js check(
+            ccall((:polee_kmer_tree, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt64}, Ptr{Int32}, Ptr{Int32}), ctx.h, n, sk, parents, js), ctx.h)
+    end
+    return parents, js
+end
+
+"build_polya_tree_transformation (kmercluster.jl:96-262) on the GPU: the sketches stay on the device between the two steps"
+function build_polya_tree_transformation(ctx::Context, seqs)
+    offsets, bases = concat_sequences(seqs)
+    n = length(seqs)
+    parents, js = Vector{Int32}(undef, 2n - 1), Vector{Int32}(undef, 2n - 1)
+    GC.@preserve offsets bases parents js check(
+        ccall((:polee_fit_tree, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}),
+              ctx.h, n, offsets, bases, parents, js), ctx.h)
+    return parents, js
+end
+
 "release the scratch blocks the host-side builders keep between samples"
 host_cache_trim() = ccall((:polee_host_cache_trim, LIB), Cvoid, ())
 

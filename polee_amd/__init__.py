@@ -20,6 +20,8 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   gibbs_sampler / GibbsSampler (`polee debug-sample`)                        src/gibbs.jl, src/main.jl:925-957
   expectation_maximization / EM (`polee debug-optimize`)                     src/em.jl, src/main.jl:960-988
   polee_sample / ApproxSampleStream / multinomial_counts (`polee sample`)    src/main.jl:756-919
+  read_fasta / kmer_sketches / build_polya_tree_transformation               src/kmersketch.jl, src/kmercluster.jl
+  (`polee fit-tree`: python -m polee_amd.fit_tree)                           src/main.jl:638-660
 
 All numerics run in libpolee_hip.so on the GPU; nothing here computes on the CPU.
 """
@@ -57,6 +59,9 @@ def __getattr__(name):
     if name in ("RNASeqLogisticRegression", "build_factor_matrix", "write_classification_probs"):
         from . import classify
         return getattr(classify, name)
+    if name in ("read_fasta", "kmer_sketches", "kmer_tree", "kmer_candidate_edges", "build_polya_tree_transformation"):
+        from . import fit_tree
+        return getattr(fit_tree, name)
     if name in ("IsoformEffects", "estimate_isoform_effect_sizes", "build_design_matrix", "gene_map", "gene_initial_values",
                 "write_isoform_regression_effects", "write_aitchison_results", "write_expression", "load_kallisto_estimates"):
         from . import regression

@@ -92,6 +92,14 @@ def lib():
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         L.polee_vi_default_opts.restype = None
+        # polee fit-tree (polee_amd/fit_tree.py)
+        L.polee_kmer_sketch.argtypes = [C.c_void_p, C.c_int64, i64p, u8p, u64p]
+        L.polee_kmer_sketch_host.argtypes = [C.c_int64, i64p, u8p, u64p]
+        L.polee_kmer_tree_host.argtypes = [C.c_int64, u64p, i32p, i32p]
+        L.polee_kmer_tree.argtypes = [C.c_void_p, C.c_int64, u64p, i32p, i32p]
+        L.polee_fit_tree.argtypes = [C.c_void_p, C.c_int64, i64p, u8p, i32p, i32p]
+        L.polee_debug_kmer_edges_count.argtypes = [C.c_void_p, C.c_int64, u64p, C.POINTER(C.c_int64)]
+        L.polee_debug_kmer_edges_fill.argtypes = [C.c_void_p, C.c_int64, u64p, C.c_int64, u32p, u32p, u32p, u32p]
         _lib = L
     return _lib
 

@@ -370,6 +370,25 @@ def read_transformation(filename):
         return f.read("node_parent_idxs", np.int32), f.read("node_js", np.int32)
 
 
+PTT_FORMAT_VERSION = 1  # (src/constants.jl: the format version `polee fit-tree` writes)
+
+
+def write_transformation(filename, parents, js, transcript_ids, args=""):
+    """PTT file of `polee fit-tree` (main.jl:650-659): node_parent_idxs, node_js (int32), transcript_ids, and the metadata
+    group with version, date and args.  read_transformation / read_transformation_ids read it back."""
+    parents, js = np.ascontiguousarray(parents, np.int32), np.ascontiguousarray(js, np.int32)
+    if len(parents) != len(js) or len(js) != 2 * len(transcript_ids) - 1:
+        raise ValueError("a tree of %d transcripts has %d nodes, not %d" % (len(transcript_ids), 2 * len(transcript_ids) - 1, len(js)))
+    with File(filename, "w") as f:
+        f.write("node_parent_idxs", parents)
+        f.write("node_js", js)
+        f.write_strings("transcript_ids", list(transcript_ids))
+        f.create_group("metadata")
+        f.write_attr("metadata", "version", PTT_FORMAT_VERSION)
+        f.write_attr("metadata", "date", datetime.datetime.now().isoformat())
+        f.write_attr("metadata", "args", args)
+
+
 def _read_variable_strings(f, name):
     """A variable-length string dataset (what HDF5.jl writes for an Array{String}): a list of str."""
     L = lib()

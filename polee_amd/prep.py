@@ -19,9 +19,10 @@ AUTO_EXACT_MAX_N transcripts (where it costs well under a second) and the rounds
 
 `polee prep-salmon` (src/main.jl:723-750): the factored likelihood of `salmon quant -d` output on a given tree:
 
-    python -m polee_amd.prep --salmon salmon_quant_dir --ptt-tree tree.h5 --transcript-ids ids.txt -o prepared-sample.h5
+    python -m polee_amd.prep --salmon salmon_quant_dir --ptt-tree tree.h5 [--transcript-ids ids.txt] -o prepared-sample.h5
 
-(`ids.txt`: one transcript id per line in the tree's order, i.e. the `transcript_ids` dataset of the PTT file).
+(`tree.h5`: what `python -m polee_amd.fit_tree` writes.  `ids.txt`: one transcript id per line in the tree's order; without it
+the ids are the `transcript_ids` dataset of the tree file, main.jl:740).
 """
 import argparse
 import sys
@@ -115,10 +116,16 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.salmon is not None:
-        if a.ptt_tree is None or a.transcript_ids is None:
-            ap.error("--salmon needs --ptt-tree and --transcript-ids")
-        with open(a.transcript_ids) as f:
-            ids = [line.rstrip("\n") for line in f if line.strip()]
+        if a.ptt_tree is None:
+            ap.error("--salmon needs --ptt-tree (and --transcript-ids, unless the tree file holds transcript_ids)")
+        if a.transcript_ids is None:  # (main.jl:740: the ids `polee fit-tree` stored with the tree)
+            try:
+                ids = h5io.read_transformation_ids(a.ptt_tree)
+            except h5io.HDF5Error as e:
+                ap.error("--salmon without --transcript-ids: %s" % e)
+        else:
+            with open(a.transcript_ids) as f:
+                ids = [line.rstrip("\n") for line in f if line.strip()]
         params = approximate_salmon_likelihood_to_file(LogitSkewNormalPTTApprox("static"), a.salmon, ids, a.ptt_tree,
                                                        a.output, use_efflen_jacobian=not a.no_efflen_jacobian,
                                                        seed=a.seed, ctx=Context(a.device),

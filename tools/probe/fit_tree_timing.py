@@ -1,0 +1,55 @@
+"""Phase times of `polee fit-tree` at transcriptome size: a generated transcriptome (tools/synth_seq.py; default n = 200 000,
+mean 2 kb), the device path (polee_fit_tree: upload, sketch kernel, candidate edges, host merge -- the builder's own phases,
+POLEE_BUILD_TIMING, on stderr) and the --host path (polee_kmer_sketch_host + polee_kmer_tree_host on the host threads), each
+once, and whether both give the same tree.
+
+    POLEE_BUILD_TIMING=1 python tools/probe/fit_tree_timing.py [--n 200000] [--mean-len 2000] [--seed 1] [--skip-host]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=200000)
+    ap.add_argument("--mean-len", type=int, default=2000)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--skip-device", action="store_true")
+    a = ap.parse_args()
+    import polee_amd as P
+    from tools import synth_seq
+    t0 = time.time()
+    seqs = synth_seq.make_transcripts(a.n, seed=a.seed, mean_len=a.mean_len)
+    total = sum(len(s) for s in seqs)
+    print("generated n = %d, %d bases (mean %.0f, longest %d) in %.1f s" % (a.n, total, total / a.n, max(map(len, seqs)), time.time() - t0), flush=True)
+    trees = {}
+    if not a.skip_device:
+        ctx = P.Context(0)
+        P.kmer_sketches(seqs[:1000], ctx=ctx)  # (first use: module load, the context's first allocations)
+        t0 = time.time()
+        trees["device"] = P.build_polya_tree_transformation(seqs, ctx=ctx)
+        print("device path (polee_fit_tree, with the concatenation of the sequences): %.3f s" % (time.time() - t0), flush=True)
+    if not a.skip_host:
+        t0 = time.time()
+        sk = P.kmer_sketches(seqs, host=True)
+        t1 = time.time()
+        trees["host"] = P.kmer_tree(sk, host=True)
+        t2 = time.time()
+        print("host path: sketches %.3f s, tree %.3f s (%d host threads usable)" % (t1 - t0, t2 - t1, len(os.sched_getaffinity(0))), flush=True)
+        filled = (sk != 0).sum(axis=1)
+        print("sketches: %.1f non-empty bins on average, %d empty sketches" % (filled.mean(), int((filled == 0).sum())))
+    if len(trees) == 2:
+        same = all(np.array_equal(x, y) for x, y in zip(trees["device"], trees["host"]))
+        print("device tree == host tree: %s" % same)
+        return 0 if same else 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
