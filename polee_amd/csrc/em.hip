@@ -172,17 +172,15 @@ __global__ __launch_bounds__(EM_NORM_BLOCK) void em_normalise_kernel(int64_t n, 
 // ---- the fixed-point residual, in f64 ---------------------------------------------------------------------------------------------
 // At the optimum |g_j / M - 1| is a few 1e-8, an ulp of the f32 gradient the iterations use (summed with f32 atomics: 1e-6): the
 // residual takes a gradient in f64.  On request only, so simple rather than fast: the layout of X is read as it lies, slice by slice
-// with the decoding of loglik.hip's per-tile kernel (psell_tile_body: compact, masked and mixed slices), a lane per fragment,
-// row sums and weights in f64, the tile's gradient window in LDS (f64 atomics), flushed with f64 atomics; streams C and S likewise.
-// It is evaluated at the mixture polee_em_get_mixture hands out (m = the f32 of y / sum y), so that a caller can check it.
-// The slice decoding (hdr_id / vat / cat, the row counts) is psell_tile_body's, restated: a change of a slice format has to be made
-// in both (loglik_internal.hpp says so at the formats); tests/test_gpu_em.py holds this kernel against f64 NumPy on the fixture,
-// with multiplicities, and against the f64 oracle over every stream of a C2-size layout.
+// through PsellSliceReader (psell_slice.hpp: compact, masked and mixed slices, as loglik.hip's per-tile kernel reads them), a lane per
+// fragment, row sums and weights in f64, the tile's gradient window in LDS (f64 atomics), flushed with f64 atomics; streams C and S
+// likewise.  It is evaluated at the mixture polee_em_get_mixture hands out (m = the f32 of y / sum y), so that a caller can check it;
+// tests/test_gpu_em.py holds this kernel against f64 NumPy on the fixture, with multiplicities, and against the f64 oracle.
 struct EmG64Args {
     const uint8_t *data;
     const uint32_t *slice_off, *tile_slice, *tile_dict, *dict;
     const float *slice_ks;
-    int tiles_a1, tiles_a1m, tiles_a2, tiles_a, tiles_s;
+    PsellTileBounds tiles;
     const float *m;  // [n]
     double *g;       // [n], zeroed
 };
@@ -198,44 +196,21 @@ __global__ __launch_bounds__(256) void em_g64_tiles_kernel(EmG64Args A)
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t s0 = A.tile_slice[tile], s1 = A.tile_slice[tile + 1];
-    const bool compact = tile < A.tiles_a;
-    const int stream = tile < A.tiles_a1 ? PSELL_A1 : (tile < A.tiles_a1m ? PSELL_A1M : (tile < A.tiles_a2 ? PSELL_A2 : (tile < A.tiles_a ? PSELL_A2M : (tile < A.tiles_s ? PSELL_BN : PSELL_B))));
+    const int stream = psell_stream_of_tile(A.tiles, tile);
     for (uint32_t s = s0 + wave; s < s1; s += 4u) {
-        const uint32_t off = A.slice_off[s] & PSELL_OFF_MASK;
-        const uint32_t units = (A.slice_off[s + 1] & PSELL_OFF_MASK) - off;
-        const bool masked = stream == PSELL_A1M || stream == PSELL_A2M || ((A.slice_off[s] >> PSELL_FLAG_MASKED_BIT) & 1u) != 0;
-        const int hrows = stream == PSELL_A2M ? 2 : 1;
-        const int nrows = compact ? (int)(units / 2u) - hrows - (HAS_KS ? 1 : 0)
-                                  : (int)((units - (HAS_KS && stream == PSELL_BN ? 2u : 0u)) / 3u);
-        const uint16_t *hdr = reinterpret_cast<const uint16_t *>(A.data + (size_t)off * 128);
-        int w = nrows;
-        uint32_t mk = 0;
-        auto hdr_id = [&](int t) -> uint16_t { return hdr[128 * (t >> 4) + 2 * (t & 15) + 1]; };
-        if (masked) {
-            w = 0;
-            while (w < 16 * hrows && hdr_id(w) != PSELL_NO_COL) ++w;
-            mk = hdr[2 * lane];
-            if (hrows == 2) mk |= (uint32_t)hdr[128 + 2 * lane] << 16;
-        }
-        const float *vbase = reinterpret_cast<const float *>(A.data + (size_t)off * 128 + (compact ? 256 * hrows : 0));
-        auto vat = [&](int t) -> float {
-            if (masked) return (mk >> t) & 1u ? vbase[__popc(mk & ((1u << t) - 1u)) * 64 + lane] : 0.0f;
-            return vbase[t * 64 + (compact ? (int)psell_row_pos(stream, (uint32_t)t, (uint32_t)lane) : lane)];
-        };
-        const uint16_t *cols = compact ? hdr : reinterpret_cast<const uint16_t *>(A.data + (size_t)off * 128 + (size_t)w * 256) + lane;
-        const int cstride = compact ? 1 : 64;
-        auto cat = [&](int t) -> int { return masked ? (int)hdr_id(t) : (int)cols[t * cstride]; };
+        const PsellSliceReader R(A.data, A.slice_off[s], A.slice_off[s + 1], stream, HAS_KS, lane);
+        const int w = R.w;
         double p = 0.0;
         for (int t = 0; t < w; ++t) {
-            const float v = vat(t);
-            if (v != 0.0f) p += (double)v * (double)A.m[A.dict[d0 + cat(t)]];
+            const float v = R.value(t);
+            if (v != 0.0f) p += (double)v * (double)A.m[A.dict[d0 + R.col(t)]];
         }
         const double ksv = HAS_KS ? (double)A.slice_ks[(size_t)s * 64 + lane] : 1.0;
         const double wgt = p > 0.0 ? ksv / p : 0.0;  // (unused lanes: only zero values)
         if (wgt != 0.0)
             for (int t = 0; t < w; ++t) {
-                const float v = vat(t);
-                if (v != 0.0f) atomicAdd(&gw[cat(t)], (double)v * wgt);
+                const float v = R.value(t);
+                if (v != 0.0f) atomicAdd(&gw[R.col(t)], (double)v * wgt);
             }
     }
     __syncthreads();
@@ -475,7 +450,7 @@ polee_status em_residual64(polee_em *E)
         if (ceil_div(h.max_tile_cols, PSELL_DICT_ALIGN) * PSELL_DICT_ALIGN > PSELL_MAX_TILE_COLS)
             return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_em_get_info: a tile dictionary of %d entries", (int)h.max_tile_cols);
         EmG64Args A{ll->d_data.p, ll->d_slice_off.p, ll->d_tile_slice.p, ll->d_tile_dict.p, ll->d_dict.p, ll->d_slice_ks.p,
-                    (int)h.num_tiles_a1, (int)h.num_tiles_a1m, (int)h.num_tiles_a2, (int)h.num_tiles_a, (int)h.num_tiles_s, E->out.p, g64.p};
+                    h.tile_bounds(), E->out.p, g64.p};
         if (ll->has_ks) hipLaunchKernelGGL(em_g64_tiles_kernel<true>, dim3((unsigned)h.num_tiles), dim3(256), 0, stream, A);
         else hipLaunchKernelGGL(em_g64_tiles_kernel<false>, dim3((unsigned)h.num_tiles), dim3(256), 0, stream, A);
         POLEE_KERNEL_CHECK(ctx);

@@ -111,12 +111,11 @@ __device__ inline void psell_tile_body(const PsellArgs &A, int tile, float *xw, 
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t s0 = tile_slice[tile], s1 = tile_slice[tile + 1];
-    const bool compact = tile < A.tiles_a;
     double lpacc[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) lpacc[k] = 0.0;
 
-    const int stream = tile < A.tiles_a1 ? PSELL_A1 : (tile < A.tiles_a1m ? PSELL_A1M : (tile < A.tiles_a2 ? PSELL_A2 : (tile < A.tiles_a ? PSELL_A2M : (tile < A.tiles_s ? PSELL_BN : PSELL_B))));
+    const int stream = psell_stream_of_tile(PsellTileBounds{A.tiles_a1, A.tiles_a1m, A.tiles_a2, A.tiles_a, A.tiles_s}, tile);
     // Deterministic mode, stream B (rows of more than 32 transcripts: rare, a fraction of a per cent of the non-zeros where they
     // occur at all): ONE wave takes all slices of the tile in order -- a wave's LDS adds retire in program order, four waves' do
     // not -- and the tile's sums are STORED to its slots of gwin, which gwin_reduce_kernel adds in tile order like every other
@@ -124,35 +123,9 @@ __device__ inline void psell_tile_body(const PsellArgs &A, int tile, float *xw, 
     // bitwise reproducible -- one gradient entry moving by an ulp between launches on a 3 M-fragment sample with 699 such rows.)
     const bool det = A.gwin != nullptr && tile >= A.tiles_s;
     for (uint32_t s = det ? (wave == 0 ? s0 : s1) : s0 + wave; s < s1; s += det ? 1u : 4u) {
-        const uint32_t off = slice_off[s] & PSELL_OFF_MASK;
-        const uint32_t units = (slice_off[s + 1] & PSELL_OFF_MASK) - off;
-        // compact slices (uniform streams): uint16 lcol[128] header, then float val[w][64];
-        // masked slices: one (A1M) or two (A2M) rows of uint32 hw[64] (low half: 16 bits of the lane's mask, high half:
-        // transcript ids), then float val[i][64] = the lane's i-th non-zero;
-        // mixed slices: float val[w][64]; uint16 lcol[w][64]
-        const bool masked = stream == PSELL_A1M || stream == PSELL_A2M || ((slice_off[s] >> PSELL_FLAG_MASKED_BIT) & 1u) != 0;
-        const int hrows = stream == PSELL_A2M ? 2 : 1;
-        const int nrows = compact ? (int)(units / 2u) - hrows - (HAS_KS ? 1 : 0)  // (+ a ks row when factored: uniform streams and BN)
-                                  : (int)((units - (HAS_KS && stream == PSELL_BN ? 2u : 0u)) / 3u);
-        const uint16_t *hdr = reinterpret_cast<const uint16_t *>(data + (size_t)off * 128);
-        int w = nrows;
-        uint32_t mk = 0;
-        auto hdr_id = [&](int t) -> uint16_t { return hdr[128 * (t >> 4) + 2 * (t & 15) + 1]; };  // (masked slices)
-        if (masked) {
-            w = 0;
-            while (w < 16 * hrows && hdr_id(w) != PSELL_NO_COL) ++w;
-            mk = hdr[2 * lane];
-            if (hrows == 2) mk |= (uint32_t)hdr[128 + 2 * lane] << 16;
-        }
-        // (compact slices store element r of row t at position psell_row_pos(stream, t, r) of the row)
-        const float *vbase = reinterpret_cast<const float *>(data + (size_t)off * 128 + (compact ? 256 * hrows : 0));
-        auto vat = [&](int t) -> float {
-            if (masked) return (mk >> t) & 1u ? vbase[__popc(mk & ((1u << t) - 1u)) * 64 + lane] : 0.0f;
-            return vbase[t * 64 + (compact ? (int)psell_row_pos(stream, (uint32_t)t, (uint32_t)lane) : lane)];
-        };
-        const uint16_t *cols = compact ? hdr : reinterpret_cast<const uint16_t *>(data + (size_t)off * 128 + (size_t)w * 256) + lane;
-        const int cstride = compact ? 1 : 64;
-        auto cat = [&](int t) -> int { return masked ? (int)hdr_id(t) : (int)cols[t * cstride]; };
+        // (the slice's format -- compact, masked or mixed -- is the reader's business: psell_slice.hpp)
+        const PsellSliceReader R(data, slice_off[s], slice_off[s + 1], stream, HAS_KS, lane);
+        const int w = R.w;
 
         // sweep 1: row sums s[k] = sum_t v[t] * x[c[t]][k]
         float sacc[K];
@@ -164,13 +137,13 @@ __device__ inline void psell_tile_body(const PsellArgs &A, int tile, float *xw, 
             int c[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                v[u] = vat(t + u);
-                c[u] = cat(t + u);
+                v[u] = R.value(t + u);
+                c[u] = R.col(t + u);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) fma_row<K>(v[u], xw + c[u] * K, sacc);
         }
-        for (; t < w; ++t) fma_row<K>(vat(t), xw + cat(t) * K, sacc);
+        for (; t < w; ++t) fma_row<K>(R.value(t), xw + R.col(t) * K, sacc);
         const float ksv = HAS_KS ? slice_ks[(size_t)s * 64 + lane] : 1.0f;
         float wk[K];
 #pragma unroll
@@ -180,8 +153,8 @@ __device__ inline void psell_tile_body(const PsellArgs &A, int tile, float *xw, 
         }
         // sweep 2 (slice is L1/L2 resident): g[c[t]][k] += v[t] * w[k], summed per run of equal ids
         for (t = 0; t < w; ++t) {
-            const float v = vat(t);
-            const int c = cat(t);
+            const float v = R.value(t);
+            const int c = R.col(t);
             float q[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) q[k] = v * wk[k];
@@ -607,7 +580,7 @@ static polee_status launch_stream(polee_loglik *ll, PsellArgs &A, int dbg)
     hipStream_t st = ctx->stream;
     // a uniform slice of w transcripts occupies (w+1)*256 bytes and may start 768 bytes into a 1 KiB piece
     static_assert((PSELL_NARROW_MAX + 2) * 256 + 1024 <= STREAM_RB1, "A1 slices (+ ks row) must fit their ring");
-    static_assert(((PSELL_MIXED_NARROW_MAX * 384 + 255) & ~255) + 256 + 1024 <= STREAM_RB1, "BN slices (+ ks row) must fit their ring");
+    static_assert(psell_slice_geom(PSELL_BN, false, PSELL_MIXED_NARROW_MAX, true).bytes + 1024 <= STREAM_RB1, "BN slices (+ ks row) must fit their ring");
     static_assert((PSELL_WIDE_MAX + 3) * 256 + 1024 <= STREAM_RB2, "A2M slices (+ ks row) must fit their ring");  // (A2: wide_stream's own assertion)
     const size_t lds = stream_lds_bytes<K, DET>();
     int &occ = ll->occ_cache[K][LP ? 1 : 0][KS ? 1 : 0][DET ? 1 : 0];

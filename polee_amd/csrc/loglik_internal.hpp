@@ -17,57 +17,16 @@
 //     by xwin_gather_kernel -- starts 16-byte aligned and reaches LDS by LDS-DMA like the slice stream.
 //   * The kernel accumulates the tile's gradient contributions in LDS (ds_add_f32) and flushes L*K
 //     values to HBM per tile.
-//   * Rows are split into six streams, each a contiguous range of tiles (in this order):
-//       A1, A1M, A2, A2M = UNIFORM slices: all rows of a slice are stored under ONE transcript set, kept once per slice.
-//         A1  (dense, sets of <= 16): uint16 lcol[128] header + float val[w][64], 4 B per entry: whole 64-row slices of
-//              every run of identical rows, run remainders of >= 32 rows (zero padded), and dense UNION slices -- leftover
-//              rows of neighbouring sets packed under the union of their sets with zeros where a row lacks a transcript
-//              (a zero adds nothing to a row sum or a gradient, exactly) -- when the union is (almost) full.
-//         A1M (MASKED, unions of <= 16): leftover rows whose sets differ -- any 64 rows whose union has <= 16 transcripts.
-//              Header: uint32 hw[64] -- low half of hw[r] = the mask of fragment r (bit t: it is compatible with
-//              transcript t of the union), high half of hw[t], t < 16, = the tile-local id of transcript t (0x8000 past
-//              the union); then float val[i][64], the i-th non-zero of fragment r at position r of row i, for i < the
-//              longest row of the slice.  (Every 32-bit word of a slice is a FINITE float -- ids < 128 or 0x8000 in the
-//              high halves: the dense streams' kernels read the rows behind a slice's last transcript from their LDS
-//              rings and multiply them by zero, and a ring may still hold a masked tile's bytes.)  Zeros cost no bytes: 4 B per non-zero + 4 B per
-//              fragment + padding to the slice's longest row -- never more than the dense union slice, and below CSR's
-//              8 B per non-zero + 4 B per fragment whatever the sets look like.  The kernel expands a fragment's values
-//              with its mask (rank = popcount of the lower bits) and runs the same matrix-core phases.
-//         A2  (dense, sets of 17..32): runs, remainders and union slices that are (almost) full.
-//         A2M (MASKED, unions of 17..32): the leftover rows that fit no union of 16 -- fragments of a gene with many
-//              isoforms.  Header: two rows of uint32 hw[64] (mask bits 0..15 / 16..31 in the low halves, the ids of
-//              transcripts 0..15 / 16..31 in the high halves of each row's first sixteen words); values as in A1M.
-//       BN, B = MIXED slices (float val[w][64]; uint16 lcol[w][64], 6 B per entry, any 64 fragments of the tile): the
-//              leftover rows that fit no uniform slice at CSR's cost or less -- unrelated fragments, fewer than a handful
-//              of which share any 32 transcripts.  BN: rows of <= 15 transcripts (with multiplicities a row float ks[64]
-//              follows, at the next multiple of 256 bytes), lane = fragment, gathers from / LDS adds into the tile's
-//              windows.
-//         One persistent launch (loglik_stream_kernel) streams these five: the usual sample needs no other.
-//              B: rows of more than 16 transcripts that found no uniform slice (more than 32, as a rule); the per-tile
-//              kernel loglik_psell_kernel takes them in a second launch.  That kernel also runs over all other slices
-//              on request (polee_debug_loglik_force_mixed): the independent second algorithm of the cross-check tests.
-//       C     = rows kept in CSR (u32 ids, f32 values, u32 row offsets: 8 B per non-zero + 4 B per row): fragments with no structure at all,
-//              whose mixed tiles would close on the dictionary before a slice is full -- the last resort that keeps
-//              the layout below CSR's size for ANY matrix; loglik_csr_kernel (lane = row, global gathers / atomics).
-//       S     = fragments compatible with ONE transcript (54 % of the rows of the reference's real-data fixture): not stored at
-//              all.  Such a fragment adds log(X_ij) + log(x_j) to the log-likelihood and 1 / x_j to transcript j's
-//              gradient (X_ij cancels: X_ij / (X_ij x_j)), ks_i times with multiplicities -- so the build keeps c_j = the
-//              number of such fragments per transcript (single_cnt) and the constant sum of log X_ij (single_logsum), and
-//              a pass adds c_j / x_j[k] and c_j log x_j[k] + const (single_rows_kernel): 4 B per TRANSCRIPT instead of
-//              8 B + a slice lane per fragment.
-//   * Each slice carries two flag bits (in the top bits of its offset word): "uniform" (its rows
-//     are stored under one transcript set) and "continues" (the same set as the previous slice).  Runs of such
-//     slices -- the bulk of real and synthetic data, where many fragments fall into the same
-//     equivalence class -- keep their gradient contributions in registers.
+//   * Rows are split into six streams, each a contiguous range of tiles, with three slice formats (compact, masked, mixed), and each
+//     slice carries its flags in the top bits of its offset word: psell_slice.hpp describes the streams and formats next to the code that
+//     implements them -- geometry, offset word, header words and the one decoder of the lane-by-lane readers.
 // HBM traffic per likelihood pass ~ 4.9 B/nnz at BASELINE's C2 (CSR: 8 B + row pointers), read once.
-// Two kernels decode ANY slice of these formats lane by lane: psell_tile_body (loglik.hip: stream B and the cross-check) and
-// em_g64_tiles_kernel (em.hip: the f64 gradient behind the EM fixed-point residual).  A change of a format goes into both.
 #pragma once
 #include "common.hpp"
+#include "psell_slice.hpp"
 
 namespace polee {
 
-constexpr int PSELL_LANES = 64;
 constexpr int PSELL_MAX_TILE_COLS = 1024;     // hard limit = longest supported row
 constexpr int PSELL_TILE_COLS_TARGET = 128;   // a tile is closed when its dictionary would grow past this
 constexpr int PSELL_DICT_ALIGN = 4;           // a tile's dictionary starts at a multiple of this many entries
@@ -75,19 +34,11 @@ constexpr int PSELL_TILE_SLICES_A1 = 64;      // slices per tile (= per workgrou
 constexpr int PSELL_TILE_SLICES_A2 = 32;     // (round 5: all four waves work on a wide tile -- 8 slices until then, for two)
 constexpr int PSELL_TILE_SLICES_B = 16;
 constexpr int PSELL_MAX_K = 8;
-constexpr uint32_t PSELL_OFF_MASK = 0x1fffffffu;  // slice_off entries carry the slice flags in bits 29..31
-constexpr uint32_t PSELL_FLAG_MASKED_BIT = 29;    // bit 29: a MASKED slice (set for every slice of streams A1M / A2M; the cross-check kernel reads it)
 constexpr int PSELL_NARROW_MAX = 16;        // widest transcript set of stream A1 (7 KiB LDS ring, four groups of four transcripts: narrow_stream)
 constexpr int PSELL_WIDE_MAX = 32;          // widest transcript set of streams A2 / A2M (two 16-row MFMA tiles: wide_stream, in two stages through the 7 KiB ring; A2M: 14 KiB rings)
-// Uniform slices store fragment r of transcript row t at this position of the row's 64 values, chosen per stream so that
-// the kernel's LDS operand reads are bank-conflict free: A1 (batched 4 x 4 outer products, narrow_stream) r ^ (t & 3);
-// A2 (16 x 16 x 4 tiles, wide_stream) a rotation by 4 t.
-enum : int { PSELL_A1 = 0, PSELL_A1M = 1, PSELL_A2 = 2, PSELL_A2M = 3, PSELL_BN = 4, PSELL_B = 5, PSELL_C = 6, PSELL_S = 7, PSELL_NSTREAMS = 8 };  // streams, in tile order (C and S have no tiles)
 constexpr int PSELL_MIXED_NARROW_MAX = 15;  // longest row of stream BN (its slices pass through the narrow streams' 7 KiB rings)
 constexpr int PSELL_TILE_SLICES_A2M = 16;
 constexpr int PSELL_TILE_SLICES_BN = 64;
-constexpr uint32_t psell_row_pos(int stream, uint32_t t, uint32_t r) { return stream == PSELL_A1 ? (r ^ (t & 3u)) : (stream == PSELL_A2 ? ((r + 4u * t) & 63u) : r); }
-constexpr uint16_t PSELL_NO_COL = 0x8000u;  // header entries of a masked slice past its union (0x8000xxxx is a finite float)
 // leftover rows are packed in independent chunks of this many candidates (host: a thread each; device: a WAVE each, whose walk is
 // bound by instruction latency -- a group is cut once per chunk.  2 048 since round 6 (4 096 before): polee_loglik_create 0.080 / 0.096 s
 // -> 0.073 / 0.084 s at C2 patterns / literal with the pass's time unchanged within run-to-run noise on the three inputs of
@@ -120,10 +71,8 @@ struct PsellHost {
     int64_t rows_a2 = 0, num_tiles_a2 = 0;    // A2 = [num_tiles_a1m, num_tiles_a2): dense wide; A2M = [num_tiles_a2, num_tiles_a): masked wide
     int64_t rows_s = 0, num_tiles_s = 0;      // BN = [num_tiles_a, num_tiles_s): mixed narrow -- [0, num_tiles_s) is the persistent launch's share; B = the rest
     int64_t stream_rows[PSELL_NSTREAMS] = {}, stream_nnz[PSELL_NSTREAMS] = {}, stream_bytes[PSELL_NSTREAMS] = {};
-    int stream_of_tile(int64_t t) const
-    {
-        return t < num_tiles_a1 ? PSELL_A1 : (t < num_tiles_a1m ? PSELL_A1M : (t < num_tiles_a2 ? PSELL_A2 : (t < num_tiles_a ? PSELL_A2M : (t < num_tiles_s ? PSELL_BN : PSELL_B))));
-    }
+    PsellTileBounds tile_bounds() const { return PsellTileBounds{(int)num_tiles_a1, (int)num_tiles_a1m, (int)num_tiles_a2, (int)num_tiles_a, (int)num_tiles_s}; }
+    int stream_of_tile(int64_t t) const { return psell_stream_of_tile(tile_bounds(), t); }
     int32_t max_row = 0, max_tile_cols = 0;
     std::vector<uint8_t, default_init_allocator<uint8_t>> data;  // slice blocks (resize(n) leaves new bytes uninitialised; resize(n, 0) zeroes)
     std::vector<uint32_t> slice_off;   // [num_slices+1], 128-byte units in bits 0..29, slice flags in bits 30..31

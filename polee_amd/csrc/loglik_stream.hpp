@@ -411,6 +411,7 @@ __device__ inline void slice_consumed(Advance &&advance, Stamps &st, int dbg)
 }
 
 // A slice's entry: e0 = its offset word (128-byte units in the low bits, the flags on top), e1 = the next slice's
+// (the slice loops below spell out "rows from units" and kind_of by hand; the format they restate is psell_slice.hpp's)
 struct SliceEntry {
     uint32_t units, bytes;
     int flags;  // bit 1: the slice continues the previous one's transcript set

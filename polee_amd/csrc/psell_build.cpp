@@ -575,12 +575,12 @@ std::string psell_stage2(int64_t m, int64_t n, const uint64_t *rowptr, const uin
                         nnz_t += len;
                         slice_w = std::max(slice_w, len);
                         if (++in_slice == (size_t)PSELL_LANES) {
-                            bytes += (slice_w * 384 + 255) & ~(size_t)255;
+                            bytes += psell_slice_geom(PSELL_B, false, (uint32_t)slice_w, false).bytes;
                             slice_w = in_slice = 0;
                         }
                         ++j;
                     }
-                    if (in_slice) bytes += (slice_w * 384 + 255) & ~(size_t)255;
+                    if (in_slice) bytes += psell_slice_geom(PSELL_B, false, (uint32_t)slice_w, false).bytes;
                     bytes += 4 * dict + 8;
                     if (bytes > 8 * nnz_t + 4 * (j - i))
                         rcsr.insert(rcsr.end(), lst->begin() + i, lst->begin() + j);
@@ -765,20 +765,26 @@ std::string psell_stage3(int64_t m, int64_t n, const uint64_t *rowptr, const uin
             w = (uint32_t)pattern.size();
         }
         const size_t base = out.data.size();
-        uint32_t stored_rows = w;  // rows of 64 values the slice stores
-        const bool masked_slice = cur_stream == PSELL_A1M || cur_stream == PSELL_A2M || (cur_stream == PSELL_A1 && slice_form == 2);
+        const bool masked_slice = psell_kind(cur_stream, slice_form == 2) == PSELL_MASKED;
+        const uint32_t stored_rows = masked_slice ? longest : w;  // rows of 64 values the slice stores
         const int stat_stream = masked_slice && cur_stream == PSELL_A1 ? PSELL_A1M : cur_stream;  // (accounting: by slice kind)
+        // the slice's bytes (psell_slice.hpp): zeroed, then -- with row multiplicities (factored likelihood) -- its last row float ks[64],
+        // so that they reach the kernel through the same stream as the values (stream B's slices have none)
+        const PsellSliceGeom G = psell_slice_geom(cur_stream, masked_slice, stored_rows, ks != nullptr);
+        out.data.resize(base + G.bytes, 0);
+        float *vals = reinterpret_cast<float *>(out.data.data() + base + G.val);
+        if (psell_has_ks_row(cur_stream, ks != nullptr)) {
+            float *kr = reinterpret_cast<float *>(out.data.data() + base + G.ks);
+            for (size_t lane = 0; lane < slice_rows.size(); ++lane) kr[lane] = (float)ks[slice_rows[lane]];
+        }
         if (masked_slice) {
             // masked slice: header rows of uint32 hw[64] -- one for unions of <= 16, two for 17..32: low half = bits
             // 0..15 (16..31) of the mask of the fragment in lane r; high half, r < 16: tile-local id of transcript r
             // (16 + r) of the union, PSELL_NO_COL past it -- then float val[i][64] = the i-th non-zero of the fragment in
-            // lane r, i < longest row (+ the ks row)
-            const size_t hrows = cur_stream == PSELL_A2M ? 2 : 1;
-            stored_rows = longest;
-            out.data.resize(base + 256 * hrows + (size_t)longest * 256 + (ks ? 256 : 0), 0);
-            uint32_t *hw = reinterpret_cast<uint32_t *>(out.data.data() + base);
-            float *vals = reinterpret_cast<float *>(out.data.data() + base + 256 * hrows);
-            for (uint32_t t = 0; t < 16u * hrows; ++t) hw[(t >> 4) * 64 + (t & 15)] = (uint32_t)(t < w ? col_local[pattern[t]] : PSELL_NO_COL) << 16;
+            // lane r, i < longest row
+            const uint32_t hrows = (uint32_t)psell_hdr_rows(cur_stream);
+            uint32_t *hw = reinterpret_cast<uint32_t *>(out.data.data() + base + G.hdr);
+            for (uint32_t t = 0; t < 16u * hrows; ++t) hw[psell_masked_id_slot(t)] = psell_masked_id_word(t < w ? col_local[pattern[t]] : PSELL_NO_COL);
             for (size_t lane = 0; lane < slice_rows.size(); ++lane) {
                 const uint64_t b = rowptr[slice_rows[lane]], e = rowptr[slice_rows[lane] + 1];
                 uint32_t t = 0, mk = 0;
@@ -787,25 +793,12 @@ std::string psell_stage3(int64_t m, int64_t n, const uint64_t *rowptr, const uin
                     mk |= 1u << t;
                     vals[(size_t)(k - b) * 64 + lane] = val[k];
                 }
-                hw[lane] |= mk & 0xffffu;
-                if (hrows == 2) hw[64 + lane] |= mk >> 16;
-            }
-            if (ks) {
-                float *kr = reinterpret_cast<float *>(out.data.data() + base + 256 * hrows + (size_t)longest * 256);
-                for (size_t lane = 0; lane < slice_rows.size(); ++lane) kr[lane] = (float)ks[slice_rows[lane]];
+                for (uint32_t h = 0; h < hrows; ++h) hw[64 * h + lane] |= psell_masked_mask_word(mk, h);
             }
         } else if (uniform_stream) {
             // dense uniform slice: the 64 fragments share one transcript set, so the column ids are stored once:
             //   uint16 lcol[128] (256-byte header, w used) ; float val[w][64] (rows rotated, see below)
-            // with row multiplicities (factored likelihood) a last row float ks[64] follows, so that they reach the
-            // kernel through the same stream as the values
-            out.data.resize(base + 256 + (size_t)w * 256 + (ks ? 256 : 0), 0);
-            if (ks) {
-                float *kr = reinterpret_cast<float *>(out.data.data() + base + 256 + (size_t)w * 256);
-                for (size_t lane = 0; lane < slice_rows.size(); ++lane) kr[lane] = (float)ks[slice_rows[lane]];
-            }
-            uint16_t *hdr = reinterpret_cast<uint16_t *>(out.data.data() + base);
-            float *vals = reinterpret_cast<float *>(out.data.data() + base + 256);
+            uint16_t *hdr = reinterpret_cast<uint16_t *>(out.data.data() + base + G.hdr);
             for (uint32_t t = 0; t < w; ++t) hdr[t] = col_local[pattern[t]];
             for (size_t lane = 0; lane < slice_rows.size(); ++lane) {
                 const uint64_t b = rowptr[slice_rows[lane]], e = rowptr[slice_rows[lane] + 1];
@@ -821,16 +814,8 @@ std::string psell_stage3(int64_t m, int64_t n, const uint64_t *rowptr, const uin
                 }
             }
         } else {
-            // mixed streams: float val[w][64]; uint16 lcol[w][64], padded to a multiple of 256 bytes; in stream BN with
-            // multiplicities a row float ks[64] follows
-            const size_t body = ((size_t)w * 384 + 255) & ~(size_t)255;
-            out.data.resize(base + body + (ks && cur_stream == PSELL_BN ? 256 : 0), 0);
-            if (ks && cur_stream == PSELL_BN) {
-                float *kr = reinterpret_cast<float *>(out.data.data() + base + body);
-                for (size_t lane = 0; lane < slice_rows.size(); ++lane) kr[lane] = (float)ks[slice_rows[lane]];
-            }
-            float *vals = reinterpret_cast<float *>(out.data.data() + base);
-            uint16_t *lcols = reinterpret_cast<uint16_t *>(out.data.data() + base + (size_t)w * 256);
+            // mixed streams: float val[w][64]; uint16 lcol[w][64], padded to a multiple of 256 bytes
+            uint16_t *lcols = reinterpret_cast<uint16_t *>(out.data.data() + base + G.lcol);
             for (size_t lane = 0; lane < slice_rows.size(); ++lane) {
                 const uint32_t r = slice_rows[lane];
                 const uint64_t b = rowptr[r], len = rowptr[r + 1] - b;
@@ -1054,7 +1039,7 @@ std::string psell_stage3(int64_t m, int64_t n, const uint64_t *rowptr, const uin
     if (out.data.size() / 128 >= (1ull << 29)) return "matrix too large (the slice stream is limited to 64 GiB)";
     // the two flag bits of slice s ride in the top bits of slice_off[s] (one scalar/lane load per slice)
     for (int64_t s = 0; s < out.num_slices; ++s)
-        out.slice_off[s] |= ((uint32_t)(out.slice_flags[s] & 3u) << 30) | ((uint32_t)((out.slice_flags[s] >> 2) & 1u) << PSELL_FLAG_MASKED_BIT);
+        out.slice_off[s] = psell_pack_off(out.slice_off[s], out.slice_flags[s]);
     return "";
 }
 

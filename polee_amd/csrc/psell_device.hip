@@ -497,17 +497,10 @@ __global__ __launch_bounds__(64) void s3_size_kernel(S3Size P)
             }
             if (uni) flags |= 1;
         }
-        const bool masked = st == PSELL_A1M || st == PSELL_A2M || (st == PSELL_A1 && form == 2);
+        const bool masked = psell_kind(st, form == 2) == PSELL_MASKED;
         if (masked) flags |= 4;
-        uint32_t bytes, stored = w;
-        if (masked) {
-            stored = longest;
-            bytes = 256u * (st == PSELL_A2M ? 2u : 1u) + longest * 256u + (P.has_ks ? 256u : 0u);
-        } else if (uniform) {
-            bytes = 256u + w * 256u + (P.has_ks ? 256u : 0u);
-        } else {
-            bytes = ((w * 384u + 255u) & ~255u) + (P.has_ks && st == PSELL_BN ? 256u : 0u);
-        }
+        const uint32_t stored = masked ? longest : w;  // rows of 64 values
+        const uint32_t bytes = psell_slice_geom(st, masked, stored, P.has_ks).bytes;
         P.sl_ri[s] = rs;
         P.sl_n[s] = nr;
         P.sl_units[s] = bytes / 128u;
@@ -559,7 +552,7 @@ __global__ __launch_bounds__(64) void s3_emit_kernel(S3Emit E)
     const uint32_t rs = E.sl_ri[s], nr = E.sl_n[s], longest = E.sl_long[s];
     const bool uniform = st <= PSELL_A2M;
     const uint32_t form = uniform ? E.A.form[rs] : 0u;
-    const bool masked = st == PSELL_A1M || st == PSELL_A2M || (st == PSELL_A1 && form == 2);
+    const bool masked = psell_kind(st, form == 2) == PSELL_MASKED;
     uint8_t *base = E.data + (size_t)E.slice_off[s] * 128u;
     const bool valid = lane < nr;
     const uint32_t r = valid ? E.A.rows[rs + lane] : 0u;
@@ -584,10 +577,12 @@ __global__ __launch_bounds__(64) void s3_emit_kernel(S3Emit E)
     }
     __syncthreads();
     const float ksv = E.A.ks && valid ? (float)E.A.ks[r] : 0.0f;
+    const PsellSliceGeom G = psell_slice_geom(st, masked, masked ? longest : w, E.A.ks != nullptr);
+    float *vals = reinterpret_cast<float *>(base + G.val);
+    if (psell_has_ks_row(st, E.A.ks != nullptr) && valid) reinterpret_cast<float *>(base + G.ks)[lane] = ksv;
     if (masked) {
-        const uint32_t hrows = st == PSELL_A2M ? 2u : 1u;
-        uint32_t *hw = reinterpret_cast<uint32_t *>(base);
-        float *vals = reinterpret_cast<float *>(base + 256u * hrows);
+        const uint32_t hrows = (uint32_t)psell_hdr_rows(st);
+        uint32_t *hw = reinterpret_cast<uint32_t *>(base + G.hdr);
         uint32_t mk = 0, tpos = 0;
         for (uint32_t k = 0; k < len; ++k) {
             const uint32_t c = E.A.col[b + k];
@@ -597,17 +592,15 @@ __global__ __launch_bounds__(64) void s3_emit_kernel(S3Emit E)
         }
         for (uint32_t h = 0; h < hrows; ++h) {
             uint32_t word = 0;
-            if (lane < 16) {
+            if (lane < 16) {  // (word psell_masked_id_slot(16 h + lane) = 64 h + lane)
                 const uint32_t tt = 16u * h + lane;
-                word = (uint32_t)(tt < w ? spat_local[tt] : (uint32_t)PSELL_NO_COL) << 16;
+                word = psell_masked_id_word(tt < w ? spat_local[tt] : (uint32_t)PSELL_NO_COL);
             }
-            if (valid) word |= h == 0 ? (mk & 0xffffu) : (mk >> 16);
+            if (valid) word |= psell_masked_mask_word(mk, h);
             hw[h * 64 + lane] = word;
         }
-        if (E.A.ks && valid) reinterpret_cast<float *>(base + 256u * hrows + (size_t)longest * 256u)[lane] = ksv;
     } else if (uniform) {
-        uint16_t *hdr = reinterpret_cast<uint16_t *>(base);
-        float *vals = reinterpret_cast<float *>(base + 256);
+        uint16_t *hdr = reinterpret_cast<uint16_t *>(base + G.hdr);
         if (lane < w) hdr[lane] = (uint16_t)spat_local[lane];
         if (valid) {
             if (form == 0) {
@@ -620,12 +613,9 @@ __global__ __launch_bounds__(64) void s3_emit_kernel(S3Emit E)
                     vals[(size_t)tpos * 64 + psell_row_pos(st, tpos, lane)] = E.A.val[b + k];
                 }
             }
-            if (E.A.ks) reinterpret_cast<float *>(base + 256 + (size_t)w * 256u)[lane] = ksv;
         }
     } else {
-        const size_t body = ((size_t)w * 384 + 255) & ~(size_t)255;
-        float *vals = reinterpret_cast<float *>(base);
-        uint16_t *lcols = reinterpret_cast<uint16_t *>(base + (size_t)w * 256);
+        uint16_t *lcols = reinterpret_cast<uint16_t *>(base + G.lcol);
         if (valid) {
             uint16_t last = 0;
             for (uint32_t tt = 0; tt < w; ++tt) {
@@ -635,7 +625,6 @@ __global__ __launch_bounds__(64) void s3_emit_kernel(S3Emit E)
                 }
                 lcols[(size_t)tt * 64 + lane] = last;
             }
-            if (E.A.ks && st == PSELL_BN) reinterpret_cast<float *>(base + body)[lane] = ksv;
         }
     }
     if (E.row_order) E.row_order[(size_t)s * 64 + lane] = valid ? r : 0xffffffffu;
@@ -646,7 +635,7 @@ __global__ void s3_flags_kernel(uint32_t S, const uint8_t *slice_flags, uint32_t
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
-    slice_off[s] |= ((uint32_t)(slice_flags[s] & 3u) << 30) | ((uint32_t)((slice_flags[s] >> 2) & 1u) << PSELL_FLAG_MASKED_BIT);
+    slice_off[s] = psell_pack_off(slice_off[s], slice_flags[s]);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------

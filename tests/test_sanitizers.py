@@ -2,7 +2,8 @@
 builder, csc_to_csr's partitioned transposition and hclust.cpp's two tree builders -- the rounds variant merges on all host
 threads under striped spin locks -- compiled host-only with -fsanitize=address,undefined and with -fsanitize=thread
 (polee_amd/csrc/Makefile, target sanitize-build) and driven by tests/san/host_builders_main.cpp over four kinds of matrices
-with and without multiplicities.  No GPU is touched."""
+with and without multiplicities; the driver also decodes every slice of every layout on the host through PsellSliceReader
+(csrc/psell_slice.hpp, the reader of the device decoders) and holds it against the input matrix.  No GPU is touched."""
 import os
 import subprocess
 
