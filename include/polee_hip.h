@@ -932,6 +932,63 @@ polee_status polee_effects_run(polee_effects *fx, const float *qw_loc, const flo
                                const float *zw_or_null, int64_t zw_len, float *min_effect_sizes, float *mean_effect_sizes, float *prob_de,
                                float *aitchison_min, float *aitchison_mean, float *aitchison_prob_de, double *kernel_ms_or_null);
 
+/* ---- `polee model tsne` (models/tsne.jl:52-99, models/polee_tsne.py:17-185, :213-398; csrc/tsne.hip) -------
+ * Parametric t-SNE of log expression: z = lx W, W f32 [n][C], zero at creation (the caller sets W0, :293-298); lx = log of one draw
+ * per sample from the fitted approximations, drawn afresh at every evaluation, no gradient through it; with the *_points entries
+ * lx = x f32 [S][n], log expression already (must be finite: POLEE_ERR_NONFINITE).  The bias of the reference's embedding stays at
+ * zero: the loss sees z through differences only, its exact gradient is zero.
+ *   delta_ab = sum_j (lx_aj - lx_bj)^2 / n - (mean_a - mean_b)^2 (pairwise_vlr, :17-26); use_vlr = 0: sum_j (lx_aj - lx_bj)^2 (:42-48)
+ *   on a batch I of B sample indices, in order (tsne_p, :136-174): E_ab = clip(exp(-delta_ab / (2 sigma_b^2)), 1e-12, 1), E_aa = 0,
+ *     P = (E_ab / sum_a E_ab + E_ba / sum_b E_ba) / (2 S) + eps
+ *   on ALL samples (tsne_q, :177-185): k_ij = (1 + |z_i - z_j|^2 / alpha)^(-(alpha + 1) / 2), k_ii = 0, Q = k / sum k, gathered to
+ *     I x I, + eps
+ *   loss = sum_{a,b in I} P_ab log(P_ab / Q_ab) (:337); samples outside the batch get a gradient through sum k.
+ * The draws never leave the device; every sum has a fixed order (no float atomics): every result is bitwise reproducible.
+ * Draw rule: the draw with index i uses seed + 0x9E3779B97F4A7C15 i.  polee_tsne_fit: i = t - 1 for Adam step t of the handle's step
+ * clock, which runs on across calls, so fit(2) then fit(3) equals fit(5); polee_tsne_distances and polee_tsne_eval: i = 0;
+ * polee_tsne_embed: i = its own draw number.
+ * POLEE_ERR_BAD_ARG: a batch index outside 0 .. S-1 or repeated within a batch, B < 2 or B > S, bandwidths not set or not positive,
+ * an `ap` of another context, n or S. */
+typedef struct polee_tsne polee_tsne;
+typedef struct {
+    int32_t num_components; /* C, --num-components, 2 (tsne.jl:23-27) */
+    int32_t use_vlr;        /* 1 (tsne.jl:94) */
+    float alpha;            /* 1 (polee_tsne.py:218) */
+    float eps;              /* 1e-6, added to P and to Q (:309, :319, :327) */
+    float learning_rate;    /* 1e-6 (:344) */
+    float beta1, beta2, epsilon; /* tf.train.AdamOptimizer: 0.99, 0.999 (:344-345), 1e-8 */
+} polee_tsne_opts;
+void polee_tsne_default_opts(polee_tsne_opts *opts);
+/* 1 <= num_components <= 16, anything else POLEE_ERR_UNSUPPORTED; opts NULL = the defaults (estimate_tsne, :213-218) */
+polee_status polee_tsne_create(polee_ctx *ctx, int32_t n, int32_t S, const polee_tsne_opts *opts, polee_tsne **out);
+void polee_tsne_destroy(polee_tsne *ts);
+/* W f32 [n][C] (:293-296); set leaves the Adam moments and the step clock alone */
+polee_status polee_tsne_get_params(polee_tsne *ts, float *w);
+polee_status polee_tsne_set_params(polee_tsne *ts, const float *w);
+/* Adam moments and step clock back to zero (a fresh optimiser, :344-347) */
+polee_status polee_tsne_reset(polee_tsne *ts);
+/* the bandwidths of find_sigmas (:64-103, :238), f32 [S], positive and finite */
+polee_status polee_tsne_set_sigmas(polee_tsne *ts, const float *sigmas);
+/* delta f64 [S][S] of one draw (what find_sigmas works on, :238); exactly symmetric, diagonal exactly 0; z0_or_null f32 [S][n-1] */
+polee_status polee_tsne_distances(polee_tsne *ts, polee_approx *ap, const float *z0_or_null, uint64_t seed, double *delta);
+polee_status polee_tsne_distances_points(polee_tsne *ts, const float *x, double *delta);
+/* the loss (:337) of one evaluation on the batch i32 [B] and its gradient g_w f32 [n][C] (may be NULL), no update: exactly the
+ * numbers a fit step feeds to Adam (the same kernels in the same order) */
+polee_status polee_tsne_eval(polee_tsne *ts, polee_approx *ap, const int32_t *batch, int32_t B, const float *z0_or_null, uint64_t seed,
+                             float *loss, float *g_w);
+polee_status polee_tsne_eval_points(polee_tsne *ts, const float *x, const int32_t *batch, int32_t B, float *loss, float *g_w);
+/* niter Adam steps (:355-390), step `it` on the batch batches[it] (i32 [niter][B]): lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t),
+ * p -= lr_t m / (sqrt(v) + epsilon).  z0_or_null f32 [niter][S][n-1], uploaded once; loss_trace_or_null f32 [niter].  Nothing waits
+ * for the device until the last step is queued.  A call that fails partway keeps the updates of the steps it completed and advances
+ * the clock by those. */
+polee_status polee_tsne_fit(polee_tsne *ts, polee_approx *ap, const int32_t *batches, int32_t B, int32_t niter, uint64_t seed,
+                            const float *z0_or_null, float *loss_trace_or_null);
+polee_status polee_tsne_fit_points(polee_tsne *ts, const float *x, const int32_t *batches, int32_t B, int32_t niter,
+                                   float *loss_trace_or_null);
+/* the mean over ndraws draws of z = lx W (:392-395), accumulated in f64; z0_or_null f32 [ndraws][S][n-1]; z f32 [S][C] */
+polee_status polee_tsne_embed(polee_tsne *ts, polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0_or_null, float *z);
+polee_status polee_tsne_embed_points(polee_tsne *ts, const float *x, float *z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1411,6 +1411,112 @@ function predict(cl::LogisticRegression, x::Vector{Float32}, S::Integer)
     return probs
 end
 
+# ---- `polee model tsne` (models/tsne.jl:52-99, models/polee_tsne.py:213-398): parametric t-SNE on posterior draws ------------------
+"mirror of `polee_tsne_opts` (include/polee_hip.h): field order and types must stay in step with the header"
+mutable struct TSNEOpts
+    num_components::Int32; use_vlr::Int32
+    alpha::Float32; eps::Float32; learning_rate::Float32
+    beta1::Float32; beta2::Float32; epsilon::Float32
+    function TSNEOpts()
+        o = new()
+        ccall((:polee_tsne_default_opts, LIB), Cvoid, (Ref{TSNEOpts},), o)
+        return o
+    end
+end
+
+"the embedding z = lx W of estimate_tsne (polee_tsne.py:293-298); matrices are row-major vectors: W [n*C] (transcript by transcript),
+z [S*C] (sample by sample), delta [S*S]; batches hold 0-based sample indices"
+mutable struct TSNE
+    h::Ptr{Cvoid}
+    ctx::Context
+    n::Int
+    S::Int
+    C::Int
+end
+function TSNE(ctx::Context, n::Integer, S::Integer; opts::TSNEOpts=TSNEOpts())
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:polee_tsne_create, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ref{TSNEOpts}, Ref{Ptr{Cvoid}}), ctx.h, n, S, opts, r), ctx.h)
+    ts = TSNE(r[], ctx, n, S, opts.num_components)
+    finalizer(x -> ccall((:polee_tsne_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), ts)
+    return ts
+end
+function get_params(ts::TSNE)
+    w = Vector{Float32}(undef, ts.n * ts.C)
+    GC.@preserve w check(ccall((:polee_tsne_get_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), ts.h, w), ts.ctx.h)
+    return w
+end
+function set_params!(ts::TSNE, w::Vector{Float32})
+    GC.@preserve w check(ccall((:polee_tsne_set_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), ts.h, w), ts.ctx.h)
+end
+"Adam moments and step clock back to zero"
+reset!(ts::TSNE) = check(ccall((:polee_tsne_reset, LIB), Cint, (Ptr{Cvoid},), ts.h), ts.ctx.h)
+"the bandwidths of find_sigmas (polee_tsne.py:64-103), [S]"
+function set_sigmas!(ts::TSNE, sigmas::Vector{Float32})
+    GC.@preserve sigmas check(ccall((:polee_tsne_set_sigmas, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), ts.h, sigmas), ts.ctx.h)
+end
+"delta [S*S] of one draw (pairwise_vlr, polee_tsne.py:17-26)"
+function distances(ts::TSNE, ap::ApproxLikelihood; seed::Integer=0, z0::Union{Nothing,Vector{Float32}}=nothing)
+    delta = Vector{Float64}(undef, ts.S * ts.S)
+    GC.@preserve z0 delta check(
+        ccall((:polee_tsne_distances, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, UInt64, Ptr{Float64}),
+              ts.h, ap.h, z0 === nothing ? C_NULL : pointer(z0), seed, delta), ts.ctx.h)
+    return delta
+end
+"delta [S*S] of a fixed x [S*n]"
+function distances(ts::TSNE, x::Vector{Float32})
+    delta = Vector{Float64}(undef, ts.S * ts.S)
+    GC.@preserve x delta check(ccall((:polee_tsne_distances_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float64}), ts.h, x, delta),
+                               ts.ctx.h)
+    return delta
+end
+"the loss (polee_tsne.py:337) of one evaluation on `batch` and its gradient (loss, g_w [n*C]); no update"
+function loss_and_gradient(ts::TSNE, ap::ApproxLikelihood, batch::Vector{Int32}; seed::Integer=0,
+                           z0::Union{Nothing,Vector{Float32}}=nothing)
+    loss = Ref{Float32}(0)
+    gw = Vector{Float32}(undef, ts.n * ts.C)
+    GC.@preserve batch z0 gw check(
+        ccall((:polee_tsne_eval, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Float32}, UInt64, Ref{Float32}, Ptr{Float32}),
+              ts.h, ap.h, batch, length(batch), z0 === nothing ? C_NULL : pointer(z0), seed, loss, gw), ts.ctx.h)
+    return loss[], gw
+end
+function loss_and_gradient(ts::TSNE, x::Vector{Float32}, batch::Vector{Int32})
+    loss = Ref{Float32}(0)
+    gw = Vector{Float32}(undef, ts.n * ts.C)
+    GC.@preserve x batch gw check(
+        ccall((:polee_tsne_eval_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}, Int32, Ref{Float32}, Ptr{Float32}),
+              ts.h, x, batch, length(batch), loss, gw), ts.ctx.h)
+    return loss[], gw
+end
+"niter Adam steps on fresh draws (polee_tsne.py:355-375), step i on batches[(i-1)*B+1 : i*B]: the loss trace"
+function fit!(ts::TSNE, ap::ApproxLikelihood, batches::Vector{Int32}, B::Integer, niter::Integer; seed::Integer=0,
+              z0::Union{Nothing,Vector{Float32}}=nothing)
+    trace = Vector{Float32}(undef, niter)
+    GC.@preserve batches z0 trace check(
+        ccall((:polee_tsne_fit, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Int32, UInt64, Ptr{Float32}, Ptr{Float32}),
+              ts.h, ap.h, batches, B, niter, seed, z0 === nothing ? C_NULL : pointer(z0), trace), ts.ctx.h)
+    return trace
+end
+function fit!(ts::TSNE, x::Vector{Float32}, batches::Vector{Int32}, B::Integer, niter::Integer)
+    trace = Vector{Float32}(undef, niter)
+    GC.@preserve x batches trace check(
+        ccall((:polee_tsne_fit_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}, Int32, Int32, Ptr{Float32}),
+              ts.h, x, batches, B, niter, trace), ts.ctx.h)
+    return trace
+end
+"the mean of z over ndraws draws (polee_tsne.py:392-395), [S*C]"
+function embed(ts::TSNE, ap::ApproxLikelihood, ndraws::Integer; seed::Integer=0, z0::Union{Nothing,Vector{Float32}}=nothing)
+    z = Vector{Float32}(undef, ts.S * ts.C)
+    GC.@preserve z0 z check(
+        ccall((:polee_tsne_embed, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt64, Ptr{Float32}, Ptr{Float32}),
+              ts.h, ap.h, ndraws, seed, z0 === nothing ? C_NULL : pointer(z0), z), ts.ctx.h)
+    return z
+end
+function embed(ts::TSNE, x::Vector{Float32})
+    z = Vector{Float32}(undef, ts.S * ts.C)
+    GC.@preserve x z check(ccall((:polee_tsne_embed_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), ts.h, x, z), ts.ctx.h)
+    return z
+end
+
 # ---- isoform effect sizes (estimate_isoform_effect_sizes, src/regression.jl:761-945; csrc/effects.hip) -----------------------------
 "the transcripts of `gene_of` (0-based gene of every transcript, any order) segmented by gene once, on creation"
 mutable struct IsoformEffects

@@ -21,6 +21,7 @@
 // There are no float atomics: every sum has a fixed order, so results are bitwise reproducible.
 // Parameters, moments and accumulators share one flat layout: wT [k][n] | x_bias [n] | z_bias [k] (the ABI speaks w [n][k]).
 #include "common.hpp"
+#include "wave.hpp"  // wave_split_reduce
 
 #include <cmath>
 
@@ -30,26 +31,6 @@ constexpr int CL_BLOCK = 256;
 constexpr int CL_WAVE_J = 128;  // transcripts per chunk of the logits kernel: one wave, two per lane
 constexpr int CL_TILE_S = 64;   // samples whose dl the gradient kernel stages in LDS at a time
 constexpr uint64_t CL_DRAW_STRIDE = 0x9E3779B97F4A7C15ull;  // draw i uses seed + stride * i (as polee_approx_feature_moments)
-
-// p[0..KP) per lane -> the wave's sums: afterwards p[0] of every lane holds the sum of class lane / (64 / KP).  Halving exchange: at
-// every step a lane keeps half of its values and receives its partner's partial of those, so KP - 1 + log2(64 / KP) shuffles in all.
-template <int KP>
-__device__ inline void wave_split_reduce(float (&p)[KP], int lane)
-{
-#pragma unroll
-    for (int h = KP / 2; h >= 1; h >>= 1) {
-        const int off = 64 * h / KP;
-        const bool up = (lane & off) != 0;
-#pragma unroll
-        for (int c = 0; c < h; ++c) {
-            const float send = up ? p[c] : p[c + h];
-            const float keep = up ? p[c + h] : p[c];
-            p[c] = keep + __shfl_xor(send, off, 64);
-        }
-    }
-#pragma unroll
-    for (int off = 32 / KP; off >= 1; off >>= 1) p[0] += __shfl_xor(p[0], off, 64);
-}
 
 // part [nchunks][S][k]; abs_part [nchunks] or null: sum |w| of the chunk (the L1 term of the loss, once per step)
 template <int KP>

@@ -58,4 +58,25 @@ __device__ inline void wave_sum_to_lane63_n(float (&v)[N])
     for (int i = 0; i < N; ++i) v[i] = dpp_add<0x143, 0xc, 0xf>(v[i]);
 }
 
+// ---- KP sums at once with shuffles (classify.hip, tsne.hip) --------------------------------------
+// p[0..KP) per lane -> the wave's sums: afterwards p[0] of every lane holds the sum of class lane / (64 / KP).  Halving exchange: at
+// every step a lane keeps half of its values and receives its partner's partial of those, so KP - 1 + log2(64 / KP) shuffles in all.
+template <int KP>
+__device__ inline void wave_split_reduce(float (&p)[KP], int lane)
+{
+#pragma unroll
+    for (int h = KP / 2; h >= 1; h >>= 1) {
+        const int off = 64 * h / KP;
+        const bool up = (lane & off) != 0;
+#pragma unroll
+        for (int c = 0; c < h; ++c) {
+            const float send = up ? p[c] : p[c + h];
+            const float keep = up ? p[c + h] : p[c];
+            p[c] = keep + __shfl_xor(send, off, 64);
+        }
+    }
+#pragma unroll
+    for (int off = 32 / KP; off >= 1; off >>= 1) p[0] += __shfl_xor(p[0], off, 64);
+}
+
 }  // namespace polee
