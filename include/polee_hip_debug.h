@@ -98,6 +98,12 @@ polee_status polee_debug_fast_log(polee_ctx *ctx, const double *x, int64_t count
 /* fast_exp (csrc/scan.hpp), the double-precision exp of the VI loop's forward kernel (leaf u = exp of a path sum of edge logs) */
 polee_status polee_debug_fast_exp(polee_ctx *ctx, const double *x, int64_t count, double *out);
 
+/* Draws per workgroup of the VI loop's forward and backward tree kernels (csrc/vi_fused.hpp, DrawSplit) for the steps that follow:
+ * num_mc_samples, or 3, 2, 1 where that is below it; 0 = the library's own choice.  Every split computes the same bits
+ * (tests/test_gpu_vi_draw_split.py); the library's choice is the fastest one measured.  The update kernel has no split (a lane per
+ * node and draw was slower): dpw_update must be 0 or num_mc_samples. */
+polee_status polee_vi_debug_set_draw_split(polee_vi *vi, int32_t dpw_fwd, int32_t dpw_bwd, int32_t dpw_update);
+
 /* The Gibbs sampler's last sweep, chain `chain`: z i32 [m] = the 1-based transcript each fragment was assigned (original fragment
  * order; 0 = a fragment with no compatible transcript).  Recomputed by the assignment kernel on the state that sweep started from. */
 polee_status polee_debug_gibbs_assignments(polee_gibbs *g, int32_t chain, int32_t *z);

@@ -20,6 +20,7 @@
 #include "sampler_internal.hpp"
 
 #include <cmath>
+#include <type_traits>
 
 namespace polee {
 
@@ -208,9 +209,35 @@ struct polee_vi {
     DevBuf<double> d_ygrad, d_xgrad_rows;
     DevBuf<float> d_mug, d_omg, d_alg, d_x_rows;
 
+    // draws per workgroup of the forward and the backward kernel (DrawSplit, vi_fused.hpp); 0 = the production choice
+    // (draw_split_default), another value only through the test hook polee_vi_debug_set_draw_split
+    int32_t dpw_fwd = 0, dpw_bwd = 0;
+
     NoiseSrc noise() const { return NoiseSrc{d_z0.p, o.seed, K, (int64_t)n - 1}; }
     polee_status one_step(bool apply, bool want_values, bool hook_outputs);
 };
+
+// The instantiated draw splits of K draws are {K, 3, 2, 1} (those below K).  Production runs one per kernel (0 forward, 1 backward)
+// and K, chosen by measurement at C2 (EXPERIMENTS.md, "Draw split"): only the backward kernel at K = 6 gained from a split; the
+// others exist for the tests.
+static inline int draw_split_default(int K, int kernel)
+{
+    return kernel == 1 && K == 6 ? 2 : K;
+}
+static inline bool draw_split_offered(int K, int dpw) { return dpw == K || (dpw >= 1 && dpw <= 3 && dpw < K); }
+// f(std::integral_constant<int, DPW>) for the run-time dpw (a value that is not offered runs DPW = K)
+template <int K, typename F>
+static inline void with_draw_split(int dpw, F &&f)
+{
+    if (dpw == 3 && K > 3)
+        f(std::integral_constant<int, (K > 3 ? 3 : K)>{});
+    else if (dpw == 2 && K > 2)
+        f(std::integral_constant<int, (K > 2 ? 2 : K)>{});
+    else if (dpw == 1 && K > 1)
+        f(std::integral_constant<int, 1>{});
+    else
+        f(std::integral_constant<int, K>{});
+}
 
 template <int K>
 static polee_status vi_step_k(polee_vi *vi, bool apply, bool want_values, bool hook_outputs)
@@ -259,23 +286,28 @@ static polee_status vi_step_k(polee_vi *vi, bool apply, bool want_values, bool h
     } else {
         POLEE_HIP_TRY(ctx, hipMemsetAsync(chunk_f, 0, sizeof(VK<K>), st));
     }
-    if (want_values) {
-        hipLaunchKernelGGL((vi_fwd_apply_kernel<K, YRows, float, true>), dim3(nch_f), dim3(SCAN_THREADS), 0, st, lview, ysrc, chunk_f,
+    // (draws per workgroup: the production choice of draw_split_default, or the test hook's)
+    const int dpw_f = vi->dpw_fwd ? vi->dpw_fwd : draw_split_default(K, 0);
+    const int dpw_b = vi->dpw_bwd ? vi->dpw_bwd : draw_split_default(K, 1);
+    static const bool sib_far = getenv("POLEE_VI_SPLIT_CONSECUTIVE") != nullptr;  // (A/B: the siblings' placement, DrawSplit::block)
+    const bool sib_near = !sib_far;
+    auto fwd_apply = [&](auto ladj, auto dpw) {
+        constexpr bool LADJ = decltype(ladj)::value;
+        constexpr int DPW = decltype(dpw)::value;
+        const int sib = sib_near ? draw_split_sib(nch_f) : 0;
+        hipLaunchKernelGGL((vi_fwd_apply_kernel<K, YRows, float, LADJ, DPW>), dim3(DrawSplit<K, DPW>::grid(nch_f, sib)), dim3(SCAN_THREADS), 0, st,
+                           lview, ysrc, chunk_f,
                            vi->d_u32.p, vi->d_x.p, vi->d_g.p, eff, (float)o.y_eps, (float)(1.0 - o.y_eps),
                            eff ? vi->d_part_c.p : nullptr, want_values ? vi->d_part_ladj.p : nullptr, nch_f > 1 ? own_f : 0,
                            (const uint32_t *)vi->d_open_ptr.p, (const uint32_t *)vi->d_open_code.p,
                            xwin_here ? (const uint32_t *)vi->ll->d_tslot_ptr.p : nullptr, xwin_here ? (const uint32_t *)vi->ll->d_tslot.p : nullptr,
                            xwin_here ? vi->ll->d_xwin.p : nullptr,
-                           remap && remap->singles_in_g ? (const float *)vi->d_single_leaf.p : nullptr);
-    } else {
-        hipLaunchKernelGGL((vi_fwd_apply_kernel<K, YRows, float, false>), dim3(nch_f), dim3(SCAN_THREADS), 0, st, lview, ysrc, chunk_f,
-                           vi->d_u32.p, vi->d_x.p, vi->d_g.p, eff, (float)o.y_eps, (float)(1.0 - o.y_eps),
-                           eff ? vi->d_part_c.p : nullptr, want_values ? vi->d_part_ladj.p : nullptr, nch_f > 1 ? own_f : 0,
-                           (const uint32_t *)vi->d_open_ptr.p, (const uint32_t *)vi->d_open_code.p,
-                           xwin_here ? (const uint32_t *)vi->ll->d_tslot_ptr.p : nullptr, xwin_here ? (const uint32_t *)vi->ll->d_tslot.p : nullptr,
-                           xwin_here ? vi->ll->d_xwin.p : nullptr,
-                           remap && remap->singles_in_g ? (const float *)vi->d_single_leaf.p : nullptr);
-    }
+                           remap && remap->singles_in_g ? (const float *)vi->d_single_leaf.p : nullptr, nch_f, sib);
+    };
+    if (want_values)
+        with_draw_split<K>(dpw_f, [&](auto dpw) { fwd_apply(std::true_type{}, dpw); });
+    else
+        with_draw_split<K>(dpw_f, [&](auto dpw) { fwd_apply(std::false_type{}, dpw); });
     POLEE_KERNEL_CHECK(ctx);
     // likelihood
     if (want_values) POLEE_HIP_TRY(ctx, hipMemsetAsync(vi->d_lp.p, 0, sizeof(double) * PSELL_MAX_K, st));
@@ -336,7 +368,11 @@ static polee_status vi_step_k(polee_vi *vi, bool apply, bool want_values, bool h
         VD<K> *chunk_bu = reinterpret_cast<VD<K> *>(vi->d_chunk_bu.p);
         const BwdArgs<K> ba{lview, vi->d_u32.p, vi->d_g.p, eff, vi->d_csum.p, gp, chunk_bu, vi->d_C.p, (const uint32_t *)vi->d_need.p,
                             (const int32_t *)vi->d_node_start.p, vi->d_H.p};
-        hipLaunchKernelGGL((vi_bwd_local_kernel<K>), dim3(nch_bu), dim3(256), 0, st, ba);
+        with_draw_split<K>(dpw_b, [&](auto dpw) {
+            constexpr int DPW = decltype(dpw)::value;
+            const int sib = sib_near ? draw_split_sib(nch_bu) : 0;
+            hipLaunchKernelGGL((vi_bwd_local_kernel<K, DPW>), dim3(DrawSplit<K, DPW>::grid(nch_bu, sib)), dim3(256), 0, st, ba, nch_bu, sib);
+        });
         if (nm1 > 0) {
             hipLaunchKernelGGL((vi_bwd_spine_kernel<K>), dim3(1), dim3(64 * K), 0, st, chunk_bu, nch_bu);
             hipLaunchKernelGGL((vi_update_k_kernel<K, NoiseSrc>), dim3((unsigned)ceil_div(nm1, 256)), dim3(256), 0, st, view,
@@ -581,6 +617,13 @@ polee_status polee_vi_create(polee_loglik *ll, polee_ptt *t, const float *efflen
     vi->o = o;
     vi->n = t->n;
     vi->K = o.num_mc_samples;
+    if (const char *e = getenv("POLEE_VI_DRAW_SPLIT")) {  // (A/B: "fwd,bwd" draws per workgroup; a value not offered = the default)
+        int f = 0, b = 0;
+        if (sscanf(e, "%d,%d", &f, &b) == 2) {
+            vi->dpw_fwd = draw_split_offered(vi->K, f) ? f : 0;
+            vi->dpw_bwd = draw_split_offered(vi->K, b) ? b : 0;
+        }
+    }
     ll->profile = o.profile != 0;
     ll->prof_every = o.profile > 1 ? o.profile : 1;
     // (opts.deterministic belongs to THIS fit: applied around its likelihood passes, the handle's own setting restored)
@@ -866,6 +909,20 @@ polee_status polee_debug_vi_stamps(unsigned long long *out)
 }
 #endif
 
+polee_status polee_vi_debug_set_draw_split(polee_vi *vi, int32_t dpw_fwd, int32_t dpw_bwd, int32_t dpw_update)
+{
+    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
+    for (int32_t dpw : {dpw_fwd, dpw_bwd})
+        if (dpw != 0 && !draw_split_offered(vi->K, dpw))
+            return fail(vi->ctx, POLEE_ERR_BAD_ARG, "draw split %d of %d draws is not instantiated (0, %d, or 3, 2, 1 below it)", dpw, vi->K, vi->K);
+    // (the update kernel has no split: a lane per node and draw was slower at every DPW and is not kept, EXPERIMENTS.md)
+    if (dpw_update != 0 && dpw_update != vi->K)
+        return fail(vi->ctx, POLEE_ERR_BAD_ARG, "the update kernel runs all %d draws of a node on one lane: dpw_update must be 0 or %d", vi->K, vi->K);
+    vi->dpw_fwd = dpw_fwd;
+    vi->dpw_bwd = dpw_bwd;
+    return POLEE_OK;
+}
+
 polee_status polee_vi_export_noise(polee_vi *vi, int32_t step, float *z0)
 {
     if (!vi || !z0 || step < 1) return fail(nullptr, POLEE_ERR_BAD_ARG, "bad argument");
@@ -958,7 +1015,7 @@ polee_status polee_optimize_ptt(polee_loglik *ll, polee_ptt *t, const float *eff
         hipLaunchKernelGGL((vi_fwd_apply_kernel<1, LogRows, double, false>), dim3(nch_f), dim3(SCAN_THREADS), 0, st, view, LogRows{vi->d_lyy.p}, chunk_f,
                            vi->d_uleaf.p, vi->d_x.p, vi->d_g.p, vi->d_efflens.p, (float)o.y_eps, (float)(1.0 - o.y_eps),
                            vi->d_part_c.p, (double *)nullptr, 0, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, (float *)nullptr, (const float *)nullptr);
+                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, (float *)nullptr, (const float *)nullptr, nch_f, 0);
         POLEE_KERNEL_CHECK(ctx);
         return POLEE_OK;
     };

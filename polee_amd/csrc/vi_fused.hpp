@@ -101,6 +101,46 @@ struct ScanOps<VD<K>> {
     }
 };
 
+// Draw split.  The K draws are independent until the update takes their mean, so the tree kernels can hand them to more, shorter
+// workgroups: a workgroup of vi_fwd_apply_kernel / vi_bwd_local_kernel owns the DPW draws [d0, d0 + DPW) of its chunk (grid:
+// chunks x NG, NG = ceil(K / DPW)).  DPW = K is the geometry without a split (d0 = 0 at compile time).  Where DPW does not
+// divide K the last group's surplus draws LOAD draw K - 1 again (ld) and store nothing (on): every array keeps its [..][K]
+// layout, a workgroup writes its own draw columns.  Measured at C2 (EXPERIMENTS.md D1): the backward kernel gains from
+// DPW = 2, the forward kernel from none; the update kernel (a thread per node, all draws) has no split -- a lane per node and
+// draw was slower.
+template <int K, int DPW>
+struct DrawSplit {
+    static_assert(DPW >= 1 && DPW <= K, "draws per workgroup");
+    static constexpr int NG = (K + DPW - 1) / DPW;
+    static constexpr bool REM = K % DPW != 0;
+    __device__ static inline int ld(int d0, int dl) { return REM ? min(d0 + dl, K - 1) : d0 + dl; }
+    __device__ static inline bool on(int d0, int dl) { return !REM || d0 + dl < K; }
+    // block index -> (chunk, first draw).  sib == 0: the NG siblings of a chunk are consecutive blocks (consecutive blocks go to
+    // different XCDs); sib > 0 (the chunk count rounded up to a multiple of 8): siblings are sib blocks apart, on one XCD, whose
+    // L2 then serves the 128-byte lines of the [..][K] rows they share.  false: a filler block past the last chunk.
+    __device__ static inline bool block(int nch, int sib, int &chunk, int &d0)
+    {
+        if constexpr (NG == 1) {
+            chunk = blockIdx.x;
+            d0 = 0;
+            return true;
+        } else {
+            int grp;
+            if (sib) {
+                grp = blockIdx.x / sib;
+                chunk = blockIdx.x - grp * sib;
+            } else {
+                chunk = blockIdx.x / NG;
+                grp = blockIdx.x - chunk * NG;
+            }
+            d0 = grp * DPW;
+            return chunk < nch;
+        }
+    }
+    static inline unsigned grid(int nch, int sib) { return (unsigned)(NG == 1 ? nch : (sib ? sib : nch) * NG); }
+};
+inline int draw_split_sib(int nch) { return (nch + 7) / 8 * 8; }
+
 // Block-wide sums of K doubles per thread (256 threads).  smem must hold 4*K doubles; results valid in
 // threads 0..K-1 as out (and for every thread after the trailing barrier through smem[0..K-1]).
 template <int K>
@@ -206,12 +246,12 @@ struct LogRows {
     const double *lyy;
     template <int K>
     __device__ inline double edge_one(uint32_t k, uint32_t left, int d) const { return lyy[((size_t)k * 2 + left) * K + d]; }
-    template <int K>
-    __device__ inline void edge(uint32_t k, uint32_t left, double (&e)[K]) const
+    template <int K, int DPW>
+    __device__ inline void edge(uint32_t k, uint32_t left, int d0, double (&e)[DPW]) const
     {
         const double *p = lyy + ((size_t)k * 2 + left) * K;
 #pragma unroll
-        for (int d = 0; d < K; ++d) e[d] = p[d];
+        for (int d = 0; d < DPW; ++d) e[d] = p[DrawSplit<K, DPW>::ld(d0, d)];
     }
 };
 struct YRows {
@@ -223,14 +263,14 @@ struct YRows {
         const double y = clamped_y_pos(y32[(size_t)k * K + d], y_eps, 1.0 - y_eps);
         return fast_log_pos(left ? y : 1.0 - y);
     }
-    template <int K>
-    __device__ inline void edge(uint32_t k, uint32_t left, double (&e)[K]) const
+    template <int K, int DPW>
+    __device__ inline void edge(uint32_t k, uint32_t left, int d0, double (&e)[DPW]) const
     {
         const float *p = y32 + (size_t)k * K;
         const double hi = 1.0 - y_eps;
 #pragma unroll
-        for (int d = 0; d < K; ++d) {
-            const double y = clamped_y_pos(p[d], y_eps, hi);
+        for (int d = 0; d < DPW; ++d) {
+            const double y = clamped_y_pos(p[DrawSplit<K, DPW>::ld(d0, d)], y_eps, hi);
             e[d] = fast_log_pos(left ? y : 1.0 - y);  // (log1p(-y): y is clamped to [eps, 1 - eps], both arguments normal and positive)
         }
     }
@@ -243,20 +283,20 @@ constexpr int FWD_ITEMS = 2;
 constexpr int FWD_CHUNK = SCAN_THREADS * FWD_ITEMS;
 inline int fwd_num_chunks(int64_t len) { return (int)((len + FWD_CHUNK - 1) / FWD_CHUNK); }
 
-template <int K, typename Src>
-__device__ inline VK<K> tour_value(uint32_t code, const Src &src, VK<K> &edge)
+template <int K, int DPW, typename Src>
+__device__ inline VK<DPW> tour_value(uint32_t code, const Src &src, int d0, VK<DPW> &edge)
 {
     // edge = log of this entry's edge factor (0 for the root); value = +edge on ENTER, -edge on EXIT, 0 on LEAF
-    VK<K> val;
+    VK<DPW> val;
     const uint32_t type = code & 3u;
     if (code & 4u) {
 #pragma unroll
-        for (int d = 0; d < K; ++d) edge.v[d] = 0.0;
+        for (int d = 0; d < DPW; ++d) edge.v[d] = 0.0;
     } else {
-        src.template edge<K>(code >> 4, (code >> 3) & 1u, edge.v);
+        src.template edge<K, DPW>(code >> 4, (code >> 3) & 1u, d0, edge.v);
     }
 #pragma unroll
-    for (int d = 0; d < K; ++d) val.v[d] = type == TOUR_ENTER ? edge.v[d] : (type == TOUR_EXIT ? -edge.v[d] : 0.0);
+    for (int d = 0; d < DPW; ++d) val.v[d] = type == TOUR_ENTER ? edge.v[d] : (type == TOUR_EXIT ? -edge.v[d] : 0.0);
     return val;
 }
 
@@ -281,7 +321,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_reduce_kernel(PttView v, 
     VK<K> acc = ScanOps<VK<K>>::zero(), edge;
 #pragma unroll
     for (int j = 0; j < FWD_ITEMS; ++j)
-        if (base + j < v.TL) acc = ScanOps<VK<K>>::add(acc, tour_value<K, Src>(v.tour_code[base + j], lyy, edge));
+        if (base + j < v.TL) acc = ScanOps<VK<K>>::add(acc, tour_value<K, K, Src>(v.tour_code[base + j], lyy, 0, edge));
     VK<K> tot;
     (void)block_exclusive_scan<VK<K>>(acc, smem, &tot);
     if (threadIdx.x == 0) chunk_sums[blockIdx.x] = tot;
@@ -293,7 +333,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_reduce_kernel(PttView v, 
 // forward apply: leaves get u = exp(prefix + own edge); x = clamp(max(f32(u), 1e-16)) (ptt.jl:138-139,
 // likelihood-approximation.jl:526) written to xs[tid][K]; g[tid][K] is zeroed for the likelihood pass;
 // per-chunk partial sums of x/efflen (likelihood.jl:97-100) and, if wanted, of log u over internal nodes.
-template <int K, typename Src, typename UT, bool LADJ>
+// (the offset sums of chunk_prefix for the workgroup's own draws: chunk_sums is [chunks][K])
+template <int K, int DPW>
+__device__ inline VK<DPW> chunk_prefix_draws(const VK<K> *__restrict__ chunk_sums, int chunk, int d0, VK<DPW> *smem)
+{
+    VK<DPW> acc = ScanOps<VK<DPW>>::zero();
+    for (int i = threadIdx.x; i < chunk; i += SCAN_THREADS)
+#pragma unroll
+        for (int d = 0; d < DPW; ++d) acc.v[d] = acc.v[d] + chunk_sums[i].v[DrawSplit<K, DPW>::ld(d0, d)];
+    VK<DPW> tot;
+    (void)block_exclusive_scan<VK<DPW>>(acc, smem, &tot);
+    return tot;
+}
+
+// DPW: draws per workgroup (DrawSplit).  Grid: chunks x ceil(K / DPW); nch = the number of chunks, sib = the siblings' placement.
+template <int K, typename Src, typename UT, bool LADJ, int DPW = K>
 __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, Src lyy,
                                                                    const VK<K> *__restrict__ chunk_offsets,
                                                                    UT *__restrict__ uleaf, float *__restrict__ xs,
@@ -306,28 +360,31 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
                                                                    const uint32_t *__restrict__ tslot_ptr,
                                                                    const uint32_t *__restrict__ tslot,
                                                                    float *__restrict__ xwin,
-                                                                   const float *__restrict__ single_cnt)
+                                                                   const float *__restrict__ single_cnt, int nch, int sib)
 {
-    __shared__ VK<K> smem[SCAN_THREADS / 64];
-    __shared__ double smd[4 * K];
-    __shared__ double spre[K];  // the chunk's offset from the open-edge list
-    __shared__ double smd2[LADJ ? 4 * K : 1];
+    using DS = DrawSplit<K, DPW>;
+    __shared__ VK<DPW> smem[SCAN_THREADS / 64];
+    __shared__ double smd[4 * DPW];
+    __shared__ double spre[DPW];  // the chunk's offset from the open-edge list
+    __shared__ double smd2[LADJ ? 4 * DPW : 1];
     // x windows of the sparse pass (loglik_internal.hpp): a transcript's x row also goes to its slot in every tile
     // dictionary that holds it (tslot lists) -- the gather launch in front of the pass is gone.  A thread writes up to
     // XW_INLINE slots itself; transcripts in more tiles are written by the whole workgroup afterwards.
     constexpr int XW_INLINE = 12, XW_DEFER = 48;
     __shared__ uint32_t xw_tid[XW_DEFER];
-    __shared__ float xw_val[XW_DEFER][K];
+    __shared__ float xw_val[XW_DEFER][DPW];
     __shared__ int xw_count;
+    int chunk, d0;
+    if (!DS::block(nch, sib, chunk, d0)) return;  // (the whole workgroup)
     if (xwin && threadIdx.x == 0) xw_count = 0;
     if (xwin) __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * FWD_CHUNK + (int64_t)threadIdx.x * FWD_ITEMS;
+    const int64_t base = (int64_t)chunk * FWD_CHUNK + (int64_t)threadIdx.x * FWD_ITEMS;
     // The kernel is bound by its dependent memory round trips, not by arithmetic: every load whose address does not depend on
     // another load is issued here, in front of the first barrier (the compiler does not move loads across one).
     //   trip 1: the thread's tour entries (code, target) and the bounds of the chunk's open-edge list
     //   trip 2: the entries' edge logs (lyy rows), the list's codes, the leaves' effective lengths / single counts
     //   trip 3: the open edges' logs
-    VK<K> w[FWD_ITEMS];  // the entries' edge logs: +w on ENTER, -w on EXIT in the scan; a LEAF adds it to its prefix
+    VK<DPW> w[FWD_ITEMS];  // the entries' edge logs: +w on ENTER, -w on EXIT in the scan; a LEAF adds it to its prefix
     uint32_t code[FWD_ITEMS];
     int tgt[FWD_ITEMS];
 #pragma unroll
@@ -339,20 +396,20 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
     const int lane = threadIdx.x & 63;
     uint32_t ob = 0, oe = 0;
     if (open_ptr) {
-        ob = open_ptr[blockIdx.x];
-        oe = open_ptr[blockIdx.x + 1];
+        ob = open_ptr[chunk];
+        oe = open_ptr[chunk + 1];
     }
     // (the list is the path from the root, rarely longer than a wave: every wave takes the entries' codes and sums the edge logs
-    // of ITS draws -- wave w the draws w, w + 4 -- so the K double logs per entry are spread over the four waves; the sums go to
-    // LDS in front of the scan's barriers)
+    // of ITS draws -- wave w the workgroup's draws w, w + 4 -- so the double logs per entry are spread over the four waves; the
+    // sums go to LDS in front of the scan's barriers)
     const int wave = threadIdx.x >> 6;
     const uint32_t ocode0 = ob + lane < oe ? open_code[ob + lane] : (4u | TOUR_LEAF);
-    VK<K> acc = ScanOps<VK<K>>::zero();
+    VK<DPW> acc = ScanOps<VK<DPW>>::zero();
     float inv_l_[FWD_ITEMS], sc_[FWD_ITEMS];
     int ltid[FWD_ITEMS];
 #pragma unroll
     for (int j = 0; j < FWD_ITEMS; ++j) {
-        acc = ScanOps<VK<K>>::add(acc, tour_value<K, Src>(code[j], lyy, w[j]));  // (past the end: a root LEAF, 0)
+        acc = ScanOps<VK<DPW>>::add(acc, tour_value<K, DPW, Src>(code[j], lyy, d0, w[j]));  // (past the end: a root LEAF, 0)
         const bool leaf = (code[j] & 3u) == TOUR_LEAF && base + j < v.TL;
         // (leaf-order mode, v.leaf_tid == null: the fit numbers the transcripts by leaf position, so xs, g, efflens
         // and single_cnt are indexed by pos and a chunk's leaves write one contiguous piece of each)
@@ -369,9 +426,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
         // path from the root to that point, a list fixed by the tree (open_ptr / open_code, built once per fit): with it the
         // forward pass needs no reduce launch and no pass over the other chunks' totals.
 #pragma unroll
-        for (int dd_ = 0; dd_ < (K + 3) / 4; ++dd_) {
-            const int d = wave + 4 * dd_;  // (wave-uniform)
-            if (d < K) {
+        for (int dd_ = 0; dd_ < (DPW + 3) / 4; ++dd_) {
+            const int dl = wave + 4 * dd_;  // (wave-uniform)
+            if (dl < DPW) {
+                const int d = DS::ld(d0, dl);
                 // (ENTER codes: + the edge's log; the filler is a root LEAF: 0)
                 double pre = (ocode0 & 4u) ? 0.0 : lyy.template edge_one<K>(ocode0 >> 4, (ocode0 >> 3) & 1u, d);
                 for (uint32_t e = ob + 64 + lane; e < oe; e += 64) {
@@ -379,32 +437,39 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
                     pre += lyy.template edge_one<K>(oc >> 4, (oc >> 3) & 1u, d);
                 }
                 pre = wave_inclusive_scan<double>(pre);  // (DPP: the wave's sum lands in its last lane)
-                if (lane == 63) spre[d] = pre;
+                if (lane == 63) spre[dl] = pre;
             }
         }
     }
     VI_STAMP(0, 2);
-    VK<K> tot;
-    VK<K> off = block_exclusive_scan<VK<K>>(acc, smem, &tot);
+    VK<DPW> tot;
+    VK<DPW> off = block_exclusive_scan<VK<DPW>>(acc, smem, &tot);
     VI_STAMP(0, 3);
     // Without the lists (very deep trees): chunk_offsets holds the chunks' exclusive offsets (after a spine pass) or, with
     // own_prefix, their totals.
     if (open_ptr) {
 #pragma unroll
-        for (int d = 0; d < K; ++d) off.v[d] += spre[d];  // (written in front of the scan's barriers)
+        for (int d = 0; d < DPW; ++d) off.v[d] += spre[d];  // (written in front of the scan's barriers)
     } else {
-        off = ScanOps<VK<K>>::add(own_prefix ? chunk_prefix<VK<K>>(chunk_offsets, blockIdx.x, smem) : chunk_offsets[blockIdx.x], off);
-    }
-    double pc[K], pl[K];
+        VK<DPW> co;
+        if (own_prefix) {
+            co = chunk_prefix_draws<K, DPW>(chunk_offsets, chunk, d0, smem);
+        } else {
 #pragma unroll
-    for (int d = 0; d < K; ++d) pc[d] = pl[d] = 0.0;
+            for (int d = 0; d < DPW; ++d) co.v[d] = chunk_offsets[chunk].v[DS::ld(d0, d)];
+        }
+        off = ScanOps<VK<DPW>>::add(co, off);
+    }
+    double pc[DPW], pl[DPW];
+#pragma unroll
+    for (int d = 0; d < DPW; ++d) pc[d] = pl[d] = 0.0;
 #pragma unroll
     for (int j = 0; j < FWD_ITEMS; ++j) {
         const uint32_t tj = code[j] & 3u;
         // (the running prefix is advanced in place: + the edge's log on ENTER, - on EXIT, unchanged by a LEAF)
 #pragma unroll
-        for (int d = 0; d < K; ++d) off.v[d] = tj == TOUR_ENTER ? off.v[d] + w[j].v[d] : (tj == TOUR_EXIT ? off.v[d] - w[j].v[d] : off.v[d]);
-        const VK<K> &inc = off;
+        for (int d = 0; d < DPW; ++d) off.v[d] = tj == TOUR_ENTER ? off.v[d] + w[j].v[d] : (tj == TOUR_EXIT ? off.v[d] - w[j].v[d] : off.v[d]);
+        const VK<DPW> &inc = off;
         if (base + j < v.TL) {
             const uint32_t type = code[j] & 3u;
             if (type == TOUR_LEAF) {
@@ -412,15 +477,19 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
                 const int tid = ltid[j];
                 const float inv_l = inv_l_[j];
                 const float sc = sc_[j];
+                float xv[DPW];
 #pragma unroll
-                for (int d = 0; d < K; ++d) {
+                for (int d = 0; d < DPW; ++d) {
                     const double u = fast_exp(inc.v[d] + w[j].v[d]);
-                    uleaf[(size_t)pos * K + d] = (UT)u;
                     float x = (float)u;
                     x = (float)fmax((double)x, 1e-16);
                     x = fminf(fmaxf(x, clamp_lo), clamp_hi);
-                    xs[(size_t)tid * K + d] = x;
-                    g[(size_t)tid * K + d] = sc != 0.0f ? sc / x : 0.0f;
+                    xv[d] = x;
+                    if (DS::on(d0, d)) {
+                        uleaf[(size_t)pos * K + d0 + d] = (UT)u;
+                        xs[(size_t)tid * K + d0 + d] = x;
+                        g[(size_t)tid * K + d0 + d] = sc != 0.0f ? sc / x : 0.0f;
+                    }
                     pc[d] += (double)(x * inv_l);  // xls[i] = xs[i] / efflens[i] in f32 (likelihood.jl:97)
                 }
                 if (xwin) {
@@ -430,18 +499,19 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
                     if (q >= 0 && q < XW_DEFER) {
                         xw_tid[q] = (uint32_t)tid;
 #pragma unroll
-                        for (int d = 0; d < K; ++d) xw_val[q][d] = xs[(size_t)tid * K + d];
+                        for (int d = 0; d < DPW; ++d) xw_val[q][d] = xv[d];
                     } else {
                         for (uint32_t e = sb; e < se; ++e) {
-                            float *w = xwin + (size_t)tslot[e] * K;
+                            float *w = xwin + (size_t)tslot[e] * K + d0;
 #pragma unroll
-                            for (int d = 0; d < K; ++d) w[d] = xs[(size_t)tid * K + d];
+                            for (int d = 0; d < DPW; ++d)
+                                if (DS::on(d0, d)) w[d] = xv[d];
                         }
                     }
                 }
             } else if (LADJ && type == TOUR_ENTER) {
 #pragma unroll
-                for (int d = 0; d < K; ++d) pl[d] += inc.v[d];
+                for (int d = 0; d < DPW; ++d) pl[d] += inc.v[d];
             }
         }
     }
@@ -450,9 +520,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
         const int cnt = min(xw_count, XW_DEFER);
         for (int q = 0; q < cnt; ++q) {
             const uint32_t tid = xw_tid[q], sb = tslot_ptr[tid], se = tslot_ptr[tid + 1];
-            for (uint32_t e = sb * K + threadIdx.x; e < se * K; e += SCAN_THREADS) {
-                const uint32_t slot = e / K, d = e - slot * K;
-                xwin[(size_t)tslot[slot] * K + d] = xw_val[q][d];
+            for (uint32_t e = sb * DPW + threadIdx.x; e < se * DPW; e += SCAN_THREADS) {
+                const uint32_t slot = e / DPW, d = e - slot * DPW;
+                if (DS::on(d0, (int)d)) xwin[(size_t)tslot[slot] * K + d0 + d] = xw_val[q][d];
             }
         }
     }
@@ -460,19 +530,19 @@ __global__ __launch_bounds__(SCAN_THREADS) void vi_fwd_apply_kernel(PttView v, S
     // the chunk's partial sums: a wave's 64 values by a DPP scan, the four waves' through LDS in wave order -- one barrier
     if (part_c || LADJ) {
 #pragma unroll
-        for (int d = 0; d < K; ++d) {
+        for (int d = 0; d < DPW; ++d) {
             const double a = wave_inclusive_scan<double>(pc[d]);  // (DPP: the wave's sum lands in its last lane)
             const double b = LADJ ? wave_inclusive_scan<double>(pl[d]) : 0.0;
             if (lane == 63) {
-                smd[wave * K + d] = a;
-                if (LADJ) smd2[wave * K + d] = b;
+                smd[wave * DPW + d] = a;
+                if (LADJ) smd2[wave * DPW + d] = b;
             }
         }
         __syncthreads();
-        if ((int)threadIdx.x < K) {
+        if ((int)threadIdx.x < DPW && DS::on(d0, (int)threadIdx.x)) {
             const int d = threadIdx.x;
-            if (part_c) part_c[(size_t)blockIdx.x * K + d] = ((smd[d] + smd[K + d]) + smd[2 * K + d]) + smd[3 * K + d];
-            if (LADJ) part_ladj[(size_t)blockIdx.x * K + d] = ((smd2[d] + smd2[K + d]) + smd2[2 * K + d]) + smd2[3 * K + d];
+            if (part_c) part_c[(size_t)chunk * K + d0 + d] = ((smd[d] + smd[DPW + d]) + smd[2 * DPW + d]) + smd[3 * DPW + d];
+            if (LADJ) part_ladj[(size_t)chunk * K + d0 + d] = ((smd2[d] + smd2[DPW + d]) + smd2[2 * DPW + d]) + smd2[3 * DPW + d];
         }
     }
     VI_STAMP(0, 5);
@@ -798,11 +868,12 @@ __global__ __launch_bounds__(256) void vi_csum_finish_kernel(const double *__res
     csum_finish_block<K>(part_c, nparts, out, smd);
 }
 
-// a = u * x_grad at leaf position pos (bwd_values with the reciprocal of sum x / efflen at hand)
-template <int K>
+// a = u * x_grad at leaf position pos (bwd_values with the reciprocal of sum x / efflen at hand), draws [d0, d0 + DPW): c, inv_c
+// and a are indexed by the draw's place in the group
+template <int K, int DPW>
 __device__ inline void bwd_leaf(const PttView &v, int64_t pos, const float *__restrict__ uleaf, const float *__restrict__ g,
                                 const float *__restrict__ efflens, const double *c, const double *inv_c, const GenePrior &gp,
-                                double (&a)[K])
+                                int d0, double (&a)[DPW])
 {
     const int tid = v.leaf_tid ? v.leaf_tid[pos] : (int)pos;  // (leaf-order mode: see vi_fwd_apply_kernel)
     const float inv_lf = efflens ? 1.0f / efflens[tid] : 0.0f;
@@ -813,15 +884,16 @@ __device__ inline void bwd_leaf(const PttView &v, int64_t pos, const float *__re
         kg = gene >= 0 ? gp.gene_k[gene] : 0;
     }
 #pragma unroll
-    for (int d = 0; d < K; ++d) {
+    for (int dl = 0; dl < DPW; ++dl) {
+        const int d = DrawSplit<K, DPW>::ld(d0, dl);
         double xg = (double)g[(size_t)tid * K + d];
-        if (efflens) xg -= (double)nl * inv_c[d];
+        if (efflens) xg -= (double)nl * inv_c[dl];
         if (gp.gene_of) {
-            const double cc = c[d], inv_l = (double)inv_lf;
+            const double cc = c[dl], inv_l = (double)inv_lf;
             const double xlg = kg > 1 ? -(double)(kg - 1) / gp.gene_c[(size_t)gene * K + d] : 0.0;
             xg += xlg * (inv_l / cc) + inv_l * (gp.M / (cc * cc));
         }
-        a[d] = (double)uleaf[(size_t)pos * K + d] * xg;
+        a[dl] = (double)uleaf[(size_t)pos * K + d] * xg;
     }
 }
 
@@ -831,33 +903,39 @@ __device__ inline dd two_sum(double a, double b)
     return dd{s, (a - (s - bb)) + (b - bb)};
 }
 
-template <int K>
-__global__ __launch_bounds__(256) void vi_bwd_local_kernel(BwdArgs<K> B)
+// DPW: draws per workgroup (DrawSplit).  Grid: chunks x ceil(K / DPW).  The chunk size, the crossing nodes, node_start and the
+// need bits do not depend on DPW; a workgroup builds the prefix of its own draws (LDS: (CH + 1) DPW 16 B) and writes its own
+// draw columns of H, C and the chunk totals.
+template <int K, int DPW = K>
+__global__ __launch_bounds__(256) void vi_bwd_local_kernel(BwdArgs<K> B, int nch, int sib)
 {
+    using DS = DrawSplit<K, DPW>;
     constexpr int CH = bu_ch<K>(), LPT = CH / 256;
-    __shared__ dd P[(CH + 1) * K];
-    __shared__ VD<K> wtot[4];
+    __shared__ dd P[(CH + 1) * DPW];
+    __shared__ VD<DPW> wtot[4];
     const PttView &v = B.v;
+    int chunk, d0;
+    if (!DS::block(nch, sib, chunk, d0)) return;  // (the whole workgroup)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double c[K], inv_c[K];
+    double c[DPW], inv_c[DPW];
 #pragma unroll
-    for (int d = 0; d < K; ++d) {
-        c[d] = B.efflens ? B.csum[d] : 1.0;
-        inv_c[d] = B.efflens ? B.csum[K + d] : 1.0;
+    for (int d = 0; d < DPW; ++d) {
+        c[d] = B.efflens ? B.csum[DS::ld(d0, d)] : 1.0;
+        inv_c[d] = B.efflens ? B.csum[K + DS::ld(d0, d)] : 1.0;
     }
     VI_STAMP(1, 0);
-    const int64_t base = (int64_t)blockIdx.x * CH, p0 = base + (int64_t)threadIdx.x * LPT;
+    const int64_t base = (int64_t)chunk * CH, p0 = base + (int64_t)threadIdx.x * LPT;
     const int64_t end = min(base + CH, (int64_t)v.n), nm1 = (int64_t)v.n - 1;
     const bool exp0 = p0 <= v.n && ((B.need[p0 >> 5] >> (p0 & 31)) & 1u);
     const bool exp1 = LPT == 2 && p0 + 1 <= v.n && ((B.need[(p0 + 1) >> 5] >> ((p0 + 1) & 31)) & 1u);
-    double a[LPT][K];
+    double a[LPT][DPW];
 #pragma unroll
     for (int j = 0; j < LPT; ++j) {
         if (p0 + j < v.n)
-            bwd_leaf<K>(v, p0 + j, B.uleaf, B.g, B.efflens, c, inv_c, B.gp, a[j]);
+            bwd_leaf<K, DPW>(v, p0 + j, B.uleaf, B.g, B.efflens, c, inv_c, B.gp, d0, a[j]);
         else
 #pragma unroll
-            for (int d = 0; d < K; ++d) a[j][d] = 0.0;
+            for (int d = 0; d < DPW; ++d) a[j][d] = 0.0;
     }
     // (the first nodes' ranges are loaded here, in front of the barriers -- the node phase then starts without a memory round
     // trip -- and BEHIND the leaves' loads: loads return in order, and these wait for node_start first)
@@ -865,7 +943,7 @@ __global__ __launch_bounds__(256) void vi_bwd_local_kernel(BwdArgs<K> B)
     // (node_start through the vector memory path -- a lane-dependent zero in the index: a scalar load would stall the wave
     // on its counter in front of the leaves' arithmetic)
     const uint32_t vz = threadIdx.x >> 12;
-    const int32_t k0 = B.node_start[blockIdx.x + vz] + (int32_t)threadIdx.x, k1 = B.node_start[blockIdx.x + 1 + vz];
+    const int32_t k0 = B.node_start[chunk + vz] + (int32_t)threadIdx.x, k1 = B.node_start[chunk + 1 + vz];
     int32_t kp[PRE];
     int plo[PRE], pmid[PRE], phi[PRE];
 #pragma unroll
@@ -876,41 +954,41 @@ __global__ __launch_bounds__(256) void vi_bwd_local_kernel(BwdArgs<K> B)
         pmid[i] = in ? v.mid[kp[i]] : 0;
         phi[i] = in ? v.hi1[kp[i]] : 0;
     }
-    VD<K> s;
+    VD<DPW> s;
 #pragma unroll
-    for (int d = 0; d < K; ++d) {
+    for (int d = 0; d < DPW; ++d) {
         s.v[d] = dd_make(a[0][d]);
         if constexpr (LPT == 2) s.v[d] = two_sum(a[0][d], a[1][d]);
     }
     VI_STAMP(1, 1);
-    const VD<K> inc = wave_inclusive_scan<VD<K>>(s);
+    const VD<DPW> inc = wave_inclusive_scan<VD<DPW>>(s);
     VI_STAMP(1, 2);
     if (lane == 63) wtot[wave] = inc;
     __syncthreads();
-    VD<K> off = wave_shift_up_one<VD<K>>(inc);
-    for (int w = 0; w < wave; ++w) off = ScanOps<VD<K>>::add(wtot[w], off);  // (wave-uniform trip count)
+    VD<DPW> off = wave_shift_up_one<VD<DPW>>(inc);
+    for (int w = 0; w < wave; ++w) off = ScanOps<VD<DPW>>::add(wtot[w], off);  // (wave-uniform trip count)
 #pragma unroll
-    for (int d = 0; d < K; ++d) P[(size_t)(threadIdx.x * LPT) * K + d] = off.v[d];
+    for (int d = 0; d < DPW; ++d) P[(size_t)(threadIdx.x * LPT) * DPW + d] = off.v[d];
     if (exp0)
 #pragma unroll
-        for (int d = 0; d < K; ++d) B.C[(size_t)p0 * K + d] = off.v[d];
+        for (int d = 0; d < DPW; ++d)
+            if (DS::on(d0, d)) B.C[(size_t)p0 * K + d0 + d] = off.v[d];
     if constexpr (LPT == 2) {
         const int64_t p1 = p0 + 1;
 #pragma unroll
-        for (int d = 0; d < K; ++d) {
+        for (int d = 0; d < DPW; ++d) {
             const dd o1 = dd_add(off.v[d], dd_make(a[0][d]));
-            P[(size_t)(threadIdx.x * LPT + 1) * K + d] = o1;
-            if (exp1) B.C[(size_t)p1 * K + d] = o1;
+            P[(size_t)(threadIdx.x * LPT + 1) * DPW + d] = o1;
+            if (exp1 && DS::on(d0, d)) B.C[(size_t)p1 * K + d0 + d] = o1;
         }
     }
     if (threadIdx.x == 255) {  // the chunk's total = the last thread's inclusive prefix
-        VD<K> tot;
 #pragma unroll
-        for (int d = 0; d < K; ++d) {
-            tot.v[d] = dd_add(off.v[d], s.v[d]);
-            P[(size_t)CH * K + d] = tot.v[d];
+        for (int d = 0; d < DPW; ++d) {
+            const dd tot = dd_add(off.v[d], s.v[d]);
+            P[(size_t)CH * DPW + d] = tot;
+            if (DS::on(d0, d)) B.chunk_tot[chunk].v[d0 + d] = tot;
         }
-        B.chunk_tot[blockIdx.x] = tot;
     }
     VI_STAMP(1, 3);
     __syncthreads();
@@ -918,12 +996,14 @@ __global__ __launch_bounds__(256) void vi_bwd_local_kernel(BwdArgs<K> B)
     // the nodes whose range starts in this chunk and ends in it: both subtree sums from LDS rows
     auto node = [&](int32_t k, int lo, int mid, int hi1) {
         if (hi1 > end) return;  // crosses chunks: the update adds chunk offsets to exported rows
-        const dd *Plo = P + (size_t)(lo - base) * K, *Pmid = P + (size_t)(mid - base) * K, *Phi = P + (size_t)(hi1 - base) * K;
+        const dd *Plo = P + (size_t)(lo - base) * DPW, *Pmid = P + (size_t)(mid - base) * DPW, *Phi = P + (size_t)(hi1 - base) * DPW;
 #pragma unroll
-        for (int d = 0; d < K; ++d) {
+        for (int d = 0; d < DPW; ++d) {
             const dd pm = Pmid[d];
-            B.H[(size_t)d * nm1 + k] = (float)dd_diff(pm, Plo[d]);
-            B.H[(size_t)(K + d) * nm1 + k] = (float)dd_diff(Phi[d], pm);
+            if (DS::on(d0, d)) {
+                B.H[(size_t)(d0 + d) * nm1 + k] = (float)dd_diff(pm, Plo[d]);
+                B.H[(size_t)(K + d0 + d) * nm1 + k] = (float)dd_diff(Phi[d], pm);
+            }
         }
     };
 #pragma unroll
