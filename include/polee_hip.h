@@ -989,6 +989,61 @@ polee_status polee_tsne_fit_points(polee_tsne *ts, const float *x, const int32_t
 polee_status polee_tsne_embed(polee_tsne *ts, polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0_or_null, float *z);
 polee_status polee_tsne_embed_points(polee_tsne *ts, const float *x, float *z);
 
+/* ---- `polee model random-forest` (models/random-forest.jl; csrc/forest.hip, csrc/forest_host.cpp, csrc/forest_common.hpp; DESIGN.md
+ * section 3.14): a classification forest on log expression, grown level by level for all trees at once on the device.  The forest is
+ * this project's own exact definition (integers, Philox counters and correctly rounded f64 additions only): the device builder, the
+ * host builder below and the NumPy restatement of the tests give the same node arrays bit for bit.
+ * x f32 [N][n] is log expression already and must be finite (POLEE_ERR_NONFINITE); labels are class numbers in 0 .. k-1.
+ * A forest is ntrees trees in CSR form: tree t owns the nodes tree_off[t] .. tree_off[t+1]-1 of the five node arrays, numbered level
+ * by level from its root 0; left / right are node numbers within the tree (-1 in a leaf), feature is -1 in a leaf, label is the
+ * majority class of the node's rows (smallest class on a tie) in every node, threshold is 0 in a leaf.  A row goes left iff
+ * (double)x[feature] < threshold.
+ * A tree's bootstrap sample has N_b = max(1, floor(partial_sampling N)) rows; N_b > POLEE_FOREST_MAX_ROWS: POLEE_ERR_UNSUPPORTED. */
+#define POLEE_FOREST_MAX_ROWS 8192
+typedef struct polee_forest polee_forest;
+typedef struct {
+    int32_t ntrees;            /* 200 (random-forest.jl:40-43) */
+    int32_t max_depth;         /* -1: no limit */
+    int32_t min_samples_leaf;  /* 1 */
+    int32_t min_samples_split; /* 2 */
+    double nsubfeatures;       /* 10: nsub = max(1, min(n, round-half-even(nsubfeatures sqrt(n)))) (:44-47, :262) */
+    double partial_sampling;   /* 1 (:48-51) */
+} polee_forest_opts;
+void polee_forest_default_opts(polee_forest_opts *opts);
+/* 2 <= k <= 16, anything else POLEE_ERR_UNSUPPORTED; opts NULL = the defaults */
+polee_status polee_forest_create(polee_ctx *ctx, int32_t n, int32_t k, const polee_forest_opts *opts, polee_forest **out);
+void polee_forest_destroy(polee_forest *f);
+polee_status polee_forest_fit_points(polee_forest *f, const float *x, const int32_t *labels, int32_t N, uint64_t seed);
+/* Training rows are the logs of ndraws draws of every sample of `ap`: row d S + s is draw d of sample s (draw d uses draw_seed +
+ * 0x9E3779B97F4A7C15 d; z0_or_null f32 [ndraws][S][n-1]) and carries labels[s]; `seed` keys the forest. */
+polee_status polee_forest_fit(polee_forest *f, polee_approx *ap, const int32_t *labels, int32_t ndraws, uint64_t draw_seed,
+                              uint64_t seed, const float *z0_or_null);
+polee_status polee_forest_node_count(polee_forest *f, int32_t *ntrees, int64_t *nnodes);
+/* tree_off i64 [ntrees+1]; the node arrays [nnodes] */
+polee_status polee_forest_get_nodes(polee_forest *f, int64_t *tree_off, int32_t *feature, double *threshold, int32_t *left,
+                                    int32_t *right, int32_t *label);
+/* Loads a forest built elsewhere (the host builder, a hand-made one).  Checked: every child lies in its tree and after its parent,
+ * features in -1 .. n-1, labels in 0 .. k-1, a node has two children or none (else POLEE_ERR_BAD_ARG). */
+polee_status polee_forest_set_nodes(polee_forest *f, int32_t ntrees, const int64_t *tree_off, const int32_t *feature,
+                                    const double *threshold, const int32_t *left, const int32_t *right, const int32_t *label);
+/* votes i32 [R][k]: how many trees sent row r to a leaf of class c */
+polee_status polee_forest_predict_points(polee_forest *f, const float *x, int32_t R, int32_t *votes);
+/* votes i32 [S][k] summed over the ndraws draws of every sample (draw rule as polee_forest_fit) */
+polee_status polee_forest_predict(polee_forest *f, polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0_or_null,
+                                  int32_t *votes);
+/* out f32 [ndraws S][n]: the very rows polee_forest_fit trains on and polee_forest_predict walks (the device's log of the draws: taken in f64, rounded to f32 once) */
+polee_status polee_forest_log_draws(polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0_or_null, float *out);
+/* The same forest on the host, trees in parallel over POLEE_HOST_THREADS; no context.  With the node arrays NULL it only counts
+ * (*nnodes); otherwise it fills them, and POLEE_ERR_BAD_ARG if the forest needs more than `capacity` nodes (ntrees (2 N_b - 1) always
+ * suffices).  tree_off i64 [ntrees+1]. */
+polee_status polee_forest_build_host(const float *x, const int32_t *labels, int32_t N, int32_t n, int32_t k,
+                                     const polee_forest_opts *opts, uint64_t seed, int64_t capacity, int64_t *nnodes,
+                                     int64_t *tree_off, int32_t *feature, double *threshold, int32_t *left, int32_t *right,
+                                     int32_t *label);
+polee_status polee_forest_votes_host(int32_t n, int32_t k, int32_t ntrees, const int64_t *tree_off, const int32_t *feature,
+                                     const double *threshold, const int32_t *left, const int32_t *right, const int32_t *label,
+                                     const float *x, int32_t R, int32_t *votes);
+
 #ifdef __cplusplus
 }
 #endif

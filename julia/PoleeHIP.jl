@@ -1517,6 +1517,125 @@ function embed(ts::TSNE, x::Vector{Float32})
     return z
 end
 
+# ---- `polee model random-forest` (models/random-forest.jl; csrc/forest.hip, csrc/forest_host.cpp): forests on posterior draws -------
+"mirror of `polee_forest_opts` (include/polee_hip.h): field order and types must stay in step with the header"
+mutable struct ForestOpts
+    ntrees::Int32; max_depth::Int32; min_samples_leaf::Int32; min_samples_split::Int32
+    nsubfeatures::Float64; partial_sampling::Float64
+    function ForestOpts()
+        o = new()
+        ccall((:polee_forest_default_opts, LIB), Cvoid, (Ref{ForestOpts},), o)
+        return o
+    end
+end
+
+"the node arrays of a forest: tree t owns nodes tree_off[t]+1 : tree_off[t+1] (0-based offsets, 0-based node numbers within a tree)"
+struct ForestNodes
+    tree_off::Vector{Int64}
+    feature::Vector{Int32}
+    threshold::Vector{Float64}
+    left::Vector{Int32}
+    right::Vector{Int32}
+    label::Vector{Int32}
+end
+
+"a forest of k classes on n features; x matrices are row-major vectors [rows*n], labels 0-based class numbers"
+mutable struct Forest
+    h::Ptr{Cvoid}
+    ctx::Context
+    n::Int
+    k::Int
+end
+function Forest(ctx::Context, n::Integer, k::Integer; opts::ForestOpts=ForestOpts())
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:polee_forest_create, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ref{ForestOpts}, Ref{Ptr{Cvoid}}), ctx.h, n, k, opts, r), ctx.h)
+    f = Forest(r[], ctx, n, k)
+    finalizer(x -> ccall((:polee_forest_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), f)
+    return f
+end
+function fit!(f::Forest, x::Vector{Float32}, labels::Vector{Int32}; seed::Integer=12346)
+    GC.@preserve x labels check(
+        ccall((:polee_forest_fit_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}, Int32, UInt64), f.h, x, labels, length(labels), seed),
+        f.ctx.h)
+    return f
+end
+"trains on ndraws draws of every sample of `ap` (row d*S + s carries labels[s])"
+function fit!(f::Forest, ap::ApproxLikelihood, labels::Vector{Int32}, ndraws::Integer; draw_seed::Integer=12345, seed::Integer=12346,
+              z0::Union{Nothing,Vector{Float32}}=nothing)
+    GC.@preserve labels z0 check(
+        ccall((:polee_forest_fit, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, UInt64, UInt64, Ptr{Float32}),
+              f.h, ap.h, labels, ndraws, draw_seed, seed, z0 === nothing ? C_NULL : pointer(z0)), f.ctx.h)
+    return f
+end
+function nodes(f::Forest)
+    nt = Ref{Int32}(0)
+    nn = Ref{Int64}(0)
+    check(ccall((:polee_forest_node_count, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}), f.h, nt, nn), f.ctx.h)
+    fo = ForestNodes(Vector{Int64}(undef, nt[] + 1), Vector{Int32}(undef, nn[]), Vector{Float64}(undef, nn[]), Vector{Int32}(undef, nn[]),
+                     Vector{Int32}(undef, nn[]), Vector{Int32}(undef, nn[]))
+    check(ccall((:polee_forest_get_nodes, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                f.h, fo.tree_off, fo.feature, fo.threshold, fo.left, fo.right, fo.label), f.ctx.h)
+    return fo
+end
+function set_nodes!(f::Forest, fo::ForestNodes)
+    check(ccall((:polee_forest_set_nodes, LIB), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                f.h, length(fo.tree_off) - 1, fo.tree_off, fo.feature, fo.threshold, fo.left, fo.right, fo.label), f.ctx.h)
+end
+"votes [R*k] of the forest on x [R*n]"
+function votes(f::Forest, x::Vector{Float32})
+    R = div(length(x), f.n)
+    v = Vector{Int32}(undef, R * f.k)
+    GC.@preserve x v check(ccall((:polee_forest_predict_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Int32}), f.h, x, R, v), f.ctx.h)
+    return v
+end
+"votes [S*k] summed over ndraws draws of every sample of `ap`"
+function votes(f::Forest, ap::ApproxLikelihood, ndraws::Integer; seed::Integer=12347, z0::Union{Nothing,Vector{Float32}}=nothing)
+    v = Vector{Int32}(undef, ap.S * f.k)
+    GC.@preserve z0 v check(
+        ccall((:polee_forest_predict, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt64, Ptr{Float32}, Ptr{Int32}),
+              f.h, ap.h, ndraws, seed, z0 === nothing ? C_NULL : pointer(z0), v), f.ctx.h)
+    return v
+end
+"the rows [ndraws*S*n] training and prediction see: the device's logf of the draws"
+function forest_log_draws(ap::ApproxLikelihood, ndraws::Integer; seed::Integer=12345, z0::Union{Nothing,Vector{Float32}}=nothing)
+    out = Vector{Float32}(undef, ndraws * ap.S * ap.n)
+    GC.@preserve z0 out check(
+        ccall((:polee_forest_log_draws, LIB), Cint, (Ptr{Cvoid}, Int32, UInt64, Ptr{Float32}, Ptr{Float32}),
+              ap.h, ndraws, seed, z0 === nothing ? C_NULL : pointer(z0), out))
+    return out
+end
+"the same forest on the host, no context"
+function forest_build_host(x::Vector{Float32}, labels::Vector{Int32}, n::Integer, k::Integer; opts::ForestOpts=ForestOpts(),
+                           seed::Integer=12346)
+    N = length(labels)
+    nn = Ref{Int64}(0)
+    GC.@preserve x labels check(
+        ccall((:polee_forest_build_host, LIB), Cint,
+              (Ptr{Float32}, Ptr{Int32}, Int32, Int32, Int32, Ref{ForestOpts}, UInt64, Int64, Ref{Int64}, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+              x, labels, N, n, k, opts, seed, 0, nn, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL))
+    c = nn[]
+    fo = ForestNodes(Vector{Int64}(undef, opts.ntrees + 1), Vector{Int32}(undef, c), Vector{Float64}(undef, c), Vector{Int32}(undef, c),
+                     Vector{Int32}(undef, c), Vector{Int32}(undef, c))
+    GC.@preserve x labels check(
+        ccall((:polee_forest_build_host, LIB), Cint,
+              (Ptr{Float32}, Ptr{Int32}, Int32, Int32, Int32, Ref{ForestOpts}, UInt64, Int64, Ref{Int64}, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+              x, labels, N, n, k, opts, seed, c, nn, fo.tree_off, fo.feature, fo.threshold, fo.left, fo.right, fo.label))
+    return fo
+end
+function forest_votes_host(fo::ForestNodes, x::Vector{Float32}, n::Integer, k::Integer)
+    R = div(length(x), n)
+    v = Vector{Int32}(undef, R * k)
+    GC.@preserve x v check(
+        ccall((:polee_forest_votes_host, LIB), Cint,
+              (Int32, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Int32, Ptr{Int32}),
+              n, k, length(fo.tree_off) - 1, fo.tree_off, fo.feature, fo.threshold, fo.left, fo.right, fo.label, x, R, v))
+    return v
+end
+
 # ---- isoform effect sizes (estimate_isoform_effect_sizes, src/regression.jl:761-945; csrc/effects.hip) -----------------------------
 "the transcripts of `gene_of` (0-based gene of every transcript, any order) segmented by gene once, on creation"
 mutable struct IsoformEffects

@@ -17,6 +17,7 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   RNASeqPCA(...).fit (`polee model pca`)                                     models/polee_pca.py, models/pca.jl
   RNASeqLogisticRegression (`polee model classify`)                          models/polee_classify.py, models/classify.jl
   RNASeqTSNE, estimate_tsne (`polee model tsne`)                             models/polee_tsne.py, models/tsne.jl
+  RNASeqRandomForest (`polee model random-forest`)                           models/random-forest.jl
   build_likelihood_matrix (X from alignments, SimplisticFragModel)           src/rnaseq_sample.jl:58-121, src/fragmodel.jl
   gibbs_sampler / GibbsSampler (`polee debug-sample`)                        src/gibbs.jl, src/main.jl:925-957
   expectation_maximization / EM (`polee debug-optimize`)                     src/em.jl, src/main.jl:960-988
@@ -63,6 +64,9 @@ def __getattr__(name):
     if name in ("RNASeqTSNE", "estimate_tsne"):
         from . import tsne
         return getattr(tsne, name)
+    if name in ("RNASeqRandomForest", "build_forest_host", "forest_votes_host"):
+        from . import random_forest
+        return getattr(random_forest, name)
     if name in ("read_fasta", "kmer_sketches", "kmer_tree", "kmer_candidate_edges", "build_polya_tree_transformation"):
         from . import fit_tree
         return getattr(fit_tree, name)
