@@ -371,6 +371,17 @@ polee_status polee_kmer_tree(polee_ctx *ctx, int64_t n, const uint64_t *sketches
 /* polee_kmer_sketch + polee_kmer_tree with the sketches left on the device in between (polee fit-tree, src/main.jl:638-649) */
 polee_status polee_fit_tree(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, int32_t *node_parent_idxs,
                             int32_t *node_js);
+/* The same inputs and outputs with the Jaccard merges made in ROUNDS ("merge in rounds"): every round merges each
+ * edge that is the best edge of both its endpoints -- priority: bits of J, a hash of the two node numbers, the smaller numbers --
+ * and numbers the new nodes in the order of the priorities.  Another tree than the greedy one (a heuristic either way), the same
+ * tree from all three entries, whatever the thread count or the launch geometry.  stats: NULL, or int64 [4] = {rounds, merges,
+ * nodes left for the Huffman phase, pairs re-evaluated}.  _host: host threads only, no context.  polee_kmer_tree_rounds: index
+ * and rounds on the device, nothing of the index is copied to the host.  polee_fit_tree_rounds: sketches on the device as well. */
+polee_status polee_kmer_tree_rounds_host(int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js, int64_t *stats);
+polee_status polee_kmer_tree_rounds(polee_ctx *ctx, int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js,
+                                    int64_t *stats);
+polee_status polee_fit_tree_rounds(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, int32_t *node_parent_idxs,
+                                   int32_t *node_js, int64_t *stats);
 
 /* ---- one sample over several GPUs -----------------------------------
  * X's rows (fragments) are sharded over the ranks in contiguous blocks; every rank creates its

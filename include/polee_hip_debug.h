@@ -118,6 +118,13 @@ polee_status polee_debug_binomial(polee_ctx *ctx, const int64_t *N, const double
 polee_status polee_debug_kmer_edges_count(polee_ctx *ctx_or_null, int64_t n, const uint64_t *sketches, int64_t *count);
 polee_status polee_debug_kmer_edges_fill(polee_ctx *ctx_or_null, int64_t n, const uint64_t *sketches, int64_t capacity,
                                          uint32_t *u, uint32_t *v, uint32_t *mat, uint32_t *empt);
+/* One best-and-select step of the rounds merge (polee_kmer_tree_rounds*) on edges and keys the caller supplies: E edges, distinct
+ * pairs 1 <= u < v <= num_nodes, key != 0 (in the builders: bits of J << 32 | hash).  An edge is merged when it is the best edge of
+ * both endpoints: the largest key, among equal keys the smaller (u, v).  merged_flags u8 [E]: 1 = merged; order i32 [E]: its place
+ * among the round's merges by descending priority (the i-th gets the i-th new node), -1 = not merged.  ctx: the device's kernels;
+ * NULL: the host twin's passes. */
+polee_status polee_debug_kmer_round_select(polee_ctx *ctx_or_null, int64_t num_nodes, int64_t E, const uint32_t *u, const uint32_t *v,
+                                           const uint64_t *key, uint8_t *merged_flags, int32_t *order);
 
 #ifdef __cplusplus
 }

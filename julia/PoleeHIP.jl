@@ -374,6 +374,36 @@ function kmer_tree(sk::Matrix{UInt64}; ctx::Union{Nothing,Context}=nothing)
     return parents, js
 end
 
+"""
+sketches UInt64 [200, n] -> (node_parent_idxs, node_js, stats) with the merges made in rounds of mutually-best pairs (DESIGN.md 3.12):
+another tree than kmer_tree's, the same from the host threads (ctx = nothing) and from the GPU.  stats = (rounds, merges, nodes
+left for the Huffman phase, pairs re-evaluated).
+"""
+function kmer_tree_rounds(sk::Matrix{UInt64}; ctx::Union{Nothing,Context}=nothing)
+    n = size(sk, 2)
+    parents, js, stats = Vector{Int32}(undef, 2n - 1), Vector{Int32}(undef, 2n - 1), zeros(Int64, 4)
+    if ctx === nothing
+        GC.@preserve sk parents js stats check(
+            ccall((:polee_kmer_tree_rounds_host, LIB), Cint, (Int64, Ptr{UInt64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}), n, sk, parents, js, stats))
+    else
+        GC.@preserve sk parents js stats check(
+            ccall((:polee_kmer_tree_rounds, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                  ctx.h, n, sk, parents, js, stats), ctx.h)
+    end
+    return parents, js, stats
+end
+
+"build_polya_tree_transformation with the merges in rounds, wholly on the GPU (polee_fit_tree_rounds)"
+function build_polya_tree_transformation_rounds(ctx::Context, seqs)
+    offsets, bases = concat_sequences(seqs)
+    n = length(seqs)
+    parents, js, stats = Vector{Int32}(undef, 2n - 1), Vector{Int32}(undef, 2n - 1), zeros(Int64, 4)
+    GC.@preserve offsets bases parents js stats check(
+        ccall((:polee_fit_tree_rounds, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+              ctx.h, n, offsets, bases, parents, js, stats), ctx.h)
+    return parents, js, stats
+end
+
 "build_polya_tree_transformation (kmercluster.jl:96-262) on the GPU: the sketches stay on the device between the two steps"
 function build_polya_tree_transformation(ctx::Context, seqs)
     offsets, bases = concat_sequences(seqs)

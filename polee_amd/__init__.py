@@ -67,7 +67,7 @@ def __getattr__(name):
     if name in ("RNASeqRandomForest", "build_forest_host", "forest_votes_host"):
         from . import random_forest
         return getattr(random_forest, name)
-    if name in ("read_fasta", "kmer_sketches", "kmer_tree", "kmer_candidate_edges", "build_polya_tree_transformation"):
+    if name in ("read_fasta", "kmer_sketches", "kmer_tree", "kmer_candidate_edges", "kmer_round_select", "build_polya_tree_transformation"):
         from . import fit_tree
         return getattr(fit_tree, name)
     if name in ("IsoformEffects", "estimate_isoform_effect_sizes", "build_design_matrix", "gene_map", "gene_initial_values",

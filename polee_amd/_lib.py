@@ -100,6 +100,10 @@ def lib():
         L.polee_fit_tree.argtypes = [C.c_void_p, C.c_int64, i64p, u8p, i32p, i32p]
         L.polee_debug_kmer_edges_count.argtypes = [C.c_void_p, C.c_int64, u64p, C.POINTER(C.c_int64)]
         L.polee_debug_kmer_edges_fill.argtypes = [C.c_void_p, C.c_int64, u64p, C.c_int64, u32p, u32p, u32p, u32p]
+        L.polee_kmer_tree_rounds_host.argtypes = [C.c_int64, u64p, i32p, i32p, i64p]
+        L.polee_kmer_tree_rounds.argtypes = [C.c_void_p, C.c_int64, u64p, i32p, i32p, i64p]
+        L.polee_fit_tree_rounds.argtypes = [C.c_void_p, C.c_int64, i64p, u8p, i32p, i32p, i64p]
+        L.polee_debug_kmer_round_select.argtypes = [C.c_void_p, C.c_int64, C.c_int64, u32p, u32p, u64p, u8p, i32p]
         _lib = L
     return _lib
 

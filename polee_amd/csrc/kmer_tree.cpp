@@ -38,45 +38,14 @@ void sketch_one(const uint8_t *s, int64_t len, uint64_t *out)
     for (int b = 0; b < KMER_H; ++b) out[b] = best[b] == ~0ull ? 0 : best[b];
 }
 
-// sort on the host threads: sorted chunks, then rounds of pairwise merges
-template <class T>
-void parallel_sort(std::vector<T> &a)
-{
-    const size_t N = a.size();
-    const size_t T0 = std::max<size_t>(1, std::min<size_t>(host_threads(), N >> 16));
-    size_t parts = 1;
-    while (parts < T0) parts <<= 1;
-    if (parts == 1) {
-        std::sort(a.begin(), a.end());
-        return;
-    }
-    auto cut = [&](size_t k) { return (size_t)((unsigned __int128)N * k / parts); };
-    parallel_chunks(parts, 1, [&](size_t lo, size_t, unsigned) { std::sort(a.begin() + (ptrdiff_t)cut(lo), a.begin() + (ptrdiff_t)cut(lo + 1)); });
-    for (size_t w = 1; w < parts; w <<= 1)
-        parallel_chunks(parts / (2 * w), 1, [&](size_t lo, size_t, unsigned) {
-            std::inplace_merge(a.begin() + (ptrdiff_t)cut(2 * w * lo), a.begin() + (ptrdiff_t)cut(2 * w * lo + w),
-                               a.begin() + (ptrdiff_t)cut(2 * w * lo + 2 * w));
-        });
-}
-
 struct Entry {
     uint64_t value;
     uint32_t node;
     bool operator<(const Entry &o) const { return value != o.value ? value < o.value : node < o.node; }
 };
 
-inline uint32_t empt_of(const uint64_t *ma, const uint64_t *mb)
-{
-    return (uint32_t)(__builtin_popcountll(ma[0] & mb[0]) + __builtin_popcountll(ma[1] & mb[1]) + __builtin_popcountll(ma[2] & mb[2]) +
-                      __builtin_popcountll(ma[3] & mb[3]));
-}
-
-inline void mask_of(const uint32_t *ranks, uint64_t *m)  // bit b: bin b is empty
-{
-    m[0] = m[1] = m[2] = m[3] = 0;
-    for (int b = 0; b < KMER_H; ++b)
-        if (ranks[b] == KMER_EMPTY) m[b >> 6] |= 1ull << (b & 63);
-}
+inline uint32_t empt_of(const uint64_t *ma, const uint64_t *mb) { return kmer_empt_of(ma, mb); }
+inline void mask_of(const uint32_t *ranks, uint64_t *m) { kmer_mask_of(ranks, m); }
 
 struct HeapEdge {
     float J;
@@ -132,7 +101,7 @@ polee_status kmer_index_host(int64_t n, const uint64_t *sk, KmerIndex &ix)
                 if (sk[t * KMER_H + b]) ent[o++] = Entry{sk[t * KMER_H + b], (uint32_t)t};
         }
     });
-    parallel_sort(ent);
+    kmer_parallel_sort(ent);
     ix.ranks.assign(cells, KMER_EMPTY);
     ix.ent.resize(E);
     ix.run_start.clear();
@@ -159,7 +128,7 @@ polee_status kmer_index_host(int64_t n, const uint64_t *sk, KmerIndex &ix)
     for (size_t r = 0; r < R; ++r)
         for (uint32_t a = ix.run_start[r]; a < ix.run_start[r + 1]; ++a)
             for (uint32_t b = a + 1; b < ix.run_start[r + 1]; ++b) keys.push_back(((uint64_t)(ix.ent[a] + 1) << 32) | (ix.ent[b] + 1));
-    parallel_sort(keys);
+    kmer_parallel_sort(keys);
     std::vector<uint64_t> masks((size_t)n * 4);
     parallel_chunks((size_t)n, 4096, [&](size_t lo, size_t hi, unsigned) {
         for (size_t t = lo; t < hi; ++t) mask_of(&ix.ranks[t * KMER_H], &masks[t * 4]);
@@ -235,6 +204,13 @@ polee_status kmer_tree_merge(KmerIndex &ix, int32_t *parents, int32_t *js)
             count[x] = 0;
         }
     }
+    return kmer_tree_finish(n, next, left, right, height, active, parents, js);
+}
+
+polee_status kmer_tree_finish(int64_t n, size_t next, std::vector<uint32_t> &left, std::vector<uint32_t> &right, std::vector<uint32_t> &height,
+                              const std::vector<uint8_t> &active, int32_t *parents, int32_t *js)
+{
+    const size_t N = (size_t)(2 * n - 1);
     // Huffman phase (kmercluster.jl:245-254): the two nodes of smallest height, ties by node number; first popped = left
     typedef std::pair<uint32_t, uint32_t> HN;  // (height, node)
     std::priority_queue<HN, std::vector<HN>, std::greater<HN>> rest;

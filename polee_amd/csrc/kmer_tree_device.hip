@@ -190,7 +190,9 @@ __global__ void kmer_edge_kernel(const uint64_t *uniq, const uint32_t *counts, u
 
 inline unsigned blocks_for(uint64_t count) { return (unsigned)((count + 255) / 256); }
 
-polee_status check_offsets(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, const char *who)
+}  // namespace
+
+polee_status kmer_check_offsets(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, const char *who)
 {
     if (n < 1 || n > POLEE_KMER_MAX_N || !offsets) return fail(ctx, POLEE_ERR_BAD_ARG, "%s: null offsets, or n outside 1 .. %lld", who, (long long)POLEE_KMER_MAX_N);
     if (offsets[0] != 0) return fail(ctx, POLEE_ERR_BAD_ARG, "%s: offsets[0] must be 0", who);
@@ -201,7 +203,7 @@ polee_status check_offsets(polee_ctx *ctx, int64_t n, const int64_t *offsets, co
 }
 
 // sketches of n transcripts into d_sk [n][200], queued on the context's stream
-polee_status sketch_device(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, DevBuf<uint64_t> &d_sk, KmerClock &clk)
+polee_status kmer_sketch_device(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, DevBuf<uint64_t> &d_sk, KmerClock &clk)
 {
     hipStream_t stream = ctx->stream;
     const size_t cells = (size_t)n * KMER_H, total = (size_t)offsets[n];
@@ -248,12 +250,23 @@ polee_status sketch_device(polee_ctx *ctx, int64_t n, const int64_t *offsets, co
     return POLEE_OK;
 }
 
-// the index of the sketches d_sk [n][200] (valid ones: a value in its bin), from the device
-polee_status kmer_index_device(polee_ctx *ctx, int64_t n, const uint64_t *d_sk, KmerIndex &ix)
+// the index of the sketches d_sk [n][200] (valid ones: a value in its bin), from the device.  host: the greedy merge loop's copy
+// (ranks, holder lists, edges); keep: what the rounds go on with where it is (ranks and masks with room for `rows` nodes, edges) --
+// then nothing is copied to the host.
+polee_status kmer_index_device(polee_ctx *ctx, int64_t n, const uint64_t *d_sk, KmerIndex *host, KmerIndexDev *keep, size_t rows)
 {
     hipStream_t stream = ctx->stream;
     const size_t cells = (size_t)n * KMER_H;
     DevScratch tmp(ctx);
+    KmerIndex none;
+    KmerIndex &ix = host ? *host : none;
+    KmerIndexDev mine;
+    KmerIndexDev &D = keep ? *keep : mine;
+    DevBuf<uint32_t> &ranks = D.ranks;
+    DevBuf<uint64_t> &masks = D.masks;
+    DevBuf<KmerEdge> &edges = D.edges;
+    D.NE = 0;
+    rows = std::max(rows, (size_t)n);
     ix.n = n;
     ix.edges.clear();
     DevBuf<uint64_t> key_s;
@@ -272,16 +285,19 @@ polee_status kmer_index_device(polee_ctx *ctx, int64_t n, const uint64_t *d_sk, 
     uint32_t Z = 0;
     POLEE_TRY(d_count.download(ctx, &Z, 1));
     const uint32_t E = (uint32_t)(cells - Z);
-    ix.ranks.assign(cells, KMER_EMPTY);
-    ix.ent.resize(E);
+    if (host) {
+        ix.ranks.assign(cells, KMER_EMPTY);
+        ix.ent.resize(E);
+    }
     ix.run_start.assign(1, 0);
     if (E == 0) return POLEE_OK;
     const uint64_t *key = key_s.p + Z;
     const uint32_t *ent = node_s.p + Z;
-    DevBuf<uint32_t> head, incl, ranks, run_start;
+    DevBuf<uint32_t> head, incl, run_start;
     POLEE_TRY(head.alloc(ctx, E));
     POLEE_TRY(incl.alloc(ctx, E));
-    POLEE_TRY(ranks.alloc(ctx, cells));
+    if (ranks.alloc(ctx, rows * KMER_H) != POLEE_OK)
+        return fail(ctx, POLEE_ERR_OOM, "k-mer tree: the ranks of %zu nodes (%zu bytes) do not fit into the device's memory", rows, rows * KMER_H * sizeof(uint32_t));
     POLEE_TRY(run_start.alloc(ctx, (size_t)E + 1));
     KT_HIP(hipMemsetAsync(ranks.p, 0xFF, cells * sizeof(uint32_t), stream));
     kmer_head_kernel<<<blocks_for(E), 256, 0, stream>>>(key, E, head.p);
@@ -294,11 +310,13 @@ polee_status kmer_index_device(polee_ctx *ctx, int64_t n, const uint64_t *d_sk, 
     KT_HIP(hipStreamSynchronize(stream));
     head.release();
     incl.release();
-    ix.run_start.resize((size_t)R + 1);
-    POLEE_TRY(ranks.download(ctx, ix.ranks.data(), cells));
-    POLEE_TRY(run_start.download(ctx, ix.run_start.data(), (size_t)R + 1));
-    KT_HIP(hipMemcpyAsync(ix.ent.data(), ent, (size_t)E * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    KT_HIP(hipStreamSynchronize(stream));
+    if (host) {
+        ix.run_start.resize((size_t)R + 1);
+        POLEE_TRY(ranks.download(ctx, ix.ranks.data(), cells));
+        POLEE_TRY(run_start.download(ctx, ix.run_start.data(), (size_t)R + 1));
+        KT_HIP(hipMemcpyAsync(ix.ent.data(), ent, (size_t)E * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        KT_HIP(hipStreamSynchronize(stream));
+    }
     key_s.release();
     // count before allocating
     DevBuf<uint64_t> pc, poff;
@@ -317,7 +335,7 @@ polee_status kmer_index_device(polee_ctx *ctx, int64_t n, const uint64_t *d_sk, 
                     "gives r (r - 1) / 2 of them: mask repeats, or exclude the transcripts that carry them)",
                     (unsigned long long)P, (unsigned long long)POLEE_KMER_MAX_PAIRS);
     if (P == 0) return POLEE_OK;
-    DevBuf<uint64_t> pk, pk_s, uniq, masks;
+    DevBuf<uint64_t> pk, pk_s, uniq;
     DevBuf<uint32_t> counts;
     POLEE_TRY(pk.alloc(ctx, (size_t)P));
     POLEE_TRY(pk_s.alloc(ctx, (size_t)P));
@@ -328,26 +346,32 @@ polee_status kmer_index_device(polee_ctx *ctx, int64_t n, const uint64_t *d_sk, 
     POLEE_TRY(uniq.alloc(ctx, (size_t)P));
     POLEE_TRY(counts.alloc(ctx, (size_t)P));
     KT_PRIM(rocprim::run_length_encode(tmp_p, bytes, pk_s.p, (unsigned int)P, uniq.p, counts.p, d_count.p + 1, stream));
-    POLEE_TRY(masks.alloc(ctx, (size_t)n * 4));
+    POLEE_TRY(masks.alloc(ctx, rows * 4));
     kmer_mask_kernel<<<blocks_for((uint64_t)n * 4), 256, 0, stream>>>(ranks.p, (size_t)n, masks.p);
     POLEE_KERNEL_CHECK(ctx);
     uint32_t NE = 0;
     KT_HIP(hipMemcpyAsync(&NE, d_count.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     KT_HIP(hipStreamSynchronize(stream));
     pk_s.release();
-    DevBuf<KmerEdge> edges;
     POLEE_TRY(edges.alloc(ctx, NE));
     kmer_edge_kernel<<<blocks_for(NE), 256, 0, stream>>>(uniq.p, counts.p, NE, masks.p, edges.p);
     POLEE_KERNEL_CHECK(ctx);
-    ix.edges.resize(NE);
-    POLEE_TRY(edges.download(ctx, ix.edges.data(), NE));
+    D.NE = NE;
+    if (host) {
+        ix.edges.resize(NE);
+        POLEE_TRY(edges.download(ctx, ix.edges.data(), NE));
+    } else {
+        KT_HIP(hipStreamSynchronize(stream));  // (uniq and counts go out of scope here)
+    }
     return POLEE_OK;
 }
+
+namespace {
 
 polee_status tree_from_device_sketches(polee_ctx *ctx, int64_t n, const uint64_t *d_sk, int32_t *parents, int32_t *js, KmerClock &clk)
 {
     KmerIndex ix;
-    POLEE_TRY(kmer_index_device(ctx, n, d_sk, ix));
+    POLEE_TRY(kmer_index_device(ctx, n, d_sk, &ix, nullptr, (size_t)n));
     clk.lap("candidate edges (device)");
     POLEE_TRY(kmer_tree_merge(ix, parents, js));
     clk.lap("merge loop + DFS");
@@ -362,7 +386,7 @@ polee_status index_any(polee_ctx *ctx, int64_t n, const uint64_t *sketches, Kmer
     POLEE_TRY(kmer_validate_sketches(ctx, n, sketches));
     DevBuf<uint64_t> d_sk;
     POLEE_TRY(d_sk.upload(ctx, sketches, (size_t)n * KMER_H));
-    return kmer_index_device(ctx, n, d_sk.p, ix);
+    return kmer_index_device(ctx, n, d_sk.p, &ix, nullptr, (size_t)n);
 }
 
 }  // namespace
@@ -374,11 +398,11 @@ extern "C" polee_status polee_kmer_sketch(polee_ctx *ctx, int64_t n, const int64
 {
     return guarded(ctx, "polee_kmer_sketch", [&]() -> polee_status {
         POLEE_TRY(use_device(ctx));
-        POLEE_TRY(check_offsets(ctx, n, offsets, bases, "polee_kmer_sketch"));
+        POLEE_TRY(kmer_check_offsets(ctx, n, offsets, bases, "polee_kmer_sketch"));
         if (!sketches) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_kmer_sketch: null output");
         KmerClock clk;
         DevBuf<uint64_t> d_sk;
-        POLEE_TRY(sketch_device(ctx, n, offsets, bases, d_sk, clk));
+        POLEE_TRY(kmer_sketch_device(ctx, n, offsets, bases, d_sk, clk));
         return d_sk.download(ctx, sketches, (size_t)n * KMER_H);
     });
 }
@@ -402,11 +426,11 @@ extern "C" polee_status polee_fit_tree(polee_ctx *ctx, int64_t n, const int64_t 
 {
     return guarded(ctx, "polee_fit_tree", [&]() -> polee_status {
         POLEE_TRY(use_device(ctx));
-        POLEE_TRY(check_offsets(ctx, n, offsets, bases, "polee_fit_tree"));
+        POLEE_TRY(kmer_check_offsets(ctx, n, offsets, bases, "polee_fit_tree"));
         if (!node_parent_idxs || !node_js) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_fit_tree: null output");
         KmerClock clk;
         DevBuf<uint64_t> d_sk;
-        POLEE_TRY(sketch_device(ctx, n, offsets, bases, d_sk, clk));
+        POLEE_TRY(kmer_sketch_device(ctx, n, offsets, bases, d_sk, clk));
         return tree_from_device_sketches(ctx, n, d_sk.p, node_parent_idxs, node_js, clk);
     });
 }
