@@ -17,13 +17,12 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import arr, check, f32p, ptr
-from .core import RNASeqApproxLikelihood, default_context
+from ._model import MASK, Handle, approx_of, draw_seed, make_opts, z0_flat
+from .core import default_context
 
 NUM_STEPS = 5000         # models/classify.jl:203-205, :237-239
 TESTING_SAMPLES = 100    # models/classify.jl:241-242 (the --testing-samples default of 20 is never read there)
 DEFAULT_SEED = 123456789
-_DRAW_STRIDE = 0x9E3779B97F4A7C15
-_MASK = (1 << 64) - 1
 
 
 class ClassifyOpts(C.Structure):
@@ -32,42 +31,20 @@ class ClassifyOpts(C.Structure):
                 ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float)]
 
 
-def _approx(vars, ctx):
-    if isinstance(vars, dict) and isinstance(vars.get("approx"), RNASeqApproxLikelihood):
-        return vars["approx"]
-    return vars if isinstance(vars, RNASeqApproxLikelihood) else RNASeqApproxLikelihood(vars, ctx=ctx)
-
-
-class RNASeqLogisticRegression:
+class RNASeqLogisticRegression(Handle):
     """RNASeqLogisticRegression (models/polee_classify.py:13-114): w [n, k], x_bias [n], z_bias [k], all zero at first and all trained.
     `vars`: LoadedSamples.variables (its "approx" handle is used), an RNASeqApproxLikelihood, or the dict of
     create_tensorflow_variables!.  Options (draws_per_step, learning_rate, l1_penalty, loss_scale, beta1, beta2, epsilon) default
     to the reference's: 5 draws per step, Adam(1e-4), penalty 0.001.  `seed`, `z0` and `return_trace` are additions: draw i of a
     call uses seed + 0x9E3779B97F4A7C15 i (the bias draw of fit_sample: index -1), z0 replaces the device's N(0,1) noise."""
+    _destroy = "polee_classify_destroy"
 
     def __init__(self, k, n, ctx=None, **opts):
         self.k, self.n = int(k), int(n)
         self.ctx = ctx or default_context()
         self._h = C.c_void_p()
-        lib = L.lib()
-        lib.polee_classify_default_opts.restype = None
-        self.opts = ClassifyOpts()
-        lib.polee_classify_default_opts(C.byref(self.opts))
-        for name, v in opts.items():
-            if name not in dict(ClassifyOpts._fields_):
-                raise TypeError("unknown option %r" % name)
-            setattr(self.opts, name, v)
-        check(lib.polee_classify_create(self.ctx._h, self.n, self.k, C.byref(self.opts), C.byref(self._h)), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                f = L.lib().polee_classify_destroy
-                f.restype, f.argtypes = None, [C.c_void_p]
-                f(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+        self.opts = make_opts(ClassifyOpts, L.lib().polee_classify_default_opts, opts)
+        check(L.lib().polee_classify_create(self.ctx._h, self.n, self.k, C.byref(self.opts), C.byref(self._h)), self.ctx._h)
 
     # ---- parameters
     def get_params(self):
@@ -105,27 +82,18 @@ class RNASeqLogisticRegression:
         return x
 
     def _lik(self, num_samples, n, vars):
-        ap = _approx(vars, self.ctx)
+        ap = approx_of(vars, self.ctx)
         if int(n) != self.n or ap.n != self.n or ap.S != int(num_samples):
             raise ValueError("the approximation is [%d, %d], the call says [%d, %d], the classifier has n = %d"
                              % (ap.S, ap.n, num_samples, n, self.n))
         return ap
 
-    @staticmethod
-    def _z0(z0, count):
-        if z0 is None:
-            return None
-        z = arr(z0, np.float32).reshape(-1)
-        if z.size != count:
-            raise ValueError("z0 must hold %d values" % count)
-        return z
-
     # ---- the reference's methods
     def init_bias_sample(self, num_samples, n, vars, seed=DEFAULT_SEED, z0=None):
         """x_bias <- the column mean of the log of one draw (:52-55)"""
         ap = self._lik(num_samples, n, vars)
-        z = self._z0(z0, ap.S * (ap.n - 1))
-        check(L.lib().polee_classify_init_bias(self._h, ap._h, ptr(z, f32p), C.c_uint64(seed & _MASK)), self.ctx._h)
+        z = z0_flat(z0, ap.S * (ap.n - 1))
+        check(L.lib().polee_classify_init_bias(self._h, ap._h, ptr(z, f32p), C.c_uint64(seed & MASK)), self.ctx._h)
 
     def init_bias(self, x):
         """x_bias <- the column mean of x (:75)"""
@@ -145,8 +113,8 @@ class RNASeqLogisticRegression:
         else:
             ap = self._lik(num_samples, n, vars)
             y = self._labels(z_true, ap.S)
-            z = self._z0(z0, self.opts.draws_per_step * ap.S * (ap.n - 1))
-            check(L.lib().polee_classify_eval(self._h, ap._h, ptr(y, f32p), ptr(z, f32p), C.c_uint64(seed & _MASK), ptr(loss, f32p),
+            z = z0_flat(z0, self.opts.draws_per_step * ap.S * (ap.n - 1))
+            check(L.lib().polee_classify_eval(self._h, ap._h, ptr(y, f32p), ptr(z, f32p), C.c_uint64(seed & MASK), ptr(loss, f32p),
                                               ptr(gw, f32p), ptr(gxb, f32p), ptr(gzb, f32p)), self.ctx._h)
         return float(loss[0]), gw, gxb, gzb
 
@@ -154,9 +122,9 @@ class RNASeqLogisticRegression:
         """niter Adam steps without the bias initialisation; the step clock runs on across calls.  Returns the loss trace."""
         ap = self._lik(num_samples, n, vars)
         y = self._labels(z_true, ap.S)
-        z = self._z0(z0, int(niter) * self.opts.draws_per_step * ap.S * (ap.n - 1))
+        z = z0_flat(z0, int(niter) * self.opts.draws_per_step * ap.S * (ap.n - 1))
         trace = np.empty(int(niter), np.float32)
-        check(L.lib().polee_classify_fit(self._h, ap._h, ptr(y, f32p), int(niter), C.c_uint64(seed & _MASK), ptr(z, f32p),
+        check(L.lib().polee_classify_fit(self._h, ap._h, ptr(y, f32p), int(niter), C.c_uint64(seed & MASK), ptr(z, f32p),
                                          ptr(trace, f32p)), self.ctx._h)
         return trace
 
@@ -175,7 +143,7 @@ class RNASeqLogisticRegression:
         the device's noise."""
         if samples_per_iter is not None:
             self._set_opts(draws_per_step=int(samples_per_iter))
-        self.init_bias_sample(num_samples, n, vars, seed=(seed - _DRAW_STRIDE) & _MASK)
+        self.init_bias_sample(num_samples, n, vars, seed=draw_seed(seed, -1))
         self.reset()
         trace = self.fit_steps_sample(num_samples, n, vars, z_true, niter, seed=seed, z0=z0)
         w = self.get_params()[0]
@@ -196,9 +164,9 @@ class RNASeqLogisticRegression:
     def predict_sample(self, num_samples, n, vars, niter, seed=DEFAULT_SEED, z0=None):
         """predict_sample (:105-111): the mean over niter draws of softmax(logits), [S, k]"""
         ap = self._lik(num_samples, n, vars)
-        z = self._z0(z0, int(niter) * ap.S * (ap.n - 1))
+        z = z0_flat(z0, int(niter) * ap.S * (ap.n - 1))
         probs = np.empty((ap.S, self.k), np.float32)
-        check(L.lib().polee_classify_predict(self._h, ap._h, int(niter), C.c_uint64(seed & _MASK), ptr(z, f32p), ptr(probs, f32p)),
+        check(L.lib().polee_classify_predict(self._h, ap._h, int(niter), C.c_uint64(seed & MASK), ptr(z, f32p), ptr(probs, f32p)),
               self.ctx._h)
         return probs
 

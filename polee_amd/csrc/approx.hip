@@ -797,7 +797,7 @@ static polee_status feature_moments_impl(polee_approx *ap, const std::vector<int
         const int nd = mode == 0 ? num_mean_draws : num_var_draws;
         for (int d = 0; d < nd; ++d, ++draw) {
             if (z0) POLEE_TRY(ap->d_z0.upload(ctx, z0 + (size_t)draw * sk, sk));
-            POLEE_TRY(approx_sample_device(ap, z0 ? ap->d_z0.p : nullptr, seed + 0x9E3779B97F4A7C15ull * (uint64_t)draw));
+            POLEE_TRY(approx_sample_device(ap, z0 ? ap->d_z0.p : nullptr, seed + POLEE_DRAW_STRIDE * (uint64_t)draw));
             hipLaunchKernelGGL(feature_sum_kernel, gp, dim3(256), 0, ctx->stream, d_fi.p, d_ti.p, P, n, F, ap->d_x.p,
                                d_fx.p);
             if (anti)

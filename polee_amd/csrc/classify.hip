@@ -7,108 +7,50 @@
 //
 // Per draw, on the context's stream, nothing waits for the device:
 //   1. approx_sample_device           the draw x [S][n] (approx.hip), clipped at 1e-16 so logf is finite
-//   2. classify_logits_kernel         grid over chunks of CL_WAVE_J transcripts, one wave per chunk: the wave keeps its chunk of w and
-//                                     x_bias in registers for all S samples; f32 FMAs over the lane's transcripts, then a fixed
-//                                     shuffle tree over the lanes; partials [chunks][S][k]
+//   2. classify_logits_kernel         chunk_project with the bias: partials [chunks][S][k]; on a step's first draw also sum |w|
 //   3. classify_finish_kernel         one workgroup per sample: the partials summed in f64 in a fixed order, + z_bias, softmax in f64;
 //                                     training: dl = (softmax - labels) loss_scale / D and the sample's loss term; prediction:
 //                                     probabilities accumulated in f64
-//   4. classify_grad_kernel           one thread per transcript, coalesced over j, reads every x[s][j] once; dl staged in LDS
+//   4. classify_grad_kernel           grad_accumulate with the bias, one thread per transcript:
 //                                     g_w[c][j] += sum_s (lx - x_bias[j]) dl[s][c];  g_xb[j] -= sum_c w[j][c] sum_s dl[s][c];
 //                                     workgroup 0 adds the draw's g_zb and loss
-// After the last draw of a step classify_update_kernel adds l1 sign(w), applies Adam (the TF form, as regression.hip) to w, x_bias and
-// z_bias and leaves the accumulators at zero; in evaluation mode it hands the same gradients out instead.
-// There are no float atomics: every sum has a fixed order, so results are bitwise reproducible.
+// After the last draw of a step classify_update_kernel adds l1 sign(w), applies Adam (tf_adam) to w, x_bias and z_bias and leaves the
+// accumulators at zero; in evaluation mode it hands the same gradients out instead.
+// The projection, the LDS-tiled gradient accumulation, the f64 sums over chunks, Adam and the draw loop are draw_model.hpp's, shared
+// with tsne.hip.  There are no float atomics: every sum has a fixed order, so results are bitwise reproducible.
 // Parameters, moments and accumulators share one flat layout: wT [k][n] | x_bias [n] | z_bias [k] (the ABI speaks w [n][k]).
-#include "common.hpp"
-#include "wave.hpp"  // wave_split_reduce
-
-#include <cmath>
+#include "draw_model.hpp"
 
 namespace polee {
 
-constexpr int CL_BLOCK = 256;
-constexpr int CL_WAVE_J = 128;  // transcripts per chunk of the logits kernel: one wave, two per lane
-constexpr int CL_TILE_S = 64;   // samples whose dl the gradient kernel stages in LDS at a time
-constexpr uint64_t CL_DRAW_STRIDE = 0x9E3779B97F4A7C15ull;  // draw i uses seed + stride * i (as polee_approx_feature_moments)
-
 // part [nchunks][S][k]; abs_part [nchunks] or null: sum |w| of the chunk (the L1 term of the loss, once per step)
 template <int KP>
-__global__ __launch_bounds__(CL_BLOCK) void classify_logits_kernel(int n, int S, int k, int nchunks, const float *__restrict__ x,
+__global__ __launch_bounds__(DM_BLOCK) void classify_logits_kernel(int n, int S, int k, int nchunks, const float *__restrict__ x,
                                                                   int is_log, const float *__restrict__ P,
                                                                   float *__restrict__ part, float *__restrict__ abs_part)
 {
-    const int lane = threadIdx.x & 63;
-    const int chunk = blockIdx.x * (CL_BLOCK / 64) + (threadIdx.x >> 6);
-    if (chunk >= nchunks) return;  // (wave-uniform; the kernel has no barrier)
-    const int64_t j0 = (int64_t)chunk * CL_WAVE_J + lane, j1 = j0 + 64;
-    const bool a0 = j0 < n, a1 = j1 < n;
-    const float *xb = P + (int64_t)k * n;
-    float w0[KP], w1[KP];
-#pragma unroll
-    for (int c = 0; c < KP; ++c) {
-        w0[c] = (a0 && c < k) ? P[(int64_t)c * n + j0] : 0.0f;
-        w1[c] = (a1 && c < k) ? P[(int64_t)c * n + j1] : 0.0f;
-    }
-    const float b0 = a0 ? xb[j0] : 0.0f, b1 = a1 ? xb[j1] : 0.0f;
-    if (abs_part) {
-        float a = 0.0f;
-#pragma unroll
-        for (int c = 0; c < KP; ++c) a += fabsf(w0[c]) + fabsf(w1[c]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
-        if (lane == 0) abs_part[chunk] = a;
-    }
-    constexpr int PER = 64 / KP;
-    const int cls = lane / PER;
-    const bool writer = (lane % PER) == 0 && cls < k;
-    for (int s = 0; s < S; ++s) {
-        const float *xs = x + (int64_t)s * n;
-        const float v0 = a0 ? xs[j0] : 1.0f, v1 = a1 ? xs[j1] : 1.0f;
-        const float l0 = a0 ? (is_log ? v0 : logf(v0)) - b0 : 0.0f;
-        const float l1 = a1 ? (is_log ? v1 : logf(v1)) - b1 : 0.0f;
-        float p[KP];
-#pragma unroll
-        for (int c = 0; c < KP; ++c) p[c] = fmaf(l1, w1[c], l0 * w0[c]);
-        wave_split_reduce<KP>(p, lane);
-        if (writer) part[((int64_t)chunk * S + s) * k + cls] = p[0];
-    }
+    chunk_project<KP, true, false>(n, S, k, nchunks, x, is_log, P, P + (int64_t)k * n, part, abs_part, nullptr);
 }
 
 // grid S (+ 1 when abs_part: that workgroup sums the L1 term into lossacc[1]).  mode 0: dl [S][k], loss_s [S]; mode 1: probs [S][k] +=
 template <int KP>
-__global__ __launch_bounds__(CL_BLOCK) void classify_finish_kernel(int S, int k, int nchunks, const float *__restrict__ part,
+__global__ __launch_bounds__(DM_BLOCK) void classify_finish_kernel(int S, int k, int nchunks, const float *__restrict__ part,
                                                                   const float *__restrict__ zb, const float *__restrict__ labels,
                                                                   double scale, int mode, float *__restrict__ dl,
                                                                   double *__restrict__ loss_s, double *__restrict__ probs,
                                                                   const float *__restrict__ abs_part, double l1,
                                                                   double *__restrict__ lossacc)
 {
-    __shared__ double red[CL_BLOCK];
+    __shared__ double red[DM_BLOCK];
     const int tid = threadIdx.x, s = blockIdx.x;
     if (s == S) {  // (only launched with abs_part)
         double a = 0.0;
-        for (int ch = tid; ch < nchunks; ch += CL_BLOCK) a += (double)abs_part[ch];
-        red[tid] = a;
-        __syncthreads();
-        for (int o = CL_BLOCK / 2; o >= 1; o >>= 1) {
-            if (tid < o) red[tid] += red[tid + o];
-            __syncthreads();
-        }
-        if (tid == 0) lossacc[1] = l1 * red[0];
+        for (int ch = tid; ch < nchunks; ch += DM_BLOCK) a += (double)abs_part[ch];
+        a = block_sum(a, red);
+        if (tid == 0) lossacc[1] = l1 * a;
         return;
     }
-    constexpr int Q = CL_BLOCK / KP;
-    const int c = tid % KP, q = tid / KP;
-    double a = 0.0;
-    if (c < k)
-        for (int ch = q; ch < nchunks; ch += Q) a += (double)part[((int64_t)ch * S + s) * k + c];
-    red[tid] = a;
-    __syncthreads();
-    for (int o = Q / 2; o >= 1; o >>= 1) {
-        if (q < o) red[tid] += red[tid + o * KP];
-        __syncthreads();
-    }
+    chunk_sum<KP, false>(part, S, k, nchunks, s, red);
     if (tid != 0) return;
     // (thread 0 alone: k <= 16 numbers; the logits stay in LDS so that nothing is indexed at run time in registers)
     double mx = -INFINITY;
@@ -134,42 +76,21 @@ __global__ __launch_bounds__(CL_BLOCK) void classify_finish_kernel(int S, int k,
 
 // G: the accumulators in the parameters' layout.  Workgroup 0 also adds the draw's g_zb and its loss (lossacc[0]).
 template <int KP>
-__global__ __launch_bounds__(CL_BLOCK) void classify_grad_kernel(int n, int S, int k, const float *__restrict__ x, int is_log,
+__global__ __launch_bounds__(DM_BLOCK) void classify_grad_kernel(int n, int S, int k, const float *__restrict__ x, int is_log,
                                                                 const float *__restrict__ P, const float *__restrict__ dl,
                                                                 const double *__restrict__ loss_s, float *__restrict__ G,
                                                                 double *__restrict__ lossacc)
 {
-    __shared__ float sdl[CL_TILE_S * KP];
+    __shared__ float sdl[DM_TILE_S * KP];
     __shared__ float sds[KP];
     const int tid = threadIdx.x;
-    const int64_t j = (int64_t)blockIdx.x * CL_BLOCK + tid;
+    const int64_t j = (int64_t)blockIdx.x * DM_BLOCK + tid;
     const bool active = j < n;
     const int64_t kn = (int64_t)k * n;
     const float xbj = active ? P[kn + j] : 0.0f;
     float acc[KP];
-#pragma unroll
-    for (int c = 0; c < KP; ++c) acc[c] = 0.0f;
-    double dsum = 0.0;
-    for (int s0 = 0; s0 < S; s0 += CL_TILE_S) {
-        const int ns = min(CL_TILE_S, S - s0);
-        __syncthreads();
-        for (int e = tid; e < ns * KP; e += CL_BLOCK) {
-            const int s = e / KP, c = e % KP;
-            sdl[e] = c < k ? dl[(int64_t)(s0 + s) * k + c] : 0.0f;
-        }
-        __syncthreads();
-        if (tid < KP)
-            for (int s = 0; s < ns; ++s) dsum += (double)sdl[s * KP + tid];
-        if (active) {
-#pragma unroll 4
-            for (int s = 0; s < ns; ++s) {
-                const float v = x[(int64_t)(s0 + s) * n + j];
-                const float lx = (is_log ? v : logf(v)) - xbj;
-#pragma unroll
-                for (int c = 0; c < KP; ++c) acc[c] = fmaf(lx, sdl[s * KP + c], acc[c]);
-            }
-        }
-    }
+    double dsum;
+    grad_accumulate<KP, true, true>(n, S, k, x, is_log, dl, j, active, xbj, sdl, acc, dsum);
     if (tid < KP) sds[tid] = (float)dsum;
     __syncthreads();
     if (active) {
@@ -192,9 +113,8 @@ __global__ __launch_bounds__(CL_BLOCK) void classify_grad_kernel(int n, int S, i
     }
 }
 
-// After the last draw of a step.  mode 0: Adam (tf.optimizers.Adam: p -= lr_t m / (sqrt(v) + eps), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
-// from the host); mode 1: the gradients go to gout, nothing is updated.  Either way the accumulators are left at zero and
-// loss_out[0] = the step's loss.
+// After the last draw of a step.  mode 0: Adam; mode 1: the gradients go to gout, nothing is updated.  Either way the accumulators are
+// left at zero and loss_out[0] = the step's loss.
 __global__ void classify_update_kernel(int64_t total, int64_t kn, float *__restrict__ P, float *__restrict__ G, float *__restrict__ M,
                                        float *__restrict__ V, float lr_t, float b1, float b2, float eps, float l1, int mode,
                                        float *__restrict__ gout, double *__restrict__ lossacc, float *__restrict__ loss_out)
@@ -213,11 +133,7 @@ __global__ void classify_update_kernel(int64_t total, int64_t kn, float *__restr
         gout[i] = g;
         return;
     }
-    const float m = b1 * M[i] + (1.0f - b1) * g;
-    const float v = b2 * V[i] + (1.0f - b2) * g * g;
-    M[i] = m;
-    V[i] = v;
-    P[i] = p - lr_t * m / (sqrtf(v) + eps);
+    P[i] = tf_adam(p, &M[i], &V[i], g, lr_t, b1, b2, eps);
 }
 
 // x_bias <- the column mean over samples of lx (polee_classify.py:52-55, :75)
@@ -231,12 +147,6 @@ __global__ void classify_colmean_kernel(int n, int S, const float *__restrict__ 
         a += (double)(is_log ? v : logf(v));
     }
     xb[j] = (float)(a / (double)S);
-}
-
-__global__ void classify_probs_kernel(int64_t count, const double *__restrict__ acc, double ndraws, float *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) out[i] = (float)(acc[i] / ndraws);
 }
 
 }  // namespace polee
@@ -302,29 +212,10 @@ polee_status upload_labels(polee_classify *cl, const float *labels, int32_t S)
     return cl->d_labels.upload(ctx, labels, (size_t)S * cl->k);
 }
 
-// the reference takes log 0 = -inf silently when a TPM is 0 and no pseudocount is given (classify.jl:141-147)
 polee_status upload_points(polee_classify *cl, const float *x, int32_t S)
 {
-    polee_ctx *ctx = cl->ctx;
-    if (!x || S < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify: bad argument");
-    const size_t sn = (size_t)S * cl->n;
-    for (size_t i = 0; i < sn; ++i)
-        if (!std::isfinite(x[i]))
-            return fail(ctx, POLEE_ERR_NONFINITE,
-                        "polee_classify: x[%zu][%zu] is not finite (log of a zero point estimate? add a pseudocount)", i / cl->n,
-                        i % cl->n);
-    return cl->d_x.upload(ctx, x, sn);
-}
-
-polee_status check_approx(polee_classify *cl, polee_approx *ap, int32_t *S)
-{
-    polee_ctx *ctx = cl->ctx;
-    if (!ap) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify: null approximation handle");
-    int32_t n = 0;
-    approx_dims(ap, S, &n);
-    if (approx_ctx(ap) != ctx) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify: the approximation lives on another context");
-    if (n != cl->n) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify: the approximation has n = %d, the classifier n = %d", n, cl->n);
-    return POLEE_OK;
+    POLEE_TRY(check_points(cl->ctx, "polee_classify", x, S, cl->n));
+    return cl->d_x.upload(cl->ctx, x, (size_t)S * cl->n);
 }
 
 // one draw through the kernels.  mode 0: training (dl, loss, gradient accumulation), 1: prediction (probabilities accumulated)
@@ -334,14 +225,14 @@ polee_status draw_pass_t(polee_classify *cl, const float *d_x, int is_log, int32
     polee_ctx *ctx = cl->ctx;
     hipStream_t st = ctx->stream;
     const bool pen = first && mode == 0;
-    hipLaunchKernelGGL((classify_logits_kernel<KP>), dim3((unsigned)ceil_div(cl->nchunks, CL_BLOCK / 64)), dim3(CL_BLOCK), 0, st, cl->n, S,
+    hipLaunchKernelGGL((classify_logits_kernel<KP>), dim3((unsigned)ceil_div(cl->nchunks, DM_BLOCK / 64)), dim3(DM_BLOCK), 0, st, cl->n, S,
                        cl->k, cl->nchunks, d_x, is_log, (const float *)cl->d_P.p, cl->d_part.p, pen ? cl->d_abs.p : nullptr);
-    hipLaunchKernelGGL((classify_finish_kernel<KP>), dim3((unsigned)(S + (pen ? 1 : 0))), dim3(CL_BLOCK), 0, st, S, cl->k, cl->nchunks,
+    hipLaunchKernelGGL((classify_finish_kernel<KP>), dim3((unsigned)(S + (pen ? 1 : 0))), dim3(DM_BLOCK), 0, st, S, cl->k, cl->nchunks,
                        (const float *)cl->d_part.p, (const float *)(cl->d_P.p + cl->kn + cl->n), (const float *)cl->d_labels.p, scale,
                        mode, cl->d_dl.p, cl->d_loss_s.p, cl->d_probs.p, (const float *)(pen ? cl->d_abs.p : nullptr),
                        (double)cl->o.l1_penalty, cl->d_lossacc.p);
     if (mode == 0)
-        hipLaunchKernelGGL((classify_grad_kernel<KP>), dim3((unsigned)ceil_div(cl->n, CL_BLOCK)), dim3(CL_BLOCK), 0, st, cl->n, S, cl->k,
+        hipLaunchKernelGGL((classify_grad_kernel<KP>), dim3((unsigned)ceil_div(cl->n, DM_BLOCK)), dim3(DM_BLOCK), 0, st, cl->n, S, cl->k,
                            d_x, is_log, (const float *)cl->d_P.p, (const float *)cl->d_dl.p, (const double *)cl->d_loss_s.p,
                            cl->d_G.p, cl->d_lossacc.p);
     POLEE_KERNEL_CHECK(ctx);
@@ -350,12 +241,7 @@ polee_status draw_pass_t(polee_classify *cl, const float *d_x, int is_log, int32
 
 polee_status draw_pass(polee_classify *cl, const float *d_x, int is_log, int32_t S, double scale, bool first, int mode)
 {
-    switch (cl->KP) {
-    case 2: return draw_pass_t<2>(cl, d_x, is_log, S, scale, first, mode);
-    case 4: return draw_pass_t<4>(cl, d_x, is_log, S, scale, first, mode);
-    case 8: return draw_pass_t<8>(cl, d_x, is_log, S, scale, first, mode);
-    default: return draw_pass_t<16>(cl, d_x, is_log, S, scale, first, mode);
-    }
+    return dispatch_kp(cl->KP, [&](auto kp) { return draw_pass_t<decltype(kp)::value>(cl, d_x, is_log, S, scale, first, mode); });
 }
 
 // mode 0: the Adam step number t; mode 1: gradients to d_gout.  The step's loss goes to d_loss_out[0].
@@ -363,10 +249,8 @@ polee_status step_tail(polee_classify *cl, int mode, int64_t t, float *d_loss_ou
 {
     polee_ctx *ctx = cl->ctx;
     const polee_classify_opts &o = cl->o;
-    const double lr_t = mode == 0 ? (double)o.learning_rate * std::sqrt(1.0 - std::pow((double)o.beta2, (double)t)) /
-                                        (1.0 - std::pow((double)o.beta1, (double)t))
-                                  : 0.0;
-    hipLaunchKernelGGL(classify_update_kernel, dim3((unsigned)ceil_div(cl->total, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, cl->total,
+    const double lr_t = mode == 0 ? tf_adam_rate(o.learning_rate, o.beta1, o.beta2, t) : 0.0;
+    hipLaunchKernelGGL(classify_update_kernel, dim3((unsigned)ceil_div(cl->total, DM_BLOCK)), dim3(DM_BLOCK), 0, ctx->stream, cl->total,
                        cl->kn, cl->d_P.p, cl->d_G.p, cl->d_M.p, cl->d_V.p, (float)lr_t, o.beta1, o.beta2, o.epsilon, o.l1_penalty, mode,
                        cl->d_gout.p, cl->d_lossacc.p, d_loss_out);
     POLEE_KERNEL_CHECK(ctx);
@@ -376,12 +260,9 @@ polee_status step_tail(polee_classify *cl, int mode, int64_t t, float *d_loss_ou
 // the flat device layout <-> the ABI's w [n][k], x_bias [n], z_bias [k]
 void to_abi(const polee_classify *cl, const std::vector<float> &flat, float *w, float *xb, float *zb)
 {
-    const int64_t n = cl->n, k = cl->k;
-    if (w)
-        for (int64_t j = 0; j < n; ++j)
-            for (int64_t c = 0; c < k; ++c) w[j * k + c] = flat[(size_t)(c * n + j)];
-    if (xb) std::copy(flat.begin() + cl->kn, flat.begin() + cl->kn + n, xb);
-    if (zb) std::copy(flat.begin() + cl->kn + n, flat.end(), zb);
+    if (w) wT_to_abi(flat.data(), cl->n, cl->k, w);
+    if (xb) std::copy(flat.begin() + cl->kn, flat.begin() + cl->kn + cl->n, xb);
+    if (zb) std::copy(flat.begin() + cl->kn + cl->n, flat.end(), zb);
 }
 
 polee_status eval_tail(polee_classify *cl, float *loss, float *g_w, float *g_xb, float *g_zb)
@@ -414,22 +295,11 @@ polee_status abandon(polee_classify *cl, int64_t steps_done, polee_status st)
     return st;
 }
 
-polee_status fit_finish(polee_classify *cl, int32_t niter, float *loss_trace)
-{
-    polee_ctx *ctx = cl->ctx;
-    cl->t += niter;
-    if (loss_trace) return cl->d_loss.download(ctx, loss_trace, (size_t)niter);
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return POLEE_OK;
-}
-
 polee_status predict_finish(polee_classify *cl, int32_t S, int32_t ndraws, float *probs)
 {
     polee_ctx *ctx = cl->ctx;
     const int64_t sk = (int64_t)S * cl->k;
-    hipLaunchKernelGGL(classify_probs_kernel, dim3((unsigned)ceil_div(sk, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, sk,
-                       (const double *)cl->d_probs.p, (double)ndraws, cl->d_probs_out.p);
-    POLEE_KERNEL_CHECK(ctx);
+    POLEE_TRY(launch_acc_mean(ctx, sk, cl->d_probs.p, ndraws, cl->d_probs_out.p));
     return cl->d_probs_out.download(ctx, probs, (size_t)sk);
 }
 
@@ -466,8 +336,8 @@ polee_status polee_classify_create(polee_ctx *ctx, int32_t n, int32_t k, const p
         ctx_retain(ctx);
         cl->n = n;
         cl->k = k;
-        cl->KP = k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : 16;
-        cl->nchunks = (int32_t)ceil_div(n, CL_WAVE_J);
+        cl->KP = kp_of(k);
+        cl->nchunks = (int32_t)ceil_div(n, DM_WAVE_J);
         cl->kn = (int64_t)k * n;
         cl->total = cl->kn + n + k;
         cl->o = o;
@@ -521,10 +391,7 @@ polee_status polee_classify_set_opts(polee_classify *cl, const polee_classify_op
 
 polee_status polee_classify_get_params(polee_classify *cl, float *w, float *x_bias, float *z_bias)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_get_params: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_get_params", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_get_params", [&](polee_ctx *ctx) -> polee_status {
         std::vector<float> flat((size_t)cl->total);
         POLEE_TRY(cl->d_P.download(ctx, flat.data(), flat.size()));
         to_abi(cl, flat, w, x_bias, z_bias);
@@ -534,48 +401,41 @@ polee_status polee_classify_get_params(polee_classify *cl, float *w, float *x_bi
 
 polee_status polee_classify_set_params(polee_classify *cl, const float *w, const float *x_bias, const float *z_bias)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_set_params: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_set_params", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_set_params", [&](polee_ctx *ctx) -> polee_status {
         if (!w || !x_bias || !z_bias) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_set_params: null argument");
-        const int64_t n = cl->n, k = cl->k;
         std::vector<float> flat((size_t)cl->total);
-        for (int64_t j = 0; j < n; ++j)
-            for (int64_t c = 0; c < k; ++c) flat[(size_t)(c * n + j)] = w[j * k + c];
-        std::copy(x_bias, x_bias + n, flat.begin() + cl->kn);
-        std::copy(z_bias, z_bias + k, flat.begin() + cl->kn + n);
+        abi_to_wT(w, cl->n, cl->k, flat.data());
+        std::copy(x_bias, x_bias + cl->n, flat.begin() + cl->kn);
+        std::copy(z_bias, z_bias + cl->k, flat.begin() + cl->kn + cl->n);
         return cl->d_P.upload(ctx, flat);
     });
 }
 
 polee_status polee_classify_reset(polee_classify *cl)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_reset: null handle");
-    polee_ctx *ctx = cl->ctx;
-    POLEE_TRY(use_device(ctx));
-    const size_t bytes = (size_t)cl->total * sizeof(float);
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_M.p, 0, bytes, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_V.p, 0, bytes, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_G.p, 0, bytes, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_lossacc.p, 0, 2 * sizeof(double), ctx->stream));
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    cl->t = 0;
-    return POLEE_OK;
+    return entry(cl, "polee_classify_reset", [&](polee_ctx *ctx) -> polee_status {
+        const size_t bytes = (size_t)cl->total * sizeof(float);
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_M.p, 0, bytes, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_V.p, 0, bytes, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_G.p, 0, bytes, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_lossacc.p, 0, 2 * sizeof(double), ctx->stream));
+        POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        cl->t = 0;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_classify_init_bias(polee_classify *cl, polee_approx *ap, const float *z0, uint64_t seed)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_init_bias: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_init_bias", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_init_bias", [&](polee_ctx *ctx) -> polee_status {
         int32_t S = 0;
-        POLEE_TRY(check_approx(cl, ap, &S));
-        if (z0) POLEE_TRY(cl->d_z0.upload(ctx, z0, (size_t)S * (cl->n - 1)));
-        POLEE_TRY(approx_sample_device(ap, z0 ? cl->d_z0.p : nullptr, seed));
-        hipLaunchKernelGGL(classify_colmean_kernel, dim3((unsigned)ceil_div(cl->n, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, cl->n, S,
-                           approx_draw_buffer(ap), 0, cl->d_P.p + cl->kn);
+        POLEE_TRY(check_approx(ctx, "polee_classify", ap, cl->n, 0, &S));
+        DrawFeed feed(ap, cl->d_z0, S, cl->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, 1));
+        POLEE_TRY(feed.draw(0, 0, &d_x));
+        hipLaunchKernelGGL(classify_colmean_kernel, dim3((unsigned)ceil_div(cl->n, DM_BLOCK)), dim3(DM_BLOCK), 0, ctx->stream, cl->n, S,
+                           d_x, 0, cl->d_P.p + cl->kn);
         POLEE_KERNEL_CHECK(ctx);
         POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return POLEE_OK;
@@ -584,12 +444,9 @@ polee_status polee_classify_init_bias(polee_classify *cl, polee_approx *ap, cons
 
 polee_status polee_classify_init_bias_points(polee_classify *cl, const float *x, int32_t S)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_init_bias_points: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_init_bias_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_init_bias_points", [&](polee_ctx *ctx) -> polee_status {
         POLEE_TRY(upload_points(cl, x, S));
-        hipLaunchKernelGGL(classify_colmean_kernel, dim3((unsigned)ceil_div(cl->n, CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, cl->n, S,
+        hipLaunchKernelGGL(classify_colmean_kernel, dim3((unsigned)ceil_div(cl->n, DM_BLOCK)), dim3(DM_BLOCK), 0, ctx->stream, cl->n, S,
                            (const float *)cl->d_x.p, 1, cl->d_P.p + cl->kn);
         POLEE_KERNEL_CHECK(ctx);
         POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -600,22 +457,20 @@ polee_status polee_classify_init_bias_points(polee_classify *cl, const float *x,
 polee_status polee_classify_eval(polee_classify *cl, polee_approx *ap, const float *labels, const float *z0, uint64_t seed, float *loss,
                                  float *g_w, float *g_x_bias, float *g_z_bias)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_eval: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_eval", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_eval", [&](polee_ctx *ctx) -> polee_status {
         int32_t S = 0;
-        POLEE_TRY(check_approx(cl, ap, &S));
+        POLEE_TRY(check_approx(ctx, "polee_classify", ap, cl->n, 0, &S));
         if (!labels || !loss) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_eval: null argument");
         const int32_t D = cl->o.draws_per_step;
-        const size_t sk = (size_t)S * (cl->n - 1);
         POLEE_TRY(ensure_samples(cl, S));
         POLEE_TRY(upload_labels(cl, labels, S));
-        if (z0) POLEE_TRY(cl->d_z0.upload(ctx, z0, (size_t)D * sk));
+        DrawFeed feed(ap, cl->d_z0, S, cl->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)D));
         polee_status st = POLEE_OK;
         for (int32_t d = 0; d < D && st == POLEE_OK; ++d) {
-            st = approx_sample_device(ap, z0 ? cl->d_z0.p + (size_t)d * sk : nullptr, seed + CL_DRAW_STRIDE * (uint64_t)d);
-            if (st == POLEE_OK) st = draw_pass(cl, approx_draw_buffer(ap), 0, S, (double)cl->o.loss_scale / D, d == 0, 0);
+            st = feed.draw((uint64_t)d, (size_t)d, &d_x);
+            if (st == POLEE_OK) st = draw_pass(cl, d_x, 0, S, (double)cl->o.loss_scale / D, d == 0, 0);
         }
         if (st == POLEE_OK) st = eval_tail(cl, loss, g_w, g_x_bias, g_z_bias);
         return st == POLEE_OK ? st : abandon(cl, 0, st);
@@ -625,10 +480,7 @@ polee_status polee_classify_eval(polee_classify *cl, polee_approx *ap, const flo
 polee_status polee_classify_eval_points(polee_classify *cl, const float *x, int32_t S, const float *labels, float *loss, float *g_w,
                                         float *g_x_bias, float *g_z_bias)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_eval_points: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_eval_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_eval_points", [&](polee_ctx *ctx) -> polee_status {
         if (!labels || !loss) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_eval_points: null argument");
         POLEE_TRY(upload_points(cl, x, S));
         POLEE_TRY(ensure_samples(cl, S));
@@ -642,42 +494,36 @@ polee_status polee_classify_eval_points(polee_classify *cl, const float *x, int3
 polee_status polee_classify_fit(polee_classify *cl, polee_approx *ap, const float *labels, int32_t niter, uint64_t seed, const float *z0,
                                 float *loss_trace)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_fit: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_fit", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_fit", [&](polee_ctx *ctx) -> polee_status {
         int32_t S = 0;
-        POLEE_TRY(check_approx(cl, ap, &S));
+        POLEE_TRY(check_approx(ctx, "polee_classify", ap, cl->n, 0, &S));
         if (!labels || niter < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_fit: bad argument");
         const int32_t D = cl->o.draws_per_step;
-        const size_t sk = (size_t)S * (cl->n - 1);
         POLEE_TRY(ensure_samples(cl, S));
         POLEE_TRY(upload_labels(cl, labels, S));
         POLEE_TRY(cl->d_loss.alloc(ctx, (size_t)niter));
-        if (z0) POLEE_TRY(cl->d_z0.upload(ctx, z0, (size_t)niter * D * sk));  // (once, before the loop)
+        DrawFeed feed(ap, cl->d_z0, S, cl->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)niter * D));
         const double scale = (double)cl->o.loss_scale / D;
         for (int32_t it = 0; it < niter; ++it) {
             const int64_t t = cl->t + it + 1;
             polee_status st = POLEE_OK;
             for (int32_t d = 0; d < D && st == POLEE_OK; ++d) {
-                const uint64_t i = (uint64_t)(t - 1) * (uint64_t)D + (uint64_t)d;
-                st = approx_sample_device(ap, z0 ? cl->d_z0.p + ((size_t)it * D + d) * sk : nullptr, seed + CL_DRAW_STRIDE * i);
-                if (st == POLEE_OK) st = draw_pass(cl, approx_draw_buffer(ap), 0, S, scale, d == 0, 0);
+                st = feed.draw((uint64_t)(t - 1) * (uint64_t)D + (uint64_t)d, (size_t)it * D + d, &d_x);
+                if (st == POLEE_OK) st = draw_pass(cl, d_x, 0, S, scale, d == 0, 0);
             }
             if (st == POLEE_OK) st = step_tail(cl, 0, t, cl->d_loss.p + it);
             if (st != POLEE_OK) return abandon(cl, it, st);
         }
-        return fit_finish(cl, niter, loss_trace);
+        return fit_finish(ctx, &cl->t, cl->d_loss, niter, loss_trace);
     });
 }
 
 polee_status polee_classify_fit_points(polee_classify *cl, const float *x, int32_t S, const float *labels, int32_t niter,
                                        float *loss_trace)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_fit_points: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_fit_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_fit_points", [&](polee_ctx *ctx) -> polee_status {
         if (!labels || niter < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_fit_points: bad argument");
         POLEE_TRY(upload_points(cl, x, S));
         POLEE_TRY(ensure_samples(cl, S));
@@ -688,7 +534,7 @@ polee_status polee_classify_fit_points(polee_classify *cl, const float *x, int32
             if (st == POLEE_OK) st = step_tail(cl, 0, cl->t + it + 1, cl->d_loss.p + it);
             if (st != POLEE_OK) return abandon(cl, it, st);
         }
-        return fit_finish(cl, niter, loss_trace);
+        return fit_finish(ctx, &cl->t, cl->d_loss, niter, loss_trace);
     });
 }
 
@@ -696,20 +542,18 @@ polee_status polee_classify_fit_points(polee_classify *cl, const float *x, int32
 // term nor the clock, and their own accumulator d_probs is zeroed at the start of every call)
 polee_status polee_classify_predict(polee_classify *cl, polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0, float *probs)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_predict: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_predict", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_predict", [&](polee_ctx *ctx) -> polee_status {
         int32_t S = 0;
-        POLEE_TRY(check_approx(cl, ap, &S));
+        POLEE_TRY(check_approx(ctx, "polee_classify", ap, cl->n, 0, &S));
         if (!probs || ndraws < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_predict: bad argument");
-        const size_t sk = (size_t)S * (cl->n - 1);
         POLEE_TRY(ensure_samples(cl, S));
-        if (z0) POLEE_TRY(cl->d_z0.upload(ctx, z0, (size_t)ndraws * sk));
+        DrawFeed feed(ap, cl->d_z0, S, cl->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)ndraws));
         POLEE_HIP_TRY(ctx, hipMemsetAsync(cl->d_probs.p, 0, (size_t)S * cl->k * sizeof(double), ctx->stream));
         for (int32_t i = 0; i < ndraws; ++i) {
-            POLEE_TRY(approx_sample_device(ap, z0 ? cl->d_z0.p + (size_t)i * sk : nullptr, seed + CL_DRAW_STRIDE * (uint64_t)i));
-            POLEE_TRY(draw_pass(cl, approx_draw_buffer(ap), 0, S, 1.0, false, 1));
+            POLEE_TRY(feed.draw((uint64_t)i, (size_t)i, &d_x));
+            POLEE_TRY(draw_pass(cl, d_x, 0, S, 1.0, false, 1));
         }
         return predict_finish(cl, S, ndraws, probs);
     });
@@ -717,10 +561,7 @@ polee_status polee_classify_predict(polee_classify *cl, polee_approx *ap, int32_
 
 polee_status polee_classify_predict_points(polee_classify *cl, const float *x, int32_t S, float *probs)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_predict_points: null handle");
-    polee_ctx *ctx = cl->ctx;
-    return guarded(ctx, "polee_classify_predict_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(cl, "polee_classify_predict_points", [&](polee_ctx *ctx) -> polee_status {
         if (!probs) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_predict_points: null argument");
         POLEE_TRY(upload_points(cl, x, S));
         POLEE_TRY(ensure_samples(cl, S));

@@ -639,6 +639,22 @@ inline polee_status guarded(polee_ctx *ctx, const char *what, F &&f)
     }
 }
 
+// How an entry point on a handle H (a struct with a ctx member) opens: a null handle fails, nothing unwinds through the C ABI, the
+// context's device is current.  f(ctx) is the entry's body.
+template <class H, class F>
+inline polee_status entry(H *h, const char *name, F &&f)
+{
+    if (!h) return fail(nullptr, POLEE_ERR_BAD_ARG, "%s: null handle", name);
+    polee_ctx *ctx = h->ctx;
+    return guarded(ctx, name, [&]() -> polee_status {
+        POLEE_TRY(use_device(ctx));
+        return f(ctx);
+    });
+}
+
+// draw i of a call under `seed` is made under seed + POLEE_DRAW_STRIDE * i (polee_approx_feature_moments and the draw-fed models)
+constexpr uint64_t POLEE_DRAW_STRIDE = 0x9E3779B97F4A7C15ull;
+
 // accessors of the approximation handle (approx.hip) for its consumers
 polee_ctx *approx_ctx(const polee_approx *ap);
 void approx_dims(const polee_approx *ap, int32_t *S, int32_t *n);

@@ -19,10 +19,8 @@
 // The host reads one small record per level (open nodes and how many of them each search kernel takes) and stops at zero.
 // There are no float atomics; the only atomics append node indices to the search kernels' work lists, whose order changes nothing.
 // Compiled with -ffp-contract=off: the score is a chain of f64 additions that the host builder repeats bit for bit.
-#include "common.hpp"
+#include "draw_model.hpp"  // check_approx, check_points, DrawFeed
 #include "forest_common.hpp"
-
-#include <cmath>
 
 namespace polee {
 namespace forest {
@@ -33,7 +31,6 @@ constexpr int FO_MIN_CHUNK = 16;          // fewest candidates of one work item
 constexpr int64_t FO_TARGET_ITEMS = 1 << 15;  // work items a level is cut into when it has few open nodes
 constexpr int FO_MID = 1024;              // sort slots of the smaller workgroup kernel
 constexpr int FO_MAX_N_ROWS = 1 << 27;    // (row, label) pack into 32 bits
-constexpr uint64_t FO_DRAW_STRIDE = 0x9E3779B97F4A7C15ull;  // draw d uses seed + stride * d (as classify.hip)
 
 struct OpenNode {
     int32_t tree, node, beg, end, depth;  // rows [beg, end) of the tree's row array
@@ -561,27 +558,6 @@ struct polee_forest {
 
 namespace {
 
-polee_status check_approx(polee_ctx *ctx, int32_t n, polee_approx *ap, int32_t *S)
-{
-    if (!ap) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest: null approximation handle");
-    int32_t an = 0;
-    approx_dims(ap, S, &an);
-    if (approx_ctx(ap) != ctx) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest: the approximation lives on another context");
-    if (n > 0 && an != n) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest: the approximation has n = %d, the forest n = %d", an, n);
-    return POLEE_OK;
-}
-
-polee_status check_points(polee_ctx *ctx, const float *x, int64_t R, int32_t n)
-{
-    if (!x || R < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest: bad argument");
-    const size_t cnt = (size_t)R * n;
-    for (size_t i = 0; i < cnt; ++i)
-        if (!std::isfinite(x[i]))
-            return fail(ctx, POLEE_ERR_NONFINITE, "polee_forest: x[%zu][%zu] is not finite (log of a zero point estimate? add a pseudocount)",
-                        i / n, i % n);
-    return POLEE_OK;
-}
-
 polee_status load_nodes(polee_forest *f, int32_t ntrees, const int64_t *off, const int32_t *feature, const double *threshold,
                         const int32_t *left, const int32_t *right, const int32_t *label)
 {
@@ -820,12 +796,9 @@ void polee_forest_destroy(polee_forest *f)
 
 polee_status polee_forest_fit_points(polee_forest *f, const float *x, const int32_t *labels, int32_t N, uint64_t seed)
 {
-    if (!f) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_fit_points: null handle");
-    polee_ctx *ctx = f->ctx;
-    return guarded(ctx, "polee_forest_fit_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(f, "polee_forest_fit_points", [&](polee_ctx *ctx) -> polee_status {
         if (!labels) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_fit_points: null argument");
-        POLEE_TRY(check_points(ctx, x, N, f->n));
+        POLEE_TRY(check_points(ctx, "polee_forest", x, N, f->n));
         POLEE_TRY(check_rows(f, N));
         POLEE_TRY(upload_labels(f, labels, N, 1));
         POLEE_TRY(f->d_x.upload(ctx, x, (size_t)N * f->n));
@@ -839,22 +812,20 @@ polee_status polee_forest_fit_points(polee_forest *f, const float *x, const int3
 polee_status polee_forest_fit(polee_forest *f, polee_approx *ap, const int32_t *labels, int32_t ndraws, uint64_t draw_seed, uint64_t seed,
                               const float *z0)
 {
-    if (!f) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_fit: null handle");
-    polee_ctx *ctx = f->ctx;
-    return guarded(ctx, "polee_forest_fit", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(f, "polee_forest_fit", [&](polee_ctx *ctx) -> polee_status {
         int32_t S = 0;
-        POLEE_TRY(check_approx(ctx, f->n, ap, &S));
+        POLEE_TRY(check_approx(ctx, "polee_forest", ap, f->n, 0, &S));
         if (!labels || ndraws < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_fit: bad argument");
         const int64_t N = (int64_t)ndraws * S;
         POLEE_TRY(check_rows(f, N));
         POLEE_TRY(upload_labels(f, labels, S, ndraws));
-        const size_t sk = (size_t)S * (f->n - 1);
-        if (z0) POLEE_TRY(f->d_z0.upload(ctx, z0, (size_t)ndraws * sk));
+        DrawFeed feed(ap, f->d_z0, S, f->n, draw_seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)ndraws));
         POLEE_TRY(f->d_xT.alloc(ctx, (size_t)N * f->n));
         for (int32_t d = 0; d < ndraws; ++d) {
-            POLEE_TRY(approx_sample_device(ap, z0 ? f->d_z0.p + (size_t)d * sk : nullptr, draw_seed + FO_DRAW_STRIDE * (uint64_t)d));
-            launch_layout(f, approx_draw_buffer(ap), S, 1, N, (int64_t)d * S);
+            POLEE_TRY(feed.draw((uint64_t)d, (size_t)d, &d_x));
+            launch_layout(f, d_x, S, 1, N, (int64_t)d * S);
             POLEE_KERNEL_CHECK(ctx);
         }
         return grow(f, N, seed);
@@ -889,10 +860,7 @@ polee_status polee_forest_get_nodes(polee_forest *f, int64_t *tree_off, int32_t 
 polee_status polee_forest_set_nodes(polee_forest *f, int32_t ntrees, const int64_t *tree_off, const int32_t *feature,
                                     const double *threshold, const int32_t *left, const int32_t *right, const int32_t *label)
 {
-    if (!f) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_set_nodes: null handle");
-    polee_ctx *ctx = f->ctx;
-    return guarded(ctx, "polee_forest_set_nodes", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(f, "polee_forest_set_nodes", [&](polee_ctx *ctx) -> polee_status {
         if (ntrees < 1 || ntrees > FO_MAX_TREES || !tree_off || !feature || !threshold || !left || !right || !label)
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_set_nodes: bad argument");
         int32_t bt = 0;
@@ -905,13 +873,10 @@ polee_status polee_forest_set_nodes(polee_forest *f, int32_t ntrees, const int64
 
 polee_status polee_forest_predict_points(polee_forest *f, const float *x, int32_t R, int32_t *votes)
 {
-    if (!f) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_predict_points: null handle");
-    polee_ctx *ctx = f->ctx;
-    return guarded(ctx, "polee_forest_predict_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(f, "polee_forest_predict_points", [&](polee_ctx *ctx) -> polee_status {
         if (!votes) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_predict_points: null argument");
         if (!f->ntrees) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_predict_points: no forest yet");
-        POLEE_TRY(check_points(ctx, x, R, f->n));
+        POLEE_TRY(check_points(ctx, "polee_forest", x, R, f->n));
         POLEE_TRY(f->d_x.upload(ctx, x, (size_t)R * f->n));
         POLEE_TRY(f->d_votes.alloc(ctx, (size_t)R * f->k));
         POLEE_HIP_TRY(ctx, hipMemsetAsync(f->d_votes.p, 0, (size_t)R * f->k * sizeof(int32_t), ctx->stream));
@@ -922,23 +887,22 @@ polee_status polee_forest_predict_points(polee_forest *f, const float *x, int32_
 
 polee_status polee_forest_predict(polee_forest *f, polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0, int32_t *votes)
 {
-    if (!f) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_predict: null handle");
-    polee_ctx *ctx = f->ctx;
-    return guarded(ctx, "polee_forest_predict", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(f, "polee_forest_predict", [&](polee_ctx *ctx) -> polee_status {
         int32_t S = 0;
-        POLEE_TRY(check_approx(ctx, f->n, ap, &S));
+        POLEE_TRY(check_approx(ctx, "polee_forest", ap, f->n, 0, &S));
         if (!votes || ndraws < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_predict: bad argument");
         if (!f->ntrees) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_predict: no forest yet");
-        const size_t sk = (size_t)S * (f->n - 1), sn = (size_t)S * f->n;
-        if (z0) POLEE_TRY(f->d_z0.upload(ctx, z0, (size_t)ndraws * sk));
+        const size_t sn = (size_t)S * f->n;
+        DrawFeed feed(ap, f->d_z0, S, f->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)ndraws));
         POLEE_TRY(f->d_lx.alloc(ctx, sn));
         POLEE_TRY(f->d_votes.alloc(ctx, (size_t)S * f->k));
         POLEE_HIP_TRY(ctx, hipMemsetAsync(f->d_votes.p, 0, (size_t)S * f->k * sizeof(int32_t), ctx->stream));
         for (int32_t d = 0; d < ndraws; ++d) {
-            POLEE_TRY(approx_sample_device(ap, z0 ? f->d_z0.p + (size_t)d * sk : nullptr, seed + FO_DRAW_STRIDE * (uint64_t)d));
+            POLEE_TRY(feed.draw((uint64_t)d, (size_t)d, &d_x));
             hipLaunchKernelGGL(forest_log_kernel, dim3((unsigned)ceil_div((int64_t)sn, FO_BLOCK)), dim3(FO_BLOCK), 0, ctx->stream, (int64_t)sn,
-                               approx_draw_buffer(ap), f->d_lx.p);
+                               d_x, f->d_lx.p);
             POLEE_TRY(predict_rows(f, f->d_lx.p, S));
         }
         return f->d_votes.download(ctx, votes, (size_t)S * f->k);
@@ -954,14 +918,16 @@ polee_status polee_forest_log_draws(polee_approx *ap, int32_t ndraws, uint64_t s
         int32_t S = 0, n = 0;
         approx_dims(ap, &S, &n);
         if (!out || ndraws < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_log_draws: bad argument");
-        const size_t sk = (size_t)S * (n - 1), sn = (size_t)S * n;
+        const size_t sn = (size_t)S * n;
         DevBuf<float> d_z0, d_lx;
-        if (z0) POLEE_TRY(d_z0.upload(ctx, z0, (size_t)ndraws * sk));
+        DrawFeed feed(ap, d_z0, S, n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)ndraws));
         POLEE_TRY(d_lx.alloc(ctx, sn));
         for (int32_t d = 0; d < ndraws; ++d) {
-            POLEE_TRY(approx_sample_device(ap, z0 ? d_z0.p + (size_t)d * sk : nullptr, seed + FO_DRAW_STRIDE * (uint64_t)d));
+            POLEE_TRY(feed.draw((uint64_t)d, (size_t)d, &d_x));
             hipLaunchKernelGGL(forest_log_kernel, dim3((unsigned)ceil_div((int64_t)sn, FO_BLOCK)), dim3(FO_BLOCK), 0, ctx->stream, (int64_t)sn,
-                               approx_draw_buffer(ap), d_lx.p);
+                               d_x, d_lx.p);
             POLEE_KERNEL_CHECK(ctx);
             POLEE_TRY(d_lx.download(ctx, out + (size_t)d * sn, sn));
         }

@@ -10,9 +10,8 @@
 //
 // Per step, on the context's stream, nothing waits for the device:
 //   1. approx_sample_device        the draw x [S][n] (approx.hip), clipped at 1e-16 so logf is finite
-//   2. tsne_project_kernel         as classify_logits_kernel: one wave per chunk of TS_WAVE_J transcripts keeps its chunk of W in
-//                                  registers for all S samples; besides the C partial sums of z it writes the chunk's sum of lx
-//                                  (the row means cost no read of their own); partials [chunks][S][C] and [chunks][S]
+//   2. tsne_project_kernel         chunk_project (draw_model.hpp) without a bias: besides the C partial sums of z it writes the
+//                                  chunk's sum of lx (the row means cost no read of their own); partials [chunks][S][C] and [chunks][S]
 //   3. tsne_finish_kernel          one workgroup per sample: the partials summed in f64 in a fixed order -> z f64 [S][C], the row
 //                                  mean in f64, its f32 rounding mhat and the residue mean - mhat; the sample's position in I
 //   4. tsne_pairwise_kernel        THE HOT PATH.  A workgroup takes one pair of 64-row tiles of the batch and TS_CHUNK transcripts;
@@ -24,9 +23,10 @@
 //   6. tsne_sums_kernel            column sums of E on the batch, row sums of the Student kernel k on all samples
 //   7. tsne_loss_kernel            per batch row: P, Q, R = P / Q, the row's loss and its share of sum R o Q
 //   8. tsne_dz_kernel              per sample: dz_i = 2 sum_j A_ij (z_i - z_j); workgroup 0 writes the step's loss
-//   9. tsne_grad_update_kernel     one thread per transcript, reads every x[s][j] once: g_W[j][c] = sum_s lx[s][j] dz[s][c], then Adam
-//                                  (the TF1 form) on W in the same thread; in evaluation mode the gradient is handed out instead
+//   9. tsne_grad_update_kernel     grad_accumulate, one thread per transcript: g_W[j][c] = sum_s lx[s][j] dz[s][c], then Adam
+//                                  (tf_adam) on W in the same thread; in evaluation mode the gradient is handed out instead
 // Steps 6 - 8 are f64 throughout.  There are no float atomics and every sum has a fixed order: results are bitwise reproducible.
+// The projection, the gradient accumulation, the f64 sums, Adam and the draw loop are draw_model.hpp's, shared with classify.hip.
 // The centred form is used, not the Gram form r_a + r_b - 2 x_a.x_b: replicate samples have a delta two orders of magnitude below
 // r / n, so the Gram form cancels, and on gfx950 the f32-input matrix instructions run at the f32 vector rate anyway.
 //
@@ -38,38 +38,17 @@
 //      translation below num_steps lr.
 //   3. --posterior-mean is parsed by the reference and never read; here it selects the point path (the *_points entries): x is the
 //      fixed log of the samples' posterior mean, no draws.
-//   4. W0 and the minibatches come from the host (polee_amd/tsne.py: NumPy generators keyed by the seed); draw index i uses
-//      seed + 0x9E3779B97F4A7C15 i: -1 for the bandwidth draw, t - 1 for Adam step t, T .. T+9 for the embedding after T steps.
+//   4. W0 and the minibatches come from the host (polee_amd/tsne.py: NumPy generators keyed by the seed); draw index i (DrawFeed)
+//      is -1 for the bandwidth draw, t - 1 for Adam step t, T .. T+9 for the embedding after T steps.
 // Parameters and moments are stored transposed, wT [C][n] (the ABI speaks W [n][C]).
-#include "common.hpp"
-#include "wave.hpp"
-
-#include <cmath>
+#include "draw_model.hpp"
 
 namespace polee {
 
-constexpr int TS_BLOCK = 256;
-constexpr int TS_WAVE_J = 128;  // transcripts per chunk of the projection kernel: one wave, two per lane
-constexpr int TS_TILE_S = 64;   // samples whose dz the gradient kernel stages in LDS at a time
 constexpr int TS_ROWS = 64;     // rows of a tile of the pairwise kernel
 constexpr int TS_SUB = 64;      // transcripts staged in LDS at a time
 constexpr int TS_SUBP = TS_SUB + 1;  // (an odd row pitch: the 16 rows a half-wave reads sit in 16 banks)
 constexpr int TS_CHUNK = 512;   // transcripts per workgroup of the pairwise kernel: the length of an f32 chain
-constexpr uint64_t TS_DRAW_STRIDE = 0x9E3779B97F4A7C15ull;  // draw i uses seed + stride * i (as polee_classify_fit)
-
-// every thread gets the sum over the workgroup of v, in a fixed order (red: TS_BLOCK doubles of LDS)
-__device__ inline double block_sum(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int o = TS_BLOCK / 2; o >= 1; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // tile pair number -> (ti, tj), ti <= tj < T, in the order (0,0) (0,1) .. (0,T-1) (1,1) ..
 __device__ inline void tile_pair(int tp, int T, int &ti, int &tj)
@@ -84,55 +63,27 @@ __device__ inline void tile_pair(int tp, int T, int &ti, int &tj)
 
 // part [nchunks][S][C], rpart [nchunks][S]: the chunk's sum of lx
 template <int KP>
-__global__ __launch_bounds__(TS_BLOCK) void tsne_project_kernel(int n, int S, int C, int nchunks, const float *__restrict__ x, int is_log,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_project_kernel(int n, int S, int C, int nchunks, const float *__restrict__ x, int is_log,
                                                                const float *__restrict__ W, float *__restrict__ part,
                                                                float *__restrict__ rpart)
 {
-    const int lane = threadIdx.x & 63;
-    const int chunk = blockIdx.x * (TS_BLOCK / 64) + (threadIdx.x >> 6);
-    if (chunk >= nchunks) return;  // (wave-uniform; the kernel has no barrier)
-    const int64_t j0 = (int64_t)chunk * TS_WAVE_J + lane, j1 = j0 + 64;
-    const bool a0 = j0 < n, a1 = j1 < n;
-    float w0[KP], w1[KP];
-#pragma unroll
-    for (int c = 0; c < KP; ++c) {
-        w0[c] = (a0 && c < C) ? W[(int64_t)c * n + j0] : 0.0f;
-        w1[c] = (a1 && c < C) ? W[(int64_t)c * n + j1] : 0.0f;
-    }
-    constexpr int PER = 64 / KP;
-    const int col = lane / PER;
-    const bool writer = (lane % PER) == 0 && col < C;
-    for (int s = 0; s < S; ++s) {
-        const float *xs = x + (int64_t)s * n;
-        const float v0 = a0 ? xs[j0] : 1.0f, v1 = a1 ? xs[j1] : 1.0f;
-        const float l0 = a0 ? (is_log ? v0 : logf(v0)) : 0.0f;
-        const float l1 = a1 ? (is_log ? v1 : logf(v1)) : 0.0f;
-        float p[KP];
-#pragma unroll
-        for (int c = 0; c < KP; ++c) p[c] = fmaf(l1, w1[c], l0 * w0[c]);
-        wave_split_reduce<KP>(p, lane);
-        float r = l0 + l1;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) r += __shfl_xor(r, off, 64);
-        if (writer) part[((int64_t)chunk * S + s) * C + col] = p[0];
-        if (lane == 0) rpart[(int64_t)chunk * S + s] = r;
-    }
+    chunk_project<KP, false, true>(n, S, C, nchunks, x, is_log, W, nullptr, part, nullptr, rpart);
 }
 
 // grid S.  z f64 [S][C]; zacc (or null) += z; mean - mhat -> resid, mhat (both 0 without use_vlr); pos[s] = the position of s in
 // idx [B], -1 when it is not in the batch (idx null: not written)
 template <int KP>
-__global__ __launch_bounds__(TS_BLOCK) void tsne_finish_kernel(int n, int S, int C, int nchunks, int use_vlr,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_finish_kernel(int n, int S, int C, int nchunks, int use_vlr,
                                                               const float *__restrict__ part, const float *__restrict__ rpart,
                                                               const int32_t *__restrict__ idx, int B, double *__restrict__ z,
                                                               double *__restrict__ zacc, float *__restrict__ mhat,
                                                               double *__restrict__ resid, int32_t *__restrict__ pos)
 {
-    __shared__ double red[TS_BLOCK];
+    __shared__ double red[DM_BLOCK];
     __shared__ int spos;
     const int tid = threadIdx.x, s = blockIdx.x;
     double r = 0.0;
-    for (int ch = tid; ch < nchunks; ch += TS_BLOCK) r += (double)rpart[(int64_t)ch * S + s];
+    for (int ch = tid; ch < nchunks; ch += DM_BLOCK) r += (double)rpart[(int64_t)ch * S + s];
     r = block_sum(r, red);
     if (tid == 0) {
         const double mean = use_vlr ? r / (double)n : 0.0;
@@ -141,24 +92,13 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_finish_kernel(int n, int S, int
         resid[s] = mean - (double)mh;
         spos = -1;
     }
-    constexpr int Q = TS_BLOCK / KP;
-    const int c = tid % KP, q = tid / KP;
-    double a = 0.0;
-    if (c < C)
-        for (int ch = q; ch < nchunks; ch += Q) a += (double)part[((int64_t)ch * S + s) * C + c];
-    __syncthreads();
-    red[tid] = a;
-    __syncthreads();
-    for (int o = Q / 2; o >= 1; o >>= 1) {
-        if (q < o) red[tid] += red[tid + o * KP];
-        __syncthreads();
-    }
+    chunk_sum<KP, true>(part, S, C, nchunks, s, red);
     if (tid < C) {
         z[(int64_t)s * C + tid] = red[tid];
         if (zacc) zacc[(int64_t)s * C + tid] += red[tid];
     }
     if (!idx) return;  // (uniform)
-    for (int b = tid; b < B; b += TS_BLOCK)
+    for (int b = tid; b < B; b += DM_BLOCK)
         if (idx[b] == s) spos = b;  // (at most one: the batch has no repeated index)
     __syncthreads();
     if (tid == 0) pos[s] = spos;
@@ -166,7 +106,7 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_finish_kernel(int n, int S, int
 
 // grid ntp * nchunks, workgroup tp * nchunks + chunk.  part [ntp][nchunks][64][64]: sum over the chunk's transcripts of
 // (c_a - c_b)^2, c = lx - mhat, for local rows a of tile ti and b of tile tj (rows past B and transcripts past n are staged as 0)
-__global__ __launch_bounds__(TS_BLOCK) void tsne_pairwise_kernel(int n, int B, int nchunks, const float *__restrict__ x, int is_log,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_pairwise_kernel(int n, int B, int nchunks, const float *__restrict__ x, int is_log,
                                                                 const int32_t *__restrict__ idx, const float *__restrict__ mhat,
                                                                 float *__restrict__ part)
 {
@@ -187,7 +127,7 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_pairwise_kernel(int n, int B, i
     const int64_t jend = jbeg + TS_CHUNK < n ? jbeg + TS_CHUNK : n;
     for (int64_t j0 = jbeg; j0 < jend; j0 += TS_SUB) {
         __syncthreads();
-        for (int e = tid; e < TS_ROWS * TS_SUB; e += TS_BLOCK) {  // (a wave: 64 consecutive transcripts of one row)
+        for (int e = tid; e < TS_ROWS * TS_SUB; e += DM_BLOCK) {  // (a wave: 64 consecutive transcripts of one row)
             const int r = e >> 6, jj = e & 63;
             const int64_t j = j0 + jj;
             const int pa = ti * TS_ROWS + r, pb = tj * TS_ROWS + r;
@@ -233,11 +173,11 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_pairwise_kernel(int n, int B, i
 }
 
 // grid ntp * 64, workgroup tp * 64 + local row a; thread (stripe q, local row b).  delta f64 [B][B], exactly symmetric, diagonal 0
-__global__ __launch_bounds__(TS_BLOCK) void tsne_delta_kernel(int n, int B, int nchunks, int use_vlr, const float *__restrict__ part,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_delta_kernel(int n, int B, int nchunks, int use_vlr, const float *__restrict__ part,
                                                              const int32_t *__restrict__ idx, const double *__restrict__ resid,
                                                              double *__restrict__ delta)
 {
-    __shared__ double red[TS_BLOCK];
+    __shared__ double red[DM_BLOCK];
     const int tid = threadIdx.x, rb = tid & 63, q = tid >> 6;
     const int ra = blockIdx.x % TS_ROWS;
     const int tp = blockIdx.x / TS_ROWS;
@@ -248,7 +188,7 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_delta_kernel(int n, int B, int 
     const float *src = part + (int64_t)tp * nchunks * (TS_ROWS * TS_ROWS) + ra * TS_ROWS + rb;
     double a = 0.0;
 #pragma unroll 4
-    for (int ch = q; ch < nchunks; ch += TS_BLOCK / 64) a += (double)src[(int64_t)ch * (TS_ROWS * TS_ROWS)];
+    for (int ch = q; ch < nchunks; ch += DM_BLOCK / 64) a += (double)src[(int64_t)ch * (TS_ROWS * TS_ROWS)];
     red[tid] = a;
     __syncthreads();
     if (q != 0 || pb >= B || pa > pb) return;
@@ -282,24 +222,24 @@ __device__ inline double tsne_D(const double *__restrict__ z, int C, int i, int 
 
 // grid B + S.  Workgroup b < B: cs[b] = sum_{a != b} E_ab, E_ab = clip(exp(-delta_ab / (2 sigma_b^2))): the divisor is the column's
 // (polee_tsne.py:145, :151).  Workgroup B + i: rowk[i] = sum_{j != i} (1 + D_ij / alpha)^(-(alpha + 1) / 2)   (:177-182)
-__global__ __launch_bounds__(TS_BLOCK) void tsne_sums_kernel(int S, int B, int C, double alpha, const double *__restrict__ delta,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_sums_kernel(int S, int B, int C, double alpha, const double *__restrict__ delta,
                                                             const int32_t *__restrict__ idx, const float *__restrict__ sigma,
                                                             const double *__restrict__ z, double *__restrict__ cs,
                                                             double *__restrict__ rowk)
 {
-    __shared__ double red[TS_BLOCK];
+    __shared__ double red[DM_BLOCK];
     const int tid = threadIdx.x;
     double a = 0.0;
     if ((int)blockIdx.x < B) {
         const int b = blockIdx.x;
         const double sg = (double)sigma[idx[b]];
-        for (int r = tid; r < B; r += TS_BLOCK)
+        for (int r = tid; r < B; r += DM_BLOCK)
             if (r != b) a += tsne_E(delta[(int64_t)r * B + b], sg);
         a = block_sum(a, red);
         if (tid == 0) cs[b] = a;
     } else {
         const int i = blockIdx.x - B;
-        for (int j = tid; j < S; j += TS_BLOCK)
+        for (int j = tid; j < S; j += DM_BLOCK)
             if (j != i) a += pow(1.0 + tsne_D(z, C, i, j) / alpha, -0.5 * (alpha + 1.0));
         a = block_sum(a, red);
         if (tid == 0) rowk[i] = a;
@@ -308,22 +248,22 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_sums_kernel(int S, int B, int C
 
 // grid B, workgroup = batch row a.  P_ab = (E_ab / cs_b + E_ba / cs_a) / (2 S) + eps (S, not B: polee_tsne.py:166), Q_ab = k_ab / Z
 // + eps with Z over ALL samples; R [B][B] = P / Q; lossrow[a] = sum_b P log(P / Q); trow[a] = sum_b R_ab k_ab / Z; Zout[0] = Z
-__global__ __launch_bounds__(TS_BLOCK) void tsne_loss_kernel(int S, int B, int C, double alpha, double eps,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_loss_kernel(int S, int B, int C, double alpha, double eps,
                                                             const double *__restrict__ delta, const int32_t *__restrict__ idx,
                                                             const float *__restrict__ sigma, const double *__restrict__ z,
                                                             const double *__restrict__ cs, const double *__restrict__ rowk,
                                                             double *__restrict__ R, double *__restrict__ lossrow,
                                                             double *__restrict__ trow, double *__restrict__ Zout)
 {
-    __shared__ double red[TS_BLOCK];
+    __shared__ double red[DM_BLOCK];
     const int tid = threadIdx.x, a = blockIdx.x;
     double zs = 0.0;
-    for (int i = tid; i < S; i += TS_BLOCK) zs += rowk[i];
+    for (int i = tid; i < S; i += DM_BLOCK) zs += rowk[i];
     const double Z = block_sum(zs, red);
     const int ia = idx[a];
     const double sga = (double)sigma[ia], csa = cs[a];
     double L = 0.0, T = 0.0;
-    for (int b = tid; b < B; b += TS_BLOCK) {
+    for (int b = tid; b < B; b += DM_BLOCK) {
         const int ib = idx[b];
         double p = 0.0, qv = 0.0;
         if (b != a) {
@@ -350,16 +290,16 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_loss_kernel(int S, int B, int C
 // dk/dD = -((alpha + 1) / (2 alpha)) (1 + D / alpha)^(-(alpha + 3) / 2), dz_i = 2 sum_j (dL/dD_ij + dL/dD_ji) (z_i - z_j).
 // Samples outside the batch get their gradient through Z.  Workgroup 0 writes the step's loss.
 template <int KP>
-__global__ __launch_bounds__(TS_BLOCK) void tsne_dz_kernel(int S, int B, int C, double alpha, const double *__restrict__ z,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_dz_kernel(int S, int B, int C, double alpha, const double *__restrict__ z,
                                                           const int32_t *__restrict__ pos, const double *__restrict__ R,
                                                           const double *__restrict__ lossrow, const double *__restrict__ trow,
                                                           const double *__restrict__ Zin, float *__restrict__ dz,
                                                           float *__restrict__ loss_out)
 {
-    __shared__ double red[TS_BLOCK];
+    __shared__ double red[DM_BLOCK];
     const int tid = threadIdx.x, i = blockIdx.x;
     double ts = 0.0, ls = 0.0;
-    for (int a = tid; a < B; a += TS_BLOCK) {
+    for (int a = tid; a < B; a += DM_BLOCK) {
         ts += trow[a];
         ls += lossrow[a];
     }
@@ -376,7 +316,7 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_dz_kernel(int S, int B, int C, 
         zi[c] = c < C ? z[(int64_t)i * C + c] : 0.0;
         acc[c] = 0.0;
     }
-    for (int j = tid; j < S; j += TS_BLOCK) {
+    for (int j = tid; j < S; j += DM_BLOCK) {
         if (j == i) continue;
         double d[KP], D = 0.0;
 #pragma unroll
@@ -400,40 +340,21 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_dz_kernel(int S, int B, int C, 
     }
 }
 
-// One thread per transcript: g[c] = sum_s lx[s][j] dz[s][c].  mode 0: Adam in the TF1 form (tf.train.AdamOptimizer,
-// polee_tsne.py:344-345: p -= lr_t m / (sqrt(v) + eps), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) from the host); mode 1: g to gout,
-// nothing is updated.  P, M, V, gout: [C][n]
+// One thread per transcript: g[c] = sum_s lx[s][j] dz[s][c].  mode 0: Adam (tf.train.AdamOptimizer, polee_tsne.py:344-345);
+// mode 1: g to gout, nothing is updated.  P, M, V, gout: [C][n]
 template <int KP>
-__global__ __launch_bounds__(TS_BLOCK) void tsne_grad_update_kernel(int n, int S, int C, const float *__restrict__ x, int is_log,
+__global__ __launch_bounds__(DM_BLOCK) void tsne_grad_update_kernel(int n, int S, int C, const float *__restrict__ x, int is_log,
                                                                    const float *__restrict__ dz, float *__restrict__ P,
                                                                    float *__restrict__ M, float *__restrict__ V, float lr_t, float b1,
                                                                    float b2, float eps, int mode, float *__restrict__ gout)
 {
-    __shared__ float sdz[TS_TILE_S * KP];
+    __shared__ float sdz[DM_TILE_S * KP];
     const int tid = threadIdx.x;
-    const int64_t j = (int64_t)blockIdx.x * TS_BLOCK + tid;
+    const int64_t j = (int64_t)blockIdx.x * DM_BLOCK + tid;
     const bool active = j < n;
     float acc[KP];
-#pragma unroll
-    for (int c = 0; c < KP; ++c) acc[c] = 0.0f;
-    for (int s0 = 0; s0 < S; s0 += TS_TILE_S) {
-        const int ns = min(TS_TILE_S, S - s0);
-        __syncthreads();
-        for (int e = tid; e < ns * KP; e += TS_BLOCK) {
-            const int s = e / KP, c = e % KP;
-            sdz[e] = c < C ? dz[(int64_t)(s0 + s) * C + c] : 0.0f;
-        }
-        __syncthreads();
-        if (active) {
-#pragma unroll 4
-            for (int s = 0; s < ns; ++s) {
-                const float v = x[(int64_t)(s0 + s) * n + j];
-                const float lx = is_log ? v : logf(v);
-#pragma unroll
-                for (int c = 0; c < KP; ++c) acc[c] = fmaf(lx, sdz[s * KP + c], acc[c]);
-            }
-        }
-    }
+    double unused;
+    grad_accumulate<KP, false, false>(n, S, C, x, is_log, dz, j, active, 0.0f, sdz, acc, unused);
     if (!active) return;
 #pragma unroll
     for (int c = 0; c < KP; ++c) {
@@ -444,18 +365,8 @@ __global__ __launch_bounds__(TS_BLOCK) void tsne_grad_update_kernel(int n, int S
             gout[i] = g;
             continue;
         }
-        const float m = b1 * M[i] + (1.0f - b1) * g;
-        const float v = b2 * V[i] + (1.0f - b2) * g * g;
-        M[i] = m;
-        V[i] = v;
-        P[i] = P[i] - lr_t * m / (sqrtf(v) + eps);
+        P[i] = tf_adam(P[i], &M[i], &V[i], g, lr_t, b1, b2, eps);
     }
-}
-
-__global__ void tsne_mean_kernel(int64_t count, const double *__restrict__ acc, double ndraws, float *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) out[i] = (float)(acc[i] / ndraws);
 }
 
 }  // namespace polee
@@ -535,27 +446,15 @@ polee_status need_sigmas(polee_tsne *ts)
 
 polee_status upload_points(polee_tsne *ts, const float *x)
 {
-    polee_ctx *ctx = ts->ctx;
-    if (!x) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne: null points");
-    const size_t sn = (size_t)ts->S * ts->n;
-    for (size_t i = 0; i < sn; ++i)
-        if (!std::isfinite(x[i]))
-            return fail(ctx, POLEE_ERR_NONFINITE, "polee_tsne: x[%zu][%zu] is not finite (the log of a zero point estimate?)", i / ts->n,
-                        i % ts->n);
-    return ts->d_x.upload(ctx, x, sn);
+    POLEE_TRY(check_points(ts->ctx, "polee_tsne", x, ts->S, ts->n));
+    return ts->d_x.upload(ts->ctx, x, (size_t)ts->S * ts->n);
 }
 
-polee_status check_approx(polee_tsne *ts, polee_approx *ap)
+// ap must be the model's S x n, on its context
+polee_status approx_fits(polee_tsne *ts, polee_approx *ap)
 {
-    polee_ctx *ctx = ts->ctx;
-    if (!ap) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne: null approximation handle");
-    int32_t S = 0, n = 0;
-    approx_dims(ap, &S, &n);
-    if (approx_ctx(ap) != ctx) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne: the approximation lives on another context");
-    if (n != ts->n || S != ts->S)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne: the approximation has S = %d, n = %d, the model S = %d, n = %d", S, n, ts->S,
-                    ts->n);
-    return POLEE_OK;
+    int32_t S = 0;
+    return check_approx(ts->ctx, "polee_tsne", ap, ts->n, ts->S, &S);
 }
 
 // z (and the row means) of one x; d_idx [B] or null
@@ -564,9 +463,9 @@ polee_status project_t(polee_tsne *ts, const float *d_x, int is_log, const int32
 {
     polee_ctx *ctx = ts->ctx;
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL((tsne_project_kernel<KP>), dim3((unsigned)ceil_div(ts->nchunks, TS_BLOCK / 64)), dim3(TS_BLOCK), 0, st, ts->n, ts->S,
+    hipLaunchKernelGGL((tsne_project_kernel<KP>), dim3((unsigned)ceil_div(ts->nchunks, DM_BLOCK / 64)), dim3(DM_BLOCK), 0, st, ts->n, ts->S,
                        ts->C, ts->nchunks, d_x, is_log, (const float *)ts->d_W.p, ts->d_part.p, ts->d_rpart.p);
-    hipLaunchKernelGGL((tsne_finish_kernel<KP>), dim3((unsigned)ts->S), dim3(TS_BLOCK), 0, st, ts->n, ts->S, ts->C, ts->nchunks,
+    hipLaunchKernelGGL((tsne_finish_kernel<KP>), dim3((unsigned)ts->S), dim3(DM_BLOCK), 0, st, ts->n, ts->S, ts->C, ts->nchunks,
                        ts->o.use_vlr, (const float *)ts->d_part.p, (const float *)ts->d_rpart.p, d_idx, B, ts->d_z.p,
                        accumulate ? ts->d_zacc.p : nullptr, ts->d_mhat.p, ts->d_resid.p, ts->d_pos.p);
     POLEE_KERNEL_CHECK(ctx);
@@ -580,9 +479,9 @@ polee_status pairwise(polee_tsne *ts, const float *d_x, int is_log, const int32_
     hipStream_t st = ctx->stream;
     const int nch = (int)ceil_div(ts->n, TS_CHUNK);
     const int64_t ntp = tile_pairs(B);
-    hipLaunchKernelGGL(tsne_pairwise_kernel, dim3((unsigned)(ntp * nch)), dim3(TS_BLOCK), 0, st, ts->n, B, nch, d_x, is_log, d_idx,
+    hipLaunchKernelGGL(tsne_pairwise_kernel, dim3((unsigned)(ntp * nch)), dim3(DM_BLOCK), 0, st, ts->n, B, nch, d_x, is_log, d_idx,
                        (const float *)ts->d_mhat.p, ts->d_pw.p);
-    hipLaunchKernelGGL(tsne_delta_kernel, dim3((unsigned)(ntp * TS_ROWS)), dim3(TS_BLOCK), 0, st, ts->n, B, nch, ts->o.use_vlr,
+    hipLaunchKernelGGL(tsne_delta_kernel, dim3((unsigned)(ntp * TS_ROWS)), dim3(DM_BLOCK), 0, st, ts->n, B, nch, ts->o.use_vlr,
                        (const float *)ts->d_pw.p, d_idx, (const double *)ts->d_resid.p, ts->d_delta.p);
     POLEE_KERNEL_CHECK(ctx);
     return POLEE_OK;
@@ -598,19 +497,17 @@ polee_status step_t(polee_tsne *ts, const float *d_x, int is_log, const int32_t 
     const int32_t S = ts->S, C = ts->C;
     POLEE_TRY(project_t<KP>(ts, d_x, is_log, d_idx, B, false));
     POLEE_TRY(pairwise(ts, d_x, is_log, d_idx, B));
-    hipLaunchKernelGGL(tsne_sums_kernel, dim3((unsigned)(B + S)), dim3(TS_BLOCK), 0, st, S, B, C, (double)o.alpha,
+    hipLaunchKernelGGL(tsne_sums_kernel, dim3((unsigned)(B + S)), dim3(DM_BLOCK), 0, st, S, B, C, (double)o.alpha,
                        (const double *)ts->d_delta.p, d_idx, (const float *)ts->d_sigma.p, (const double *)ts->d_z.p, ts->d_cs.p,
                        ts->d_rowk.p);
-    hipLaunchKernelGGL(tsne_loss_kernel, dim3((unsigned)B), dim3(TS_BLOCK), 0, st, S, B, C, (double)o.alpha, (double)o.eps,
+    hipLaunchKernelGGL(tsne_loss_kernel, dim3((unsigned)B), dim3(DM_BLOCK), 0, st, S, B, C, (double)o.alpha, (double)o.eps,
                        (const double *)ts->d_delta.p, d_idx, (const float *)ts->d_sigma.p, (const double *)ts->d_z.p,
                        (const double *)ts->d_cs.p, (const double *)ts->d_rowk.p, ts->d_R.p, ts->d_lossrow.p, ts->d_trow.p, ts->d_Z.p);
-    hipLaunchKernelGGL((tsne_dz_kernel<KP>), dim3((unsigned)S), dim3(TS_BLOCK), 0, st, S, B, C, (double)o.alpha,
+    hipLaunchKernelGGL((tsne_dz_kernel<KP>), dim3((unsigned)S), dim3(DM_BLOCK), 0, st, S, B, C, (double)o.alpha,
                        (const double *)ts->d_z.p, (const int32_t *)ts->d_pos.p, (const double *)ts->d_R.p,
                        (const double *)ts->d_lossrow.p, (const double *)ts->d_trow.p, (const double *)ts->d_Z.p, ts->d_dz.p, d_loss_out);
-    const double lr_t = mode == 0 ? (double)o.learning_rate * std::sqrt(1.0 - std::pow((double)o.beta2, (double)t)) /
-                                        (1.0 - std::pow((double)o.beta1, (double)t))
-                                  : 0.0;
-    hipLaunchKernelGGL((tsne_grad_update_kernel<KP>), dim3((unsigned)ceil_div(ts->n, TS_BLOCK)), dim3(TS_BLOCK), 0, st, ts->n, S, C, d_x,
+    const double lr_t = mode == 0 ? tf_adam_rate(o.learning_rate, o.beta1, o.beta2, t) : 0.0;
+    hipLaunchKernelGGL((tsne_grad_update_kernel<KP>), dim3((unsigned)ceil_div(ts->n, DM_BLOCK)), dim3(DM_BLOCK), 0, st, ts->n, S, C, d_x,
                        is_log, (const float *)ts->d_dz.p, ts->d_W.p, ts->d_M.p, ts->d_V.p, (float)lr_t, o.beta1, o.beta2, o.epsilon, mode,
                        ts->d_gout.p);
     POLEE_KERNEL_CHECK(ctx);
@@ -619,22 +516,12 @@ polee_status step_t(polee_tsne *ts, const float *d_x, int is_log, const int32_t 
 
 polee_status step(polee_tsne *ts, const float *d_x, int is_log, const int32_t *d_idx, int32_t B, int mode, int64_t t, float *d_loss_out)
 {
-    switch (ts->KP) {
-    case 2: return step_t<2>(ts, d_x, is_log, d_idx, B, mode, t, d_loss_out);
-    case 4: return step_t<4>(ts, d_x, is_log, d_idx, B, mode, t, d_loss_out);
-    case 8: return step_t<8>(ts, d_x, is_log, d_idx, B, mode, t, d_loss_out);
-    default: return step_t<16>(ts, d_x, is_log, d_idx, B, mode, t, d_loss_out);
-    }
+    return dispatch_kp(ts->KP, [&](auto kp) { return step_t<decltype(kp)::value>(ts, d_x, is_log, d_idx, B, mode, t, d_loss_out); });
 }
 
 polee_status project(polee_tsne *ts, const float *d_x, int is_log, const int32_t *d_idx, int32_t B, bool accumulate)
 {
-    switch (ts->KP) {
-    case 2: return project_t<2>(ts, d_x, is_log, d_idx, B, accumulate);
-    case 4: return project_t<4>(ts, d_x, is_log, d_idx, B, accumulate);
-    case 8: return project_t<8>(ts, d_x, is_log, d_idx, B, accumulate);
-    default: return project_t<16>(ts, d_x, is_log, d_idx, B, accumulate);
-    }
+    return dispatch_kp(ts->KP, [&](auto kp) { return project_t<decltype(kp)::value>(ts, d_x, is_log, d_idx, B, accumulate); });
 }
 
 polee_status distances_of(polee_tsne *ts, const float *d_x, int is_log, double *delta)
@@ -659,17 +546,7 @@ polee_status eval_of(polee_tsne *ts, const float *d_x, int is_log, int32_t B, fl
     if (!g_w) return POLEE_OK;
     std::vector<float> flat((size_t)ts->cn);
     POLEE_TRY(ts->d_gout.download(ctx, flat.data(), flat.size()));
-    for (int64_t j = 0; j < ts->n; ++j)
-        for (int64_t c = 0; c < ts->C; ++c) g_w[j * ts->C + c] = flat[(size_t)(c * ts->n + j)];
-    return POLEE_OK;
-}
-
-polee_status fit_finish(polee_tsne *ts, int32_t niter, float *loss_trace)
-{
-    polee_ctx *ctx = ts->ctx;
-    ts->t += niter;
-    if (loss_trace) return ts->d_loss.download(ctx, loss_trace, (size_t)niter);
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    wT_to_abi(flat.data(), ts->n, ts->C, g_w);
     return POLEE_OK;
 }
 
@@ -677,9 +554,7 @@ polee_status embed_finish(polee_tsne *ts, int32_t ndraws, float *z)
 {
     polee_ctx *ctx = ts->ctx;
     const int64_t sc = (int64_t)ts->S * ts->C;
-    hipLaunchKernelGGL(tsne_mean_kernel, dim3((unsigned)ceil_div(sc, TS_BLOCK)), dim3(TS_BLOCK), 0, ctx->stream, sc,
-                       (const double *)ts->d_zacc.p, (double)ndraws, ts->d_zout.p);
-    POLEE_KERNEL_CHECK(ctx);
+    POLEE_TRY(launch_acc_mean(ctx, sc, ts->d_zacc.p, ndraws, ts->d_zout.p));
     return ts->d_zout.download(ctx, z, (size_t)sc);
 }
 
@@ -719,8 +594,8 @@ polee_status polee_tsne_create(polee_ctx *ctx, int32_t n, int32_t S, const polee
         ts->n = n;
         ts->S = S;
         ts->C = C;
-        ts->KP = C <= 2 ? 2 : C <= 4 ? 4 : C <= 8 ? 8 : 16;
-        ts->nchunks = (int32_t)ceil_div(n, TS_WAVE_J);
+        ts->KP = kp_of(C);
+        ts->nchunks = (int32_t)ceil_div(n, DM_WAVE_J);
         ts->cn = (int64_t)C * n;
         ts->o = o;
         polee_status st = POLEE_OK;
@@ -772,52 +647,40 @@ void polee_tsne_destroy(polee_tsne *ts)
 
 polee_status polee_tsne_get_params(polee_tsne *ts, float *w)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_get_params: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_get_params", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ts, "polee_tsne_get_params", [&](polee_ctx *ctx) -> polee_status {
         if (!w) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_get_params: null argument");
         std::vector<float> flat((size_t)ts->cn);
         POLEE_TRY(ts->d_W.download(ctx, flat.data(), flat.size()));
-        for (int64_t j = 0; j < ts->n; ++j)
-            for (int64_t c = 0; c < ts->C; ++c) w[j * ts->C + c] = flat[(size_t)(c * ts->n + j)];
+        wT_to_abi(flat.data(), ts->n, ts->C, w);
         return POLEE_OK;
     });
 }
 
 polee_status polee_tsne_set_params(polee_tsne *ts, const float *w)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_set_params: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_set_params", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ts, "polee_tsne_set_params", [&](polee_ctx *ctx) -> polee_status {
         if (!w) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_set_params: null argument");
         std::vector<float> flat((size_t)ts->cn);
-        for (int64_t j = 0; j < ts->n; ++j)
-            for (int64_t c = 0; c < ts->C; ++c) flat[(size_t)(c * ts->n + j)] = w[j * ts->C + c];
+        abi_to_wT(w, ts->n, ts->C, flat.data());
         return ts->d_W.upload(ctx, flat);
     });
 }
 
 polee_status polee_tsne_reset(polee_tsne *ts)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_reset: null handle");
-    polee_ctx *ctx = ts->ctx;
-    POLEE_TRY(use_device(ctx));
-    const size_t bytes = (size_t)ts->cn * sizeof(float);
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(ts->d_M.p, 0, bytes, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(ts->d_V.p, 0, bytes, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ts->t = 0;
-    return POLEE_OK;
+    return entry(ts, "polee_tsne_reset", [&](polee_ctx *ctx) -> polee_status {
+        const size_t bytes = (size_t)ts->cn * sizeof(float);
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(ts->d_M.p, 0, bytes, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(ts->d_V.p, 0, bytes, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ts->t = 0;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_tsne_set_sigmas(polee_tsne *ts, const float *sigmas)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_set_sigmas: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_set_sigmas", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ts, "polee_tsne_set_sigmas", [&](polee_ctx *ctx) -> polee_status {
         if (!sigmas) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_set_sigmas: null argument");
         for (int32_t s = 0; s < ts->S; ++s)
             if (!(sigmas[s] > 0.0f) || !std::isfinite(sigmas[s]))
@@ -831,24 +694,20 @@ polee_status polee_tsne_set_sigmas(polee_tsne *ts, const float *sigmas)
 
 polee_status polee_tsne_distances(polee_tsne *ts, polee_approx *ap, const float *z0, uint64_t seed, double *delta)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_distances: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_distances", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
-        POLEE_TRY(check_approx(ts, ap));
+    return entry(ts, "polee_tsne_distances", [&](polee_ctx *ctx) -> polee_status {
+        POLEE_TRY(approx_fits(ts, ap));
         if (!delta) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_distances: null argument");
-        if (z0) POLEE_TRY(ts->d_z0.upload(ctx, z0, (size_t)ts->S * (ts->n - 1)));
-        POLEE_TRY(approx_sample_device(ap, z0 ? ts->d_z0.p : nullptr, seed));
-        return distances_of(ts, approx_draw_buffer(ap), 0, delta);
+        DrawFeed feed(ap, ts->d_z0, ts->S, ts->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, 1));
+        POLEE_TRY(feed.draw(0, 0, &d_x));
+        return distances_of(ts, d_x, 0, delta);
     });
 }
 
 polee_status polee_tsne_distances_points(polee_tsne *ts, const float *x, double *delta)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_distances_points: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_distances_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ts, "polee_tsne_distances_points", [&](polee_ctx *ctx) -> polee_status {
         if (!delta) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_distances_points: null argument");
         POLEE_TRY(upload_points(ts, x));
         return distances_of(ts, ts->d_x.p, 1, delta);
@@ -858,26 +717,22 @@ polee_status polee_tsne_distances_points(polee_tsne *ts, const float *x, double 
 polee_status polee_tsne_eval(polee_tsne *ts, polee_approx *ap, const int32_t *batch, int32_t B, const float *z0, uint64_t seed,
                              float *loss, float *g_w)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_eval: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_eval", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
-        POLEE_TRY(check_approx(ts, ap));
+    return entry(ts, "polee_tsne_eval", [&](polee_ctx *ctx) -> polee_status {
+        POLEE_TRY(approx_fits(ts, ap));
         if (!loss) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_eval: null argument");
         POLEE_TRY(need_sigmas(ts));
         POLEE_TRY(upload_batches(ts, batch, B, 1));
-        if (z0) POLEE_TRY(ts->d_z0.upload(ctx, z0, (size_t)ts->S * (ts->n - 1)));
-        POLEE_TRY(approx_sample_device(ap, z0 ? ts->d_z0.p : nullptr, seed));
-        return eval_of(ts, approx_draw_buffer(ap), 0, B, loss, g_w);
+        DrawFeed feed(ap, ts->d_z0, ts->S, ts->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, 1));
+        POLEE_TRY(feed.draw(0, 0, &d_x));
+        return eval_of(ts, d_x, 0, B, loss, g_w);
     });
 }
 
 polee_status polee_tsne_eval_points(polee_tsne *ts, const float *x, const int32_t *batch, int32_t B, float *loss, float *g_w)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_eval_points: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_eval_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ts, "polee_tsne_eval_points", [&](polee_ctx *ctx) -> polee_status {
         if (!loss) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_eval_points: null argument");
         POLEE_TRY(need_sigmas(ts));
         POLEE_TRY(upload_batches(ts, batch, B, 1));
@@ -891,36 +746,31 @@ polee_status polee_tsne_eval_points(polee_tsne *ts, const float *x, const int32_
 polee_status polee_tsne_fit(polee_tsne *ts, polee_approx *ap, const int32_t *batches, int32_t B, int32_t niter, uint64_t seed,
                             const float *z0, float *loss_trace)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_fit: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_fit", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
-        POLEE_TRY(check_approx(ts, ap));
+    return entry(ts, "polee_tsne_fit", [&](polee_ctx *ctx) -> polee_status {
+        POLEE_TRY(approx_fits(ts, ap));
         if (niter < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_fit: niter < 1");
         POLEE_TRY(need_sigmas(ts));
         POLEE_TRY(upload_batches(ts, batches, B, niter));
         POLEE_TRY(ts->d_loss.alloc(ctx, (size_t)niter));
-        const size_t sk = (size_t)ts->S * (ts->n - 1);
-        if (z0) POLEE_TRY(ts->d_z0.upload(ctx, z0, (size_t)niter * sk));  // (once, before the loop)
+        DrawFeed feed(ap, ts->d_z0, ts->S, ts->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)niter));
         for (int32_t it = 0; it < niter; ++it) {
             const int64_t t = ts->t + it + 1;
-            polee_status st = approx_sample_device(ap, z0 ? ts->d_z0.p + (size_t)it * sk : nullptr, seed + TS_DRAW_STRIDE * (uint64_t)(t - 1));
-            if (st == POLEE_OK) st = step(ts, approx_draw_buffer(ap), 0, ts->d_idx.p + (size_t)it * B, B, 0, t, ts->d_loss.p + it);
+            polee_status st = feed.draw((uint64_t)(t - 1), (size_t)it, &d_x);
+            if (st == POLEE_OK) st = step(ts, d_x, 0, ts->d_idx.p + (size_t)it * B, B, 0, t, ts->d_loss.p + it);
             if (st != POLEE_OK) {
                 ts->t += it;
                 return st;
             }
         }
-        return fit_finish(ts, niter, loss_trace);
+        return fit_finish(ctx, &ts->t, ts->d_loss, niter, loss_trace);
     });
 }
 
 polee_status polee_tsne_fit_points(polee_tsne *ts, const float *x, const int32_t *batches, int32_t B, int32_t niter, float *loss_trace)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_fit_points: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_fit_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ts, "polee_tsne_fit_points", [&](polee_ctx *ctx) -> polee_status {
         if (niter < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_fit_points: niter < 1");
         POLEE_TRY(need_sigmas(ts));
         POLEE_TRY(upload_batches(ts, batches, B, niter));
@@ -933,24 +783,22 @@ polee_status polee_tsne_fit_points(polee_tsne *ts, const float *x, const int32_t
                 return st;
             }
         }
-        return fit_finish(ts, niter, loss_trace);
+        return fit_finish(ctx, &ts->t, ts->d_loss, niter, loss_trace);
     });
 }
 
 polee_status polee_tsne_embed(polee_tsne *ts, polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0, float *z)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_embed: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_embed", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
-        POLEE_TRY(check_approx(ts, ap));
+    return entry(ts, "polee_tsne_embed", [&](polee_ctx *ctx) -> polee_status {
+        POLEE_TRY(approx_fits(ts, ap));
         if (!z || ndraws < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_embed: bad argument");
-        const size_t sk = (size_t)ts->S * (ts->n - 1);
-        if (z0) POLEE_TRY(ts->d_z0.upload(ctx, z0, (size_t)ndraws * sk));
+        DrawFeed feed(ap, ts->d_z0, ts->S, ts->n, seed);
+        const float *d_x = nullptr;
+        POLEE_TRY(feed.upload(z0, (size_t)ndraws));
         POLEE_HIP_TRY(ctx, hipMemsetAsync(ts->d_zacc.p, 0, (size_t)ts->S * ts->C * sizeof(double), ctx->stream));
         for (int32_t i = 0; i < ndraws; ++i) {
-            POLEE_TRY(approx_sample_device(ap, z0 ? ts->d_z0.p + (size_t)i * sk : nullptr, seed + TS_DRAW_STRIDE * (uint64_t)i));
-            POLEE_TRY(project(ts, approx_draw_buffer(ap), 0, nullptr, 0, true));
+            POLEE_TRY(feed.draw((uint64_t)i, (size_t)i, &d_x));
+            POLEE_TRY(project(ts, d_x, 0, nullptr, 0, true));
         }
         return embed_finish(ts, ndraws, z);
     });
@@ -958,10 +806,7 @@ polee_status polee_tsne_embed(polee_tsne *ts, polee_approx *ap, int32_t ndraws, 
 
 polee_status polee_tsne_embed_points(polee_tsne *ts, const float *x, float *z)
 {
-    if (!ts) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_embed_points: null handle");
-    polee_ctx *ctx = ts->ctx;
-    return guarded(ctx, "polee_tsne_embed_points", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ts, "polee_tsne_embed_points", [&](polee_ctx *ctx) -> polee_status {
         if (!z) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_embed_points: null argument");
         POLEE_TRY(upload_points(ts, x));
         POLEE_HIP_TRY(ctx, hipMemsetAsync(ts->d_zacc.p, 0, (size_t)ts->S * ts->C * sizeof(double), ctx->stream));

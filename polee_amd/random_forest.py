@@ -16,10 +16,10 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import arr, check, f32p, f64p, i32p, i64p, ptr
+from ._model import MASK, Handle, approx_of, make_opts, z0_flat
 
 DEFAULT_SEED = 12345       # models/random-forest.jl:84-87
 FOREST_MAX_ROWS = 8192     # POLEE_FOREST_MAX_ROWS (include/polee_hip.h)
-_MASK = (1 << 64) - 1
 
 
 class ForestOpts(C.Structure):
@@ -55,13 +55,7 @@ def _bind():
 
 def forest_opts(**kw):
     """the reference's defaults (200 trees, 10 sqrt(n) candidate features, full bootstrap), overridden by keyword"""
-    o = ForestOpts()
-    _bind().polee_forest_default_opts(C.byref(o))
-    for name, v in kw.items():
-        if name not in dict(ForestOpts._fields_):
-            raise TypeError("unknown option %r" % name)
-        setattr(o, name, v)
-    return o
+    return make_opts(ForestOpts, _bind().polee_forest_default_opts, kw)
 
 
 def _node_arrays(nodes):
@@ -84,7 +78,7 @@ def build_forest_host(x, labels, k, seed=DEFAULT_SEED, **opts):
     feature, left, right, label = (np.zeros(cap, np.int32) for _ in range(4))
     threshold = np.zeros(cap, np.float64)
     nn = C.c_int64()
-    check(lib.polee_forest_build_host(ptr(x, f32p), ptr(labels, i32p), N, n, int(k), C.byref(o), C.c_uint64(seed & _MASK), cap, C.byref(nn),
+    check(lib.polee_forest_build_host(ptr(x, f32p), ptr(labels, i32p), N, n, int(k), C.byref(o), C.c_uint64(seed & MASK), cap, C.byref(nn),
                                       ptr(off, i64p), ptr(feature, i32p), ptr(threshold, f64p), ptr(left, i32p), ptr(right, i32p),
                                       ptr(label, i32p)))
     c = nn.value
@@ -105,18 +99,17 @@ def forest_votes_host(nodes, x, k):
 def log_draws(ap, ndraws, seed=DEFAULT_SEED, z0=None):
     """f32 [ndraws S, n]: the rows fit_sample trains on and predict_sample walks (row d S + s = the device's log of draw d of sample s)"""
     lib = _bind()
-    z = None if z0 is None else arr(z0, np.float32).reshape(-1)
-    if z is not None and z.size != ndraws * ap.S * (ap.n - 1):
-        raise ValueError("z0 must hold %d values" % (ndraws * ap.S * (ap.n - 1)))
+    z = z0_flat(z0, ndraws * ap.S * (ap.n - 1))
     out = np.empty((ndraws * ap.S, ap.n), np.float32)
-    check(lib.polee_forest_log_draws(ap._h, int(ndraws), C.c_uint64(seed & _MASK), ptr(z, f32p), ptr(out, f32p)), ap.ctx._h)
+    check(lib.polee_forest_log_draws(ap._h, int(ndraws), C.c_uint64(seed & MASK), ptr(z, f32p), ptr(out, f32p)), ap.ctx._h)
     return out
 
 
-class RNASeqRandomForest:
+class RNASeqRandomForest(Handle):
     """A forest of k classes on n features.  Options: ntrees, nsubfeatures, partial_sampling, max_depth, min_samples_leaf,
     min_samples_split.  host=True builds and predicts on the host and takes points only (no GPU, no context).
     Labels are class numbers 0 .. k-1, or one-hot rows [S, k]."""
+    _destroy = "polee_forest_destroy"
 
     def __init__(self, k, n, ctx=None, host=False, **opts):
         self.k, self.n, self.host = int(k), int(n), bool(host)
@@ -131,14 +124,6 @@ class RNASeqRandomForest:
             check(_bind().polee_forest_create(self.ctx._h, self.n, self.k, C.byref(self.opts), C.byref(self._h)), self.ctx._h)
         elif not 2 <= self.k <= 16:
             raise ValueError("2..16 classes are supported")
-
-    def __del__(self):
-        try:
-            if self._h:
-                _bind().polee_forest_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def _labels(self, y, S):
         y = np.asarray(y)
@@ -158,8 +143,7 @@ class RNASeqRandomForest:
         return x
 
     def _lik(self, vars):
-        from .classify import _approx
-        ap = _approx(vars, self.ctx)
+        ap = approx_of(vars, self.ctx)
         if ap.n != self.n:
             raise ValueError("the approximation has n = %d, the forest n = %d" % (ap.n, self.n))
         return ap
@@ -199,7 +183,7 @@ class RNASeqRandomForest:
         if self.host:
             self._nodes = build_forest_host(x, y, self.k, seed, **self._opts_kw)
             return self
-        check(_bind().polee_forest_fit_points(self._h, ptr(x, f32p), ptr(y, i32p), x.shape[0], C.c_uint64(seed & _MASK)), self.ctx._h)
+        check(_bind().polee_forest_fit_points(self._h, ptr(x, f32p), ptr(y, i32p), x.shape[0], C.c_uint64(seed & MASK)), self.ctx._h)
         return self
 
     def fit_sample(self, vars, labels, ndraws=20, draw_seed=DEFAULT_SEED, seed=DEFAULT_SEED + 1, z0=None):
@@ -208,10 +192,8 @@ class RNASeqRandomForest:
             raise ValueError("host=True takes points only: feed fit() the rows of log_draws()")
         ap = self._lik(vars)
         y = self._labels(labels, ap.S)
-        z = None if z0 is None else arr(z0, np.float32).reshape(-1)
-        if z is not None and z.size != ndraws * ap.S * (ap.n - 1):
-            raise ValueError("z0 must hold %d values" % (ndraws * ap.S * (ap.n - 1)))
-        check(_bind().polee_forest_fit(self._h, ap._h, ptr(y, i32p), int(ndraws), C.c_uint64(draw_seed & _MASK), C.c_uint64(seed & _MASK),
+        z = z0_flat(z0, ndraws * ap.S * (ap.n - 1))
+        check(_bind().polee_forest_fit(self._h, ap._h, ptr(y, i32p), int(ndraws), C.c_uint64(draw_seed & MASK), C.c_uint64(seed & MASK),
                                        ptr(z, f32p)), self.ctx._h)
         return self
 
@@ -230,11 +212,9 @@ class RNASeqRandomForest:
         if self.host:
             raise ValueError("host=True takes points only")
         ap = self._lik(vars)
-        z = None if z0 is None else arr(z0, np.float32).reshape(-1)
-        if z is not None and z.size != ndraws * ap.S * (ap.n - 1):
-            raise ValueError("z0 must hold %d values" % (ndraws * ap.S * (ap.n - 1)))
+        z = z0_flat(z0, ndraws * ap.S * (ap.n - 1))
         v = np.zeros((ap.S, self.k), np.int32)
-        check(_bind().polee_forest_predict(self._h, ap._h, int(ndraws), C.c_uint64(seed & _MASK), ptr(z, f32p), ptr(v, i32p)), self.ctx._h)
+        check(_bind().polee_forest_predict(self._h, ap._h, int(ndraws), C.c_uint64(seed & MASK), ptr(z, f32p), ptr(v, i32p)), self.ctx._h)
         return v
 
     def ntrees(self):

@@ -21,15 +21,14 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import arr, check, f32p, f64p, i32p, ptr
-from .core import RNASeqApproxLikelihood, default_context
+from ._model import MASK, Handle, approx_of, draw_seed, make_opts, z0_flat
+from .core import default_context
 
 NUM_STEPS = 500            # models/polee_tsne.py:355
 EMBED_DRAWS = 10           # models/polee_tsne.py:393
 TARGET_PERPLEXITY = 50.0   # models/polee_tsne.py:216
 BATCH_SIZE = 100           # models/tsne.jl:41-45
 DEFAULT_SEED = 123456789
-_DRAW_STRIDE = 0x9E3779B97F4A7C15
-_MASK = (1 << 64) - 1
 
 
 class TSNEOpts(C.Structure):
@@ -78,44 +77,22 @@ def find_sigmas(delta, target_perplexity):
     return sigmas
 
 
-def _approx(vars, ctx):
-    if isinstance(vars, dict) and isinstance(vars.get("approx"), RNASeqApproxLikelihood):
-        return vars["approx"]
-    return vars if isinstance(vars, RNASeqApproxLikelihood) else RNASeqApproxLikelihood(vars, ctx=ctx)
-
-
-class RNASeqTSNE:
+class RNASeqTSNE(Handle):
     """The embedding of estimate_tsne (models/polee_tsne.py:213-398): W [n, C], zero until set_params.  Every method takes either
     `vars` (LoadedSamples.variables, an RNASeqApproxLikelihood, or the dict of create_tensorflow_variables!: a fresh draw) or `x`
     [S, n] (log expression already: the point path).  Options (num_components, use_vlr, alpha, eps, learning_rate, beta1, beta2,
     epsilon) default to the reference's.  `seed`, `z0` and the explicit batches are additions: the draw with index i uses
     seed + 0x9E3779B97F4A7C15 i, z0 replaces the device's N(0,1) noise."""
+    _destroy = "polee_tsne_destroy"
 
     def __init__(self, n, num_samples, ctx=None, **opts):
         self.n, self.S = int(n), int(num_samples)
         self.ctx = ctx or default_context()
         self._h = C.c_void_p()
         self.t = 0  # (mirror of the handle's step clock)
-        lib = L.lib()
-        lib.polee_tsne_default_opts.restype = None
-        self.opts = TSNEOpts()
-        lib.polee_tsne_default_opts(C.byref(self.opts))
-        for name, v in opts.items():
-            if name not in dict(TSNEOpts._fields_):
-                raise TypeError("unknown option %r" % name)
-            setattr(self.opts, name, v)
+        self.opts = make_opts(TSNEOpts, L.lib().polee_tsne_default_opts, opts)
         self.C = int(self.opts.num_components)
-        check(lib.polee_tsne_create(self.ctx._h, self.n, self.S, C.byref(self.opts), C.byref(self._h)), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                f = L.lib().polee_tsne_destroy
-                f.restype, f.argtypes = None, [C.c_void_p]
-                f(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+        check(L.lib().polee_tsne_create(self.ctx._h, self.n, self.S, C.byref(self.opts), C.byref(self._h)), self.ctx._h)
 
     # ---- parameters
     def get_params(self):
@@ -149,18 +126,13 @@ class RNASeqTSNE:
         return x
 
     def _lik(self, vars):
-        ap = _approx(vars, self.ctx)
+        ap = approx_of(vars, self.ctx)
         if ap.n != self.n or ap.S != self.S:
             raise ValueError("the approximation is [%d, %d], the model [%d, %d]" % (ap.S, ap.n, self.S, self.n))
         return ap
 
     def _z0(self, z0, draws):
-        if z0 is None:
-            return None
-        z = arr(z0, np.float32).reshape(-1)
-        if z.size != draws * self.S * (self.n - 1):
-            raise ValueError("z0 must hold %d values" % (draws * self.S * (self.n - 1)))
-        return z
+        return z0_flat(z0, draws * self.S * (self.n - 1))
 
     @staticmethod
     def _batches(batches):
@@ -179,13 +151,13 @@ class RNASeqTSNE:
         else:
             ap = self._lik(vars)
             z = self._z0(z0, 1)
-            check(L.lib().polee_tsne_distances(self._h, ap._h, ptr(z, f32p), C.c_uint64(seed & _MASK), ptr(delta, f64p)), self.ctx._h)
+            check(L.lib().polee_tsne_distances(self._h, ap._h, ptr(z, f32p), C.c_uint64(seed & MASK), ptr(delta, f64p)), self.ctx._h)
         return delta
 
     def find_sigmas(self, vars=None, x=None, target_perplexity=TARGET_PERPLEXITY, seed=DEFAULT_SEED, z0=None):
         """find_sigmas (:64-103, :236-238) on ONE draw of all samples (draw index -1), in float64 on the host from the device's
         distance matrix; the target is min(target_perplexity, S - 1).  Sets and returns the bandwidths f32 [S]."""
-        delta = self.distances(vars, x, seed=(seed - _DRAW_STRIDE) & _MASK, z0=z0)
+        delta = self.distances(vars, x, seed=draw_seed(seed, -1), z0=z0)
         sigmas = find_sigmas(delta, min(float(target_perplexity), float(self.S) - 1.0))
         self.set_sigmas(sigmas)
         return sigmas
@@ -202,7 +174,7 @@ class RNASeqTSNE:
         else:
             ap = self._lik(vars)
             z = self._z0(z0, 1)
-            check(L.lib().polee_tsne_eval(self._h, ap._h, ptr(b, i32p), b.size, ptr(z, f32p), C.c_uint64(seed & _MASK), ptr(loss, f32p),
+            check(L.lib().polee_tsne_eval(self._h, ap._h, ptr(b, i32p), b.size, ptr(z, f32p), C.c_uint64(seed & MASK), ptr(loss, f32p),
                                           ptr(gw, f32p)), self.ctx._h)
         return float(loss[0]), gw
 
@@ -223,7 +195,7 @@ class RNASeqTSNE:
         else:
             ap = self._lik(vars)
             z = self._z0(z0, niter)
-            check(L.lib().polee_tsne_fit(self._h, ap._h, ptr(b, i32p), b.shape[1], niter, C.c_uint64(seed & _MASK), ptr(z, f32p),
+            check(L.lib().polee_tsne_fit(self._h, ap._h, ptr(b, i32p), b.shape[1], niter, C.c_uint64(seed & MASK), ptr(z, f32p),
                                          ptr(trace, f32p)), self.ctx._h)
         self.t += niter
         return trace
@@ -237,7 +209,7 @@ class RNASeqTSNE:
         else:
             ap = self._lik(vars)
             zz = self._z0(z0, int(ndraws))
-            check(L.lib().polee_tsne_embed(self._h, ap._h, int(ndraws), C.c_uint64(seed & _MASK), ptr(zz, f32p), ptr(z, f32p)),
+            check(L.lib().polee_tsne_embed(self._h, ap._h, int(ndraws), C.c_uint64(seed & MASK), ptr(zz, f32p), ptr(z, f32p)),
                   self.ctx._h)
         return z
 
@@ -253,7 +225,7 @@ def estimate_tsne(vars, num_components=2, batch_size=BATCH_SIZE, x0_log=None, us
         S, n = x.shape
         src = dict(x=x)
     else:
-        ap = _approx(vars, ctx)
+        ap = approx_of(vars, ctx)
         S, n = ap.S, ap.n
         src = dict(vars=ap)
     ts = RNASeqTSNE(n, S, ctx=ctx, num_components=int(num_components), use_vlr=int(bool(use_vlr)), alpha=alpha,
@@ -261,7 +233,7 @@ def estimate_tsne(vars, num_components=2, batch_size=BATCH_SIZE, x0_log=None, us
     ts.find_sigmas(target_perplexity=target_perplexity, seed=seed, **src)
     ts.set_params(initial_weights(seed, n, num_components))
     trace = ts.fit(num_steps, batch_size=batch_size, seed=seed, **src)
-    z = ts.embed(seed=(seed + _DRAW_STRIDE * int(num_steps)) & _MASK, **src)
+    z = ts.embed(seed=draw_seed(seed, num_steps), **src)
     return (z, trace) if return_trace else z
 
 
