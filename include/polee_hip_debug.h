@@ -98,6 +98,12 @@ polee_status polee_debug_fast_log(polee_ctx *ctx, const double *x, int64_t count
 /* fast_exp (csrc/scan.hpp), the double-precision exp of the VI loop's forward kernel (leaf u = exp of a path sum of edge logs) */
 polee_status polee_debug_fast_exp(polee_ctx *ctx, const double *x, int64_t count, double *out);
 
+/* Per-node intermediates of the approximation density (csrc/approx.hip) as the last polee_approx_logprob call WITH a gradient left
+ * them on the device: tpair f64 [S][n-1][2] = the two tour terms of InvHSBGrad of every internal node k (the plan's node order;
+ * [0]: the edge to its right child, leaves [lo, mid), [1]: to its left child, [mid, hi1)), bp f32 [S][n] = d / d q per transcript.
+ * Copies the two buffers; launches no kernel. */
+polee_status polee_debug_approx_node_terms(polee_approx *ap, double *tpair, float *bp);
+
 /* Draws per workgroup of the VI loop's forward and backward tree kernels (csrc/vi_fused.hpp, DrawSplit) for the steps that follow:
  * num_mc_samples, or 3, 2, 1 where that is below it; 0 = the library's own choice.  Every split computes the same bits
  * (tests/test_gpu_vi_draw_split.py); the library's choice is the fastest one measured.  The update kernel has no split (a lane per

@@ -965,6 +965,15 @@ class RNASeqApproxLikelihood:
         check(L.lib().polee_approx_logprob(self._h, ptr(x, f32p), ptr(lp, f32p), ptr(g, f32p)), self.ctx._h)
         return (lp, g) if want_grad else lp
 
+    def debug_node_terms(self):
+        """Test hook (include/polee_hip_debug.h): what the last log_prob(x, want_grad=True) left on the device -- tpair f64
+        [S,n-1,2], the two tour terms of every internal node (the tree plan's node order; [..., 0] the edge to the right
+        child), and bp f32 [S,n], the tree gradient d / d q per transcript."""
+        tpair = np.empty((self.S, self.n - 1, 2), np.float64)
+        bp = np.empty((self.S, self.n), np.float32)
+        check(L.lib().polee_debug_approx_node_terms(self._h, ptr(tpair, L.f64p), ptr(bp, f32p)), self.ctx._h)
+        return tpair, bp
+
     def gene_log_prob(self, x_gene, x_isoform, feature_idxs, want_grad=False):
         """RNASeqGeneApproxLikelihoodDist._log_prob (polee_gene_expression.py:14-90): the density reached through
         gene-level expression x_gene [S,G] and within-gene isoform log-expression x_isoform [S,n].

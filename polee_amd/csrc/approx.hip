@@ -11,6 +11,7 @@
 //   (grad) finish    : chain through q = r/R, r = p*l, p = softmax(x):
 //                      x_grad_j = q_j (bp_j - <bp,q> - 1) + 1 - (n-2) p_j
 #include "ptt_internal.hpp"
+#include "../../include/polee_hip_debug.h"
 
 #include <cmath>
 
@@ -66,8 +67,8 @@ struct ApproxLeafLoad {
 
 // npart[s][block] = lp + ladj contributions of the block's internal nodes (summed by approx_finish_lp_kernel: one
 // same-address atomic per block serialised ~800 deep per sample and dominated this kernel)
-// tpair (optional) [S][n-1][2]: the node's two tour terms of InvHSBGrad, -1/u -+ ..., for its left ([0]) and right ([1])
-// edge -- one 8-byte gather per tour element in the scan instead of three plus arithmetic
+// tpair (optional) [S][n-1][2]: the node's two tour terms of InvHSBGrad, -1/u -+ ..., for the edge to its right ([0]) and to its left
+// ([1], bit 3 of the tour code) child -- one 8-byte gather per tour element in the scan instead of three plus arithmetic
 // 1 / x by the hardware estimate and two Newton steps (~1 ulp) for normal positive x; anything else (0, denormal, inf, nan) through the
 // division, whose special cases the callers' tests pin
 __device__ inline double approx_rcp(double x)
@@ -656,6 +657,17 @@ polee_status polee_approx_logprob(polee_approx *ap, const float *x, float *lp, f
     POLEE_TRY(ap->d_lp.download(ctx, lp, ap->S));
     if (x_grad) POLEE_TRY(ap->d_xgrad.download(ctx, x_grad, sn));
     return POLEE_OK;
+}
+
+// test hook (include/polee_hip_debug.h): the node terms and the tree gradient the last call with a gradient left on the device
+polee_status polee_debug_approx_node_terms(polee_approx *ap, double *tpair, float *bp)
+{
+    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
+    polee_ctx *ctx = ap->ctx;
+    POLEE_TRY(use_device(ctx));
+    if (!tpair || !bp) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
+    POLEE_TRY(ap->d_tpair.download(ctx, tpair, 2 * (size_t)ap->S * (size_t)(ap->n - 1)));
+    return ap->d_bp.download(ctx, bp, (size_t)ap->S * (size_t)ap->n);
 }
 
 polee_status polee_approx_gene_logprob(polee_approx *ap, const float *x_gene, const float *x_isoform,
