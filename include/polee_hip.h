@@ -820,6 +820,74 @@ typedef struct {
 } polee_em_info;
 polee_status polee_em_get_info(polee_em *em, int compute_kkt, polee_em_info *info);
 
+/* ---- the alternative approximations (`prep --approx-method`, src/main.jl:5-23; src/likelihood-approximation-alt.jl) ------------
+ * The baselines the default approximation is judged against.  One handle runs the VI loop of a method on an existing polee_loglik,
+ * which it keeps alive (csrc/altvi.hip): K draws per step through ONE sparse pass, the method's chain rule,
+ * the reference's ADAM (likelihood-approximation.jl:107-146) on two parameter vectors of n - 1 values, no host synchronisation
+ * inside polee_altvi_run.  None of the methods applies the effective-length Jacobian (they call log_likelihood directly).
+ * Built: logistic_normal (likelihood-approximation-alt.jl:50-203), normal_ilr (:503-616, isometric_log_ratios.jl:43-128) and
+ * normal_alr (:619-736, additive_log_ratios.jl:12-71); their parameters are mu, omega.  The two Polya-tree alternatives are named
+ * here so that the numbering is the reference's list, and answered with POLEE_ERR_UNSUPPORTED.
+ * Like polee_em, a handle uses its loglik's one evaluation slot while steps are in flight. */
+enum {
+    POLEE_ALT_LOGISTIC_NORMAL = 1,  /* LogisticNormalApprox                                   */
+    POLEE_ALT_KUMARASWAMY_PTT = 2,  /* KumaraswamyPTTApprox (:331-498): not built             */
+    POLEE_ALT_LOGIT_NORMAL_PTT = 3, /* LogitNormalPTTApprox (:208-328): not built             */
+    POLEE_ALT_NORMAL_ILR = 4,       /* NormalILRApprox; needs a tree                          */
+    POLEE_ALT_NORMAL_ALR = 5        /* NormalALRApprox                                        */
+};
+typedef struct polee_altvi polee_altvi;
+typedef struct {
+    int32_t method;              /* POLEE_ALT_*                                                                        */
+    int32_t num_steps;           /* LIKAP_NUM_STEPS = 500                                                              */
+    int32_t num_mc_samples;      /* LIKAP_NUM_MC_SAMPLES = 6 (1..8)                                                    */
+    int32_t gradonly;            /* default 1: no ELBO / log-likelihood trace                                          */
+    int32_t refidx;              /* normal_alr: 1-based reference element, -1 = n (likelihood-approximation-alt.jl:641) */
+    int32_t reserved;
+    uint64_t seed;               /* device Philox seed                                                                 */
+    const float *z0;             /* optional HOST noise [num_steps][num_mc][n-1]; replaces the device RNG              */
+    double eps;                  /* clamp of xs to [eps, 1 - eps], 1e-10 (:109, 133)                                   */
+    double adam_initial_learning_rate, adam_learning_rate_decay, adam_min_learning_rate, adam_eps, adam_rv, adam_rm;
+    double max_step0, max_step1; /* ss_max_*_step: 2e-2 for logistic_normal (:66-67), 2e-1 for ILR and ALR (:520-521, 637-638) */
+} polee_altvi_opts;
+/* the reference's constants of `method` */
+void polee_altvi_default_opts(int32_t method, polee_altvi_opts *opts);
+typedef struct {
+    int32_t steps_done;
+    int32_t nonfinite_step; /* first step with a non-finite gradient, 0 if none */
+    double last_elbo;       /* !gradonly */
+    double last_lp_mean;    /* !gradonly */
+} polee_altvi_stats;
+/* Initial values: mu = 0; omega = 0.1 for logistic_normal (:79 -- not log 0.1), log(0.1f0) for ILR and ALR (:536, 655).
+ * t_or_null: the tree of normal_ilr (ILRTransform, isometric_log_ratios.jl:3-31), ignored by the other two. */
+polee_status polee_altvi_create(polee_loglik *ll, polee_ptt *t_or_null, const polee_altvi_opts *opts, polee_altvi **out);
+void polee_altvi_destroy(polee_altvi *a);
+/* enqueues nsteps iterations on the context's stream without host synchronisation */
+polee_status polee_altvi_run(polee_altvi *a, int32_t nsteps);
+/* waits for the stream; POLEE_ERR_NONFINITE if a step met a non-finite gradient */
+polee_status polee_altvi_sync(polee_altvi *a);
+/* the two parameter vectors, f32 [n-1] each (mu, omega); either pointer may be NULL */
+polee_status polee_altvi_get_params(polee_altvi *a, float *p0, float *p1);
+polee_status polee_altvi_set_params(polee_altvi *a, const float *p0, const float *p1);
+polee_status polee_altvi_get_stats(polee_altvi *a, polee_altvi_stats *stats);
+/* !gradonly: per step the reference's elbo -- logistic_normal: the LAST draw's lp + ladj over K (an assignment in the draw loop,
+ * :162, 180); ILR and ALR: the mean over the draws (:579, 698) -- and the mean log-likelihood.  Either pointer may be NULL. */
+polee_status polee_altvi_get_trace(polee_altvi *a, double *elbo, double *lp_mean);
+/* the noise of 1-based `step`: z0 f32 [K][n-1] */
+polee_status polee_altvi_export_noise(polee_altvi *a, int32_t step, float *z0);
+/* Test hook: the K draws of the NEXT step at the current parameters, nothing updated.  Any output may be NULL.  xs [K][n],
+ * x_grad [K][n], y_grad [K][n-1], the two averaged parameter gradients [n-1], lp [K], ladj [K]. */
+polee_status polee_altvi_eval_gradients(polee_altvi *a, float *xs, double *x_grad, double *y_grad, float *p0_grad, float *p1_grad,
+                                        double *lp, double *ladj);
+/* sample_likap (src/evaluate.jl:34-74, 203-275): `count` draws through the fit's forward kernels, each divided by the effective
+ * lengths and renormalised; out f32 [count][n].  p0, p1 = mu, omega (sigma = exp(omega), for logistic_normal too, :37);
+ * refidx as in polee_altvi_opts; z0_or_null: HOST noise [count][n-1]. */
+polee_status polee_alt_sample(polee_ctx *ctx, int32_t method, polee_ptt *t_or_null, int32_t n, const float *p0, const float *p1,
+                              const float *efflens, int32_t refidx, int32_t count, uint64_t seed, const float *z0_or_null, float *out);
+/* a = sqrt(s / (r (r + s))), b = -sqrt(r / (s (r + s))) for r, s leaves below the left and right child of every internal node
+ * (isometric_log_ratios.jl:62-66); ab f64 [count][2].  Host only. */
+polee_status polee_ilr_coefficients(const int32_t *r, const int32_t *s, int64_t count, double *ab);
+
 /* ---- `polee sample` (src/main.jl:239-289 flags, :756-919 handler) ----------------------------------------------------------------
  * A stream of draws from one fitted approximation with everything the command does after the draw: the effective-length adjustment
  * (xs ./= efflens; xs ./= sum(xs), main.jl:850-853), the running posterior mean (:857) and prop_to_counts (:859-880), on the device.

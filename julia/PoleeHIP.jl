@@ -1706,4 +1706,103 @@ function estimate_isoform_effect_sizes(fx::IsoformEffects, qw_loc::Vector{Float3
     return mn, me, pr, amn, ame, apr, ms[]
 end
 
+# ---- the alternative approximations (src/likelihood-approximation-alt.jl; `prep --approx-method`) ---------------------------------
+const ALT_LOGISTIC_NORMAL, ALT_KUMARASWAMY_PTT, ALT_LOGIT_NORMAL_PTT, ALT_NORMAL_ILR, ALT_NORMAL_ALR = Int32(1), Int32(2), Int32(3), Int32(4), Int32(5)
+
+"mirror of `polee_altvi_opts` (include/polee_hip.h): field order and types must stay in step with the header"
+mutable struct AltViOpts
+    method::Int32; num_steps::Int32; num_mc_samples::Int32; gradonly::Int32; refidx::Int32; reserved::Int32
+    seed::UInt64; z0::Ptr{Float32}; eps::Float64
+    adam_initial_learning_rate::Float64; adam_learning_rate_decay::Float64; adam_min_learning_rate::Float64
+    adam_eps::Float64; adam_rv::Float64; adam_rm::Float64
+    max_step0::Float64; max_step1::Float64
+    AltViOpts(method::Integer) = (o = new(); ccall((:polee_altvi_default_opts, LIB), Cvoid, (Int32, Ref{AltViOpts}), method, o); o)
+end
+mutable struct AltViStats
+    steps_done::Int32
+    nonfinite_step::Int32
+    last_elbo::Float64
+    last_lp_mean::Float64
+    AltViStats() = new(0, 0, 0.0, 0.0)
+end
+
+"State of one fit of approximate_likelihood(::LogisticNormalApprox | ::NormalILRApprox | ::NormalALRApprox, sample); t: the tree of normal_ilr"
+mutable struct AltLikelihoodApproximationFit
+    h::Ptr{Cvoid}
+    sample::AnySample
+    t::Union{Nothing,PolyaTreeTransform}
+    K::Int
+    function AltLikelihoodApproximationFit(s::AnySample, opts::AltViOpts, t::Union{Nothing,PolyaTreeTransform}=nothing)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:polee_altvi_create, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{AltViOpts}, Ref{Ptr{Cvoid}}),
+                    s.h, t === nothing ? C_NULL : t.h, opts, out), s.ctx.h)
+        f = new(out[], s, t, Int(opts.num_mc_samples))
+        finalizer(x -> ccall((:polee_altvi_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), f)
+        return f
+    end
+end
+run!(f::AltLikelihoodApproximationFit, nsteps::Integer) =
+    check(ccall((:polee_altvi_run, LIB), Cint, (Ptr{Cvoid}, Int32), f.h, nsteps), f.sample.ctx.h)
+sync!(f::AltLikelihoodApproximationFit) = check(ccall((:polee_altvi_sync, LIB), Cint, (Ptr{Cvoid},), f.h), f.sample.ctx.h)
+function params(f::AltLikelihoodApproximationFit)
+    mu, omega = (Vector{Float32}(undef, f.sample.n - 1) for _ in 1:2)
+    GC.@preserve mu omega check(ccall((:polee_altvi_get_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), f.h, mu, omega),
+                                f.sample.ctx.h)
+    return mu, omega
+end
+function set_params!(f::AltLikelihoodApproximationFit, mu::Vector{Float32}, omega::Vector{Float32})
+    GC.@preserve mu omega check(ccall((:polee_altvi_set_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), f.h, mu, omega),
+                                f.sample.ctx.h)
+end
+function stats(f::AltLikelihoodApproximationFit)
+    st = AltViStats()
+    check(ccall((:polee_altvi_get_stats, LIB), Cint, (Ptr{Cvoid}, Ref{AltViStats}), f.h, st), f.sample.ctx.h)
+    return st
+end
+"per-step elbo and mean log-likelihood (gradonly == 0 only)"
+function trace(f::AltLikelihoodApproximationFit)
+    k = Int(stats(f).steps_done)
+    elbo, lp = Vector{Float64}(undef, k), Vector{Float64}(undef, k)
+    GC.@preserve elbo lp check(ccall((:polee_altvi_get_trace, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), f.h, elbo, lp),
+                               f.sample.ctx.h)
+    return elbo, lp
+end
+"the N(0,1) draws of iteration `step`: Float32 [n-1, K]"
+function export_noise(f::AltLikelihoodApproximationFit, step::Integer)
+    z = Matrix{Float32}(undef, f.sample.n - 1, f.K)
+    GC.@preserve z check(ccall((:polee_altvi_export_noise, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), f.h, step, z), f.sample.ctx.h)
+    return z
+end
+"test hook: the next step's draws and averaged gradients at the current parameters, nothing updated"
+function eval_gradients(f::AltLikelihoodApproximationFit)
+    n, K = f.sample.n, f.K
+    xs = Matrix{Float32}(undef, n, K); xg = Matrix{Float64}(undef, n, K); yg = Matrix{Float64}(undef, n - 1, K)
+    mg, og = (Vector{Float32}(undef, n - 1) for _ in 1:2)
+    lp, ladj = Vector{Float64}(undef, K), Vector{Float64}(undef, K)
+    GC.@preserve xs xg yg mg og lp ladj check(
+        ccall((:polee_altvi_eval_gradients, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}, Ptr{Float64}),
+              f.h, xs, xg, yg, mg, og, lp, ladj), f.sample.ctx.h)
+    return xs, xg, yg, mg, og, lp, ladj
+end
+"sample_likap (src/evaluate.jl:34-74, 203-275): Float32 [n, count], every draw divided by the effective lengths and renormalised"
+function alt_sample(ctx::Context, method::Integer, t::Union{Nothing,PolyaTreeTransform}, mu::Vector{Float32}, omega::Vector{Float32},
+                    efflens::Vector{Float32}, refidx::Integer, count::Integer; seed::Integer=123456789,
+                    z0::Union{Nothing,Matrix{Float32}}=nothing)
+    n = length(efflens)
+    out = Matrix{Float32}(undef, n, count)
+    GC.@preserve mu omega efflens z0 out check(
+        ccall((:polee_alt_sample, LIB), Cint,
+              (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, UInt64, Ptr{Float32}, Ptr{Float32}),
+              ctx.h, method, t === nothing ? C_NULL : t.h, n, mu, omega, efflens, refidx, count, seed,
+              z0 === nothing ? C_NULL : pointer(z0), out), ctx.h)
+    return out
+end
+"a, b of the ILR balances for r, s leaves below the left and right child (isometric_log_ratios.jl:62-66): Float64 [2, count]"
+function ilr_coefficients(r::Vector{Int32}, s::Vector{Int32})
+    ab = Matrix{Float64}(undef, 2, length(r))
+    GC.@preserve r s ab check(ccall((:polee_ilr_coefficients, LIB), Cint, (Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Float64}), r, s, length(r), ab))
+    return ab
+end
+
 end # module

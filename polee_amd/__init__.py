@@ -9,6 +9,9 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   hsb / inv_hsb / inv_hsb_grad  (TF custom ops)                              src/tensorflow_ext/hsb_ops.cpp
   RNASeqSample.X + log_likelihood / factored_log_likelihood                  src/likelihood.jl
   approximate_likelihood(LogitSkewNormalPTTApprox(), sample)                 src/likelihood-approximation.jl
+  approximate_likelihood(LogisticNormalApprox() | NormalILRApprox() | NormalALRApprox(), sample)
+  (`prep --approx-method`)                                                   src/likelihood-approximation-alt.jl
+  sample_likap                                                               src/evaluate.jl:8-275
   ApproxLikelihoodSampler / rand!                                            src/approx-sampler.jl
   RNASeqApproxLikelihood(...).log_prob, rnaseq_approx_likelihood_sampler     src/polee_approx_likelihood.py
   RNASeqLinearRegression / RNASeqTranscriptLinearRegression(...).fit         models/polee_regression.py
@@ -35,7 +38,9 @@ from .core import (Context, Comm, HostComm, version, hclust, host_cache_trim, sa
                    rnaseq_approx_likelihood_sampler, LIKAP_NUM_STEPS, LIKAP_NUM_MC_SAMPLES,
                    logit_normal_transform, logit_normal_transform_gradients, sinh_asinh_transform,
                    sinh_asinh_transform_gradients, kumaraswamy_transform, kumaraswamy_transform_gradients,
-                   OptimizePTTApprox, optimize_likelihood, list_nodes)
+                   OptimizePTTApprox, optimize_likelihood, list_nodes,
+                   LogisticNormalApprox, KumaraswamyPTTApprox, LogitNormalPTTApprox, NormalILRApprox, NormalALRApprox,
+                   AltLikelihoodApproximationFit, sample_likap, approximation_type)
 
 from . import h5io, estimate  # noqa: F401,E402
 from .estimate import LoadedSamples, load_samples_from_specification, load_samples_hdf5, read_specification  # noqa: F401,E402

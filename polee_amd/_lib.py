@@ -51,6 +51,19 @@ class ViStats(C.Structure):
                 ("loglik_kernel_launches", C.c_int64), ("last_elbo", C.c_double), ("last_lp_mean", C.c_double), ("loglik_pass_ms_avg", C.c_double)]
 
 
+class AltViOpts(C.Structure):
+    """polee_altvi_opts (include/polee_hip.h)"""
+    _fields_ = [("method", C.c_int32), ("num_steps", C.c_int32), ("num_mc_samples", C.c_int32), ("gradonly", C.c_int32),
+                ("refidx", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("z0", f32p), ("eps", C.c_double),
+                ("adam_initial_learning_rate", C.c_double), ("adam_learning_rate_decay", C.c_double),
+                ("adam_min_learning_rate", C.c_double), ("adam_eps", C.c_double), ("adam_rv", C.c_double),
+                ("adam_rm", C.c_double), ("max_step0", C.c_double), ("max_step1", C.c_double)]
+
+
+class AltViStats(C.Structure):
+    _fields_ = [("steps_done", C.c_int32), ("nonfinite_step", C.c_int32), ("last_elbo", C.c_double), ("last_lp_mean", C.c_double)]
+
+
 class LoglikInfo(C.Structure):
     _fields_ = [("m", C.c_int64), ("n", C.c_int64), ("nnz", C.c_int64), ("num_slices", C.c_int64),
                 ("num_tiles", C.c_int64), ("padded_nnz", C.c_int64), ("device_bytes", C.c_int64),
@@ -88,10 +101,24 @@ def lib():
         L.polee_ptt_n.argtypes = [C.c_void_p]
         for name in ("polee_ctx_destroy", "polee_ptt_destroy", "polee_loglik_destroy", "polee_vi_destroy",
                      "polee_approx_destroy", "polee_debug_psell_free", "polee_comm_destroy", "polee_devx_destroy",
-                     "polee_gibbs_destroy", "polee_em_destroy"):
+                     "polee_gibbs_destroy", "polee_em_destroy", "polee_altvi_destroy"):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         L.polee_vi_default_opts.restype = None
+        L.polee_altvi_default_opts.restype = None
+        L.polee_altvi_default_opts.argtypes = [C.c_int32, C.POINTER(AltViOpts)]
+        L.polee_altvi_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AltViOpts), C.POINTER(C.c_void_p)]
+        L.polee_altvi_run.argtypes = [C.c_void_p, C.c_int32]
+        L.polee_altvi_sync.argtypes = [C.c_void_p]
+        L.polee_altvi_get_params.argtypes = [C.c_void_p, f32p, f32p]
+        L.polee_altvi_set_params.argtypes = [C.c_void_p, f32p, f32p]
+        L.polee_altvi_get_stats.argtypes = [C.c_void_p, C.POINTER(AltViStats)]
+        L.polee_altvi_get_trace.argtypes = [C.c_void_p, f64p, f64p]
+        L.polee_altvi_export_noise.argtypes = [C.c_void_p, C.c_int32, f32p]
+        L.polee_altvi_eval_gradients.argtypes = [C.c_void_p, f32p, f64p, f64p, f32p, f32p, f64p, f64p]
+        L.polee_alt_sample.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, f32p, f32p, f32p, C.c_int32, C.c_int32,
+                                       C.c_uint64, f32p, f32p]
+        L.polee_ilr_coefficients.argtypes = [i32p, i32p, C.c_int64, f64p]
         # polee fit-tree (polee_amd/fit_tree.py)
         L.polee_kmer_sketch.argtypes = [C.c_void_p, C.c_int64, i64p, u8p, u64p]
         L.polee_kmer_sketch_host.argtypes = [C.c_int64, i64p, u8p, u64p]

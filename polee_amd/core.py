@@ -507,6 +507,50 @@ class LogitSkewNormalPTTApprox:
         self.treemethod = treemethod
 
 
+class LogisticNormalApprox:
+    """Logistic-normal distribution (src/likelihood-approximation-alt.jl:6-9)."""
+    method, names, needs_tree = 1, ("mu", "omega"), False
+
+
+class KumaraswamyPTTApprox:
+    """Hierarchical stick breaking with Kumaraswamy distributed balances (likelihood-approximation-alt.jl:12-18).  Named so that
+    files of this type are recognised; the fit is not built."""
+    method, names, needs_tree = 2, ("alpha", "beta"), True
+
+    def __init__(self, treemethod="cluster"):
+        self.treemethod = treemethod
+
+
+class LogitNormalPTTApprox:
+    """Hierarchical stick breaking with logit-normal distributed balances (likelihood-approximation-alt.jl:21-27).  Named so that
+    files of this type are recognised; the fit is not built."""
+    method, names, needs_tree = 3, ("mu", "omega"), True
+
+    def __init__(self, treemethod="cluster"):
+        self.treemethod = treemethod
+
+
+class NormalILRApprox:
+    """Isometric log-ratio transformed normal distribution (likelihood-approximation-alt.jl:29-35)."""
+    method, names, needs_tree = 4, ("mu", "omega"), True
+
+    def __init__(self, treemethod="cluster"):
+        self.treemethod = treemethod
+
+
+class NormalALRApprox:
+    """Additive log-ratio transformed normal distribution (likelihood-approximation-alt.jl:37-47).  reference_idx: the divisor,
+    1-based; -1 = the last element.  (0, the reference's random index, is not offered.)"""
+    method, names, needs_tree = 5, ("mu", "omega"), False
+
+    def __init__(self, reference_idx=-1):
+        self.reference_idx = int(reference_idx)
+
+
+ALT_APPROX_TYPES = (LogisticNormalApprox, KumaraswamyPTTApprox, LogitNormalPTTApprox, NormalILRApprox, NormalALRApprox)
+_ALT_BUILT = (LogisticNormalApprox, NormalILRApprox, NormalALRApprox)
+
+
 class Comm:
     """RCCL communicator over the GPUs that share ONE sample by rows (polee_comm).
 
@@ -688,6 +732,93 @@ class LikelihoodApproximationFit:
         return out
 
 
+class AltLikelihoodApproximationFit:
+    """State of one fit of an alternative approximation (polee_altvi), with the shape of LikelihoodApproximationFit.  The two
+    parameter vectors are mu and omega."""
+
+    def __init__(self, sample, approx, t=None, num_steps=LIKAP_NUM_STEPS, num_mc_samples=LIKAP_NUM_MC_SAMPLES, gradonly=True,
+                 seed=123456789, z0=None, adam=None):
+        if not isinstance(approx, _ALT_BUILT):
+            raise NotImplementedError("%s is not built (built: LogisticNormalApprox, NormalILRApprox, NormalALRApprox)"
+                                      % type(approx).__name__)
+        if approx.needs_tree and t is None:
+            raise ValueError("%s needs a tree" % type(approx).__name__)
+        self.sample, self.approx, self.t, self.ctx = sample, approx, t if approx.needs_tree else None, sample.ctx
+        o = L.AltViOpts()
+        L.lib().polee_altvi_default_opts(C.c_int32(approx.method), C.byref(o))
+        o.num_steps, o.num_mc_samples, o.gradonly, o.seed = int(num_steps), int(num_mc_samples), int(gradonly), int(seed)
+        if isinstance(approx, NormalALRApprox):
+            if approx.reference_idx == 0:
+                raise NotImplementedError("reference_idx = 0 (a random reference element) is not offered")
+            o.refidx = approx.reference_idx
+        self.refidx = sample.n if o.refidx == -1 else int(o.refidx)
+        self._z0 = None
+        if z0 is not None:
+            self._z0 = arr(z0, np.float32).reshape(-1)
+            if self._z0.size != num_steps * num_mc_samples * (sample.n - 1):
+                raise ValueError("z0 must have num_steps*num_mc_samples*(n-1) elements")
+            o.z0 = ptr(self._z0, f32p)
+        for key, val in (adam or {}).items():
+            if not (key.startswith("adam_") or key.startswith("max_")) or not hasattr(o, key):
+                raise ValueError("unknown optimiser constant %r" % (key,))
+            setattr(o, key, float(val))
+        self.opts = o
+        self.n, self.K = sample.n, int(num_mc_samples)
+        self._h = C.c_void_p()
+        check(L.lib().polee_altvi_create(sample._h, self.t._h if self.t is not None else None, C.byref(o), C.byref(self._h)),
+              self.ctx._h)
+
+    def __del__(self):
+        try:
+            if self._h:
+                L.lib().polee_altvi_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def run(self, nsteps):
+        check(L.lib().polee_altvi_run(self._h, int(nsteps)), self.ctx._h)
+
+    def sync(self):
+        check(L.lib().polee_altvi_sync(self._h), self.ctx._h)
+
+    def params(self):
+        p0, p1 = (np.empty(self.n - 1, np.float32) for _ in range(2))
+        check(L.lib().polee_altvi_get_params(self._h, ptr(p0, f32p), ptr(p1, f32p)), self.ctx._h)
+        return p0, p1
+
+    def set_params(self, p0=None, p1=None):
+        a = [None if v is None else arr(v, np.float32) for v in (p0, p1)]
+        check(L.lib().polee_altvi_set_params(self._h, ptr(a[0], f32p), ptr(a[1], f32p)), self.ctx._h)
+
+    def stats(self):
+        s = L.AltViStats()
+        check(L.lib().polee_altvi_get_stats(self._h, C.byref(s)), self.ctx._h)
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def trace(self):
+        n = self.stats()["steps_done"]
+        e, l = np.zeros(n), np.zeros(n)
+        check(L.lib().polee_altvi_get_trace(self._h, ptr(e, f64p), ptr(l, f64p)), self.ctx._h)
+        return e, l
+
+    def export_noise(self, step):
+        z = np.empty((self.K, self.n - 1), np.float32)
+        check(L.lib().polee_altvi_export_noise(self._h, int(step), ptr(z, f32p)), self.ctx._h)
+        return z
+
+    def eval_gradients(self):
+        n, nm1, K = self.n, self.n - 1, self.K
+        out = dict(xs=np.empty((K, n), np.float32), x_grad=np.empty((K, n), np.float64), y_grad=np.empty((K, nm1), np.float64),
+                   mu_grad=np.empty(nm1, np.float32), omega_grad=np.empty(nm1, np.float32), lp=np.empty(K, np.float64),
+                   ladj=np.empty(K, np.float64))
+        check(L.lib().polee_altvi_eval_gradients(
+            self._h, ptr(out["xs"], f32p), ptr(out["x_grad"], f64p), ptr(out["y_grad"], f64p), ptr(out["mu_grad"], f32p),
+            ptr(out["omega_grad"], f32p), ptr(out["lp"], f64p), ptr(out["ladj"], f64p)), self.ctx._h)
+        return out
+
+
+
 import threading as _threading
 _host_tree_slot = _threading.Semaphore(1)  # treemethod "cluster_auto": one host-built tree at a time (it takes every host thread)
 _fits_lock = _threading.Lock()
@@ -766,37 +897,68 @@ def _sample_and_tree(approx, tm, m, n, colptr, rowval, nzval, effective_lengths,
     return sample, PolyaTreeTransform(parents, js, ctx=ctx)
 
 
+def _tree_for(approx, sample):
+    """PolyaTreeTransform(X, approx.treemethod) (ptt.jl:35-52, likelihood-approximation.jl:425-440)"""
+    if approx.treemethod == "cluster":
+        if getattr(sample, "_csc", None) is None:
+            raise ValueError("tree construction needs the sample's CSC arrays (create it from colptr/rowval/nzval) "
+                             "or pass a PolyaTreeTransform")
+        parents, js = hclust(sample.m, sample.n, *sample._csc)
+    elif approx.treemethod == "cluster_parallel":  # (the rounds variant of the same rule, polee_hclust_parallel)
+        if getattr(sample, "_csc", None) is None:
+            raise ValueError("tree construction needs the sample's CSC arrays")
+        parents, js = hclust(sample.m, sample.n, *sample._csc, parallel=True)
+    elif approx.treemethod in ("cluster_device", "cluster_auto"):  # (the same variant built on the GPU, polee_hclust_parallel_device)
+        if getattr(sample, "_csc", None) is None:
+            raise ValueError("tree construction needs the sample's CSC arrays")
+        parents, js = hclust(sample.m, sample.n, *sample._csc, device=True, ctx=sample.ctx)
+    elif approx.treemethod == "sequential":
+        parents, js = list_nodes(sample.n)
+    else:
+        raise ValueError("%r is not a supported Polya tree transform heuristic" % (approx.treemethod,))
+    return PolyaTreeTransform(parents, js, ctx=sample.ctx)
+
+
+def _approximate_likelihood_alt(approx, sample, t, num_steps, num_mc_samples, gradonly, seed, z0):
+    """approximate_likelihood of an alternative type (likelihood-approximation-alt.jl): the reference's Dicts -- mu, omega
+    (logistic_normal), plus the tree (normal_ilr), plus refidx (normal_alr)."""
+    if approx.needs_tree and t is None:
+        t = _tree_for(approx, sample)
+    fit = AltLikelihoodApproximationFit(sample, approx, t, num_steps=num_steps, num_mc_samples=num_mc_samples, gradonly=gradonly,
+                                        seed=seed, z0=z0)
+    fit.run(num_steps)
+    fit.sync()
+    p0, p1 = fit.params()
+    params = {approx.names[0]: p0, approx.names[1]: p1}
+    if approx.needs_tree:
+        if t.node_parent_idxs is None:
+            raise ValueError("the tree carries no node_parent_idxs / node_js to store with the fit")
+        params["node_parent_idxs"], params["node_js"] = t.node_parent_idxs, t.node_js
+    if isinstance(approx, NormalALRApprox):
+        params["refidx"] = np.array([fit.refidx], np.int32)
+    if not gradonly:
+        params["elbo"], params["lp_mean"] = fit.trace()
+    return params
+
+
 def approximate_likelihood(approx, sample, t=None, gene_noninformative=False, use_efflen_jacobian=True,
                            num_steps=LIKAP_NUM_STEPS, num_mc_samples=LIKAP_NUM_MC_SAMPLES, gradonly=True,
                            seed=123456789, z0=None, gene_transcripts=None):
     """approximate_likelihood(::LogitSkewNormalPTTApprox, sample) (likelihood-approximation.jl:395-624).
     Returns the params Dict: mu, omega, alpha (+ node_parent_idxs, node_js when the tree carries them).
+    An alternative type (LogisticNormalApprox, NormalILRApprox, NormalALRApprox; likelihood-approximation-alt.jl) goes to its
+    own loop and returns the reference's Dict of that type; the gene and effective-length options do not apply to them.
     gene_noninformative = True needs the genes of the transcripts (the reference takes them from the sample's
     transcript metadata, :475-487): `gene_transcripts` = Dict gene id -> 1-based transcript indexes, or an int array
     gene_of[n] (-1 = none known); with no gene information the option is switched off with the reference's warning."""
+    if isinstance(approx, ALT_APPROX_TYPES):
+        return _approximate_likelihood_alt(approx, sample, t, num_steps, num_mc_samples, gradonly, seed, z0)
     if not isinstance(approx, LogitSkewNormalPTTApprox):
-        raise NotImplementedError("only LogitSkewNormalPTTApprox is built (the alt approximations are out of scope)")
+        raise NotImplementedError("%r is not an approximation type" % (approx,))
     if gene_noninformative and gene_transcripts is None:
         gene_transcripts = np.full(sample.n, -1, np.int32)
-    if t is None:  # PolyaTreeTransform(X, approx.treemethod) (ptt.jl:35-52, likelihood-approximation.jl:425-440)
-        if approx.treemethod == "cluster":
-            if getattr(sample, "_csc", None) is None:
-                raise ValueError("tree construction needs the sample's CSC arrays (create it from colptr/rowval/nzval) "
-                                 "or pass a PolyaTreeTransform")
-            parents, js = hclust(sample.m, sample.n, *sample._csc)
-        elif approx.treemethod == "cluster_parallel":  # (the rounds variant of the same rule, polee_hclust_parallel)
-            if getattr(sample, "_csc", None) is None:
-                raise ValueError("tree construction needs the sample's CSC arrays")
-            parents, js = hclust(sample.m, sample.n, *sample._csc, parallel=True)
-        elif approx.treemethod in ("cluster_device", "cluster_auto"):  # (the same variant built on the GPU, polee_hclust_parallel_device)
-            if getattr(sample, "_csc", None) is None:
-                raise ValueError("tree construction needs the sample's CSC arrays")
-            parents, js = hclust(sample.m, sample.n, *sample._csc, device=True, ctx=sample.ctx)
-        elif approx.treemethod == "sequential":
-            parents, js = list_nodes(sample.n)
-        else:
-            raise ValueError("%r is not a supported Polya tree transform heuristic" % (approx.treemethod,))
-        t = PolyaTreeTransform(parents, js, ctx=sample.ctx)
+    if t is None:
+        t = _tree_for(approx, sample)
     fit = LikelihoodApproximationFit(sample, t, num_steps=num_steps, num_mc_samples=num_mc_samples,
                                      use_efflen_jacobian=use_efflen_jacobian, gradonly=gradonly, seed=seed, z0=z0,
                                      gene_transcripts=gene_transcripts if gene_noninformative else None)
@@ -816,6 +978,69 @@ def approximate_likelihood(approx, sample, t=None, gene_noninformative=False, us
     if not gradonly:
         params["elbo"], params["lp_mean"] = fit.trace()
     return params
+
+
+# the names a prepared-sample file may carry in metadata["approximation"] (evaluate.jl:12-25)
+_APPROX_TYPENAMES = {
+    "LogisticNormalApprox": LogisticNormalApprox, "LogitNormalHSBApprox": LogitNormalPTTApprox,
+    "LogitNormalPTTApprox": LogitNormalPTTApprox, "LogitSkewNormalHSBApprox": LogitSkewNormalPTTApprox,
+    "LogitSkewNormalPTTApprox": LogitSkewNormalPTTApprox, "KumaraswamyHSBApprox": KumaraswamyPTTApprox,
+    "KumaraswamyPTTApprox": KumaraswamyPTTApprox, "NormalILRApprox": NormalILRApprox, "NormalALRApprox": NormalALRApprox}
+
+
+def approximation_type(name):
+    """The type a prepared sample's metadata["approximation"] names: a leading `Polee.` / `Extruder.` stripped, the old
+    `...HSBApprox` names accepted (evaluate.jl:12-25)."""
+    import re
+    short = re.sub(r"^(Extruder|Polee)\.", "", str(name))
+    if short not in _APPROX_TYPENAMES:
+        raise ValueError("%r is not an approximation type" % (name,))
+    return _APPROX_TYPENAMES[short]
+
+
+class WrongApproximationError(ValueError):
+    """A prepared sample of an alternative approximation was given to a consumer built for the default one."""
+
+
+def require_default_approximation(prepared, filename):
+    """The consumers of prepared samples other than sample_likap are built for the default approximation only."""
+    typ = approximation_type(prepared["metadata"].get("approximation", "Polee.LogitSkewNormalPTTApprox"))
+    if typ is not LogitSkewNormalPTTApprox:
+        raise WrongApproximationError("%s holds a %s; only LogitSkewNormalPTTApprox can be used here (draw from it with polee_amd.sample_likap)"
+                         % (filename, typ.__name__))
+
+
+def sample_likap(filename, num_samples, seed=123456789, z0=None, ctx=None):
+    """sample_likap (src/evaluate.jl:8-275): num_samples draws from the approximation a prepared-sample file holds, each divided
+    by the effective lengths and renormalised; float32 [num_samples, n].  z0: the noise, [num_samples, n-1].  Built for
+    LogitSkewNormalPTTApprox (the existing sampler), LogisticNormalApprox, NormalILRApprox and NormalALRApprox."""
+    from . import h5io
+    ps = h5io.read_prepared_sample(filename, check_version=False)
+    typ = approximation_type(ps["metadata"].get("approximation", "Polee.LogitSkewNormalPTTApprox"))
+    ctx = ctx or default_context()
+    n, num_samples = int(ps["n"]), int(num_samples)
+    efflens = arr(ps["effective_lengths"], np.float32)
+    if z0 is not None:
+        z0 = arr(z0, np.float32).reshape(-1)
+        if z0.size != num_samples * (n - 1):
+            raise ValueError("z0 must have num_samples*(n-1) elements")
+    if typ is LogitSkewNormalPTTApprox:
+        # the existing sampler: `polee sample`'s stream (main.jl:850-853 is evaluate.jl:146-149).  It draws without evaluate.jl's
+        # clamps of ys and xs to [1e-10, 1 - 1e-10], which bind only where a value leaves that interval.
+        from .sample import ApproxSampleStream
+        t = PolyaTreeTransform(ps["node_parent_idxs"], ps["node_js"], ctx=ctx)
+        stream = ApproxSampleStream(t, ps["mu"], np.exp(ps["omega"]), ps["alpha"], efflens, ps["m"], seed)
+        return stream.next(num_samples, props=True, z0=z0)["props"]
+    if typ not in _ALT_BUILT:
+        raise NotImplementedError("%s holds a %s, which is not built" % (filename, typ.__name__))
+    t = PolyaTreeTransform(ps["node_parent_idxs"], ps["node_js"], ctx=ctx) if typ.needs_tree else None
+    refidx = int(ps["refidx"][0]) if typ is NormalALRApprox else -1
+    mu, omega = arr(ps["mu"], np.float32), arr(ps["omega"], np.float32)
+    out = np.empty((num_samples, n), np.float32)
+    check(L.lib().polee_alt_sample(ctx._h, typ.method, t._h if t is not None else None, n, ptr(mu, f32p), ptr(omega, f32p),
+                                   ptr(efflens, f32p), refidx, num_samples, C.c_uint64(int(seed)), ptr(z0, f32p), ptr(out, f32p)),
+          ctx._h)
+    return out
 
 
 class OptimizePTTApprox:

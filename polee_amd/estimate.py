@@ -8,7 +8,7 @@ import base64
 import numpy as np
 
 from . import h5io
-from .core import RNASeqApproxLikelihood, make_inverse_ptt_params
+from .core import RNASeqApproxLikelihood, make_inverse_ptt_params, require_default_approximation
 
 
 def read_specification(spec, point_estimates_key=None, max_num_samples=None, rng=None):
@@ -75,6 +75,7 @@ def load_samples_hdf5(filenames, n, gffhash=None, ptt_filename=None, check_gff_h
     trees = []  # (node_parent_idxs, node_js) of every sample (for the initial-value draws)
     for i, filename in enumerate(filenames):
         s = h5io.read_prepared_sample(filename)  # raises on a version mismatch (estimate.jl:388)
+        require_default_approximation(s, filename)
         if s["n"] != n:
             raise ValueError("Prepared sample %s has a different number of transcripts than provided GFF3 file." % filename)
         if check_gff_hash and gffhash is not None and base64.b64decode(s["metadata"].get("gffhash", "")) != bytes(gffhash):
@@ -148,6 +149,7 @@ def posterior_mean(loaded_samples, N=100, seed=123456789, ctx=None):
     als.seed(seed)
     for i, fn in enumerate(ls.sample_filenames):
         d = h5io.read_prepared_sample(fn)
+        require_default_approximation(d, fn)
         t = PolyaTreeTransform(d["node_parent_idxs"], d["node_js"], ctx=ctx)
         als.set_transform(t, ls.la_mu_values[i], ls.la_sigma_values[i], ls.la_alpha_values[i])
         pm[i] = als.posterior_mean(N)

@@ -310,18 +310,21 @@ def write_likelihood_matrix(filename, m, n, colptr, rowval, nzval, effective_len
 # ---- prepared sample (src/likelihood-approximation.jl:61-101) ---------------------------------------------
 def write_approximation(output_filename, m, n, efflens, params, approx_type="Polee.LogitSkewNormalPTTApprox",
                         gfffilename="", gffhash=b"", fafilename="", fahash=b"", args=""):
-    """write_approximation (likelihood-approximation.jl:61-87); params: mu, omega, alpha[, node_parent_idxs, node_js]."""
+    """write_approximation (likelihood-approximation.jl:61-87).  Like the reference's loop over the Dict (:70-72) it writes the
+    arrays `params` holds: mu, omega, alpha, beta as float32; node_parent_idxs, node_js, refidx as int32.  For the default
+    approximation (mu, omega, alpha and the tree) the file is what it always was."""
     def b64(h):
         return h if isinstance(h, str) else base64.b64encode(bytes(h)).decode()
     with File(output_filename, "w") as f:
         f.write("n", np.int64(n))
         f.write("m", np.int64(m))
         f.write("effective_lengths", np.ascontiguousarray(efflens, np.float32))
-        for key in ("mu", "omega", "alpha"):
-            f.write(key, np.ascontiguousarray(params[key], np.float32))
-        for key in ("node_parent_idxs", "node_js"):
+        for key in ("mu", "omega", "alpha", "beta"):
             if key in params and params[key] is not None:
-                f.write(key, np.ascontiguousarray(params[key], np.int32))
+                f.write(key, np.ascontiguousarray(params[key], np.float32))
+        for key in ("node_parent_idxs", "node_js", "refidx"):
+            if key in params and params[key] is not None:
+                f.write(key, np.ascontiguousarray(np.atleast_1d(params[key]), np.int32))
         f.create_group("metadata")
         f.write_attr("metadata", "version", PREPARED_SAMPLE_FORMAT_VERSION)
         f.write_attr("metadata", "approximation", approx_type)
@@ -350,10 +353,15 @@ def read_prepared_sample(filename, check_version=True):
         if check_version:
             check_prepared_sample_version(f, filename)
         out = dict(n=int(f.read("n", np.int64)[0]), m=int(f.read("m", np.int64)[0]),
-                   effective_lengths=f.read("effective_lengths", np.float32), mu=f.read("mu", np.float32),
-                   omega=f.read("omega", np.float32), alpha=f.read("alpha", np.float32))
+                   effective_lengths=f.read("effective_lengths", np.float32))
+        # (a file of an alternative approximation holds other arrays than mu / omega / alpha: what is there is read)
+        for key in ("mu", "omega", "alpha", "beta"):
+            if f.exists(key):
+                out[key] = f.read(key, np.float32)
         for key in ("node_parent_idxs", "node_js"):
             out[key] = f.read(key, np.int32) if f.exists(key) else None
+        if f.exists("refidx"):
+            out["refidx"] = f.read("refidx", np.int32)
         meta = {}
         for key in ("version", "approximation", "gfffilename", "gffhash", "fafilename", "fahash", "date", "args"):
             try:

@@ -10,6 +10,13 @@ the reference.
 
     python -m polee_amd.prep likelihood-matrix.h5 -o prepared-sample.h5 [--tree-method auto|cluster|cluster_parallel|cluster_device|cluster_auto|sequential]
         [--ptt-tree tree.h5] [--no-efflen-jacobian] [--seed N] [--device D]
+        [--approx-method logit_skew_normal_ptt|logistic_normal|normal_ilr|normal_alr|logit_normal_ptt|kumaraswamy_ptt]
+
+--approx-method (src/main.jl:5-23, 111): the reference's alternative approximations, the baselines the default is judged against
+(src/likelihood-approximation-alt.jl).  logistic_normal, normal_ilr and normal_alr are built; logit_normal_ptt and kumaraswamy_ptt
+are known names that exit with a message.  normal_ilr takes its tree from --tree-method, or from --ptt-tree: the reference ignores
+--ptt-tree for the alternative methods, honouring it is an addition.  None of them applies the effective-length Jacobian, so
+--no-efflen-jacobian changes nothing for them.  The files they write are drawn from with polee_amd.sample_likap.
 
 --tree-method (default auto): "cluster" is the reference's heuristic merge for merge (src/hclust.jl:193-319) -- a serial
 priority-queue loop, 3.7 s on one host thread at 200 000 transcripts.  "cluster_auto" / "cluster_parallel" / "cluster_device" build
@@ -29,8 +36,23 @@ import sys
 import time
 
 from . import h5io
-from .core import (Context, LogitSkewNormalPTTApprox, PolyaTreeTransform, RNASeqSample, approximate_likelihood,
-                   sample_and_tree)
+from .core import (ALT_APPROX_TYPES, Context, KumaraswamyPTTApprox, LogisticNormalApprox, LogitNormalPTTApprox,
+                   LogitSkewNormalPTTApprox, NormalALRApprox, NormalILRApprox, PolyaTreeTransform, RNASeqSample,
+                   approximate_likelihood, sample_and_tree)
+
+# --approx-method names (src/main.jl:5-23)
+APPROX_METHODS = {"logit_skew_normal_ptt": LogitSkewNormalPTTApprox, "logistic_normal": LogisticNormalApprox,
+                  "kumaraswamy_ptt": KumaraswamyPTTApprox, "logit_normal_ptt": LogitNormalPTTApprox,
+                  "normal_ilr": NormalILRApprox, "normal_alr": NormalALRApprox}
+APPROX_METHODS_BUILT = ("logit_skew_normal_ptt", "logistic_normal", "normal_ilr", "normal_alr")
+
+
+def select_approx_method(name, tree_method):
+    """select_approx_method (src/main.jl:5-23): the approximation object of an --approx-method name."""
+    if name not in APPROX_METHODS:
+        raise ValueError("%r is not a known approximation method" % (name,))
+    typ = APPROX_METHODS[name]
+    return typ(tree_method) if hasattr(typ(), "treemethod") else typ()
 
 
 # --tree-method auto: the reference-order tree up to this many transcripts, the rounds variant above (VERDICT r5 item 6: the
@@ -57,11 +79,15 @@ def approximate_likelihood_to_file(approx, likelihood_matrix_filename, output_fi
     lm = h5io.read_likelihood_matrix(likelihood_matrix_filename)
     t_read = time.time() - t0
     note = None
-    if approx.treemethod == "auto":
+    alt = isinstance(approx, ALT_APPROX_TYPES)
+    if getattr(approx, "treemethod", None) == "auto":
         tm, note = resolve_tree_method("auto", int(lm["n"]))
-        approx = LogitSkewNormalPTTApprox(tm)
+        approx = type(approx)(tm)
     t0 = time.time()
-    if tree_topology_input_filename is not None:  # likelihood-approximation.jl:428-433
+    if alt and not approx.needs_tree:
+        sample = RNASeqSample(lm["m"], lm["n"], lm["colptr"], lm["rowval"], lm["nzval"], lm["effective_lengths"], ctx=ctx)
+        tree = None
+    elif tree_topology_input_filename is not None:  # likelihood-approximation.jl:428-433
         sample = RNASeqSample(lm["m"], lm["n"], lm["colptr"], lm["rowval"], lm["nzval"], lm["effective_lengths"], ctx=ctx)
         parents, js = h5io.read_transformation(tree_topology_input_filename)
         tree = PolyaTreeTransform(parents, js, ctx=ctx)
@@ -72,9 +98,10 @@ def approximate_likelihood_to_file(approx, likelihood_matrix_filename, output_fi
     t0 = time.time()
     params = approximate_likelihood(approx, sample, tree, use_efflen_jacobian=use_efflen_jacobian, seed=seed)
     t_fit = time.time() - t0
-    h5io.write_approximation(output_filename, lm["m"], lm["n"], lm["effective_lengths"], params, args=args)
+    h5io.write_approximation(output_filename, lm["m"], lm["n"], lm["effective_lengths"], params,
+                             approx_type="Polee." + type(approx).__name__, args=args)
     params["timings"] = {"read_s": t_read, "device_layout_and_tree_s": t_layout, "fit_s": t_fit}
-    params["tree_method"] = "file" if tree_topology_input_filename is not None else approx.treemethod
+    params["tree_method"] = ("none" if tree is None else "file" if tree_topology_input_filename is not None else approx.treemethod)
     params["tree_note"] = note if tree_topology_input_filename is None else None
     return params
 
@@ -112,9 +139,23 @@ def main(argv=None):
                     help="auto (default): the reference's merge order up to %d transcripts, the rounds variant (cluster_auto) above" % AUTO_EXACT_MAX_N)
     ap.add_argument("--ptt-tree", default=None, metavar="tree.h5", help="use this tree topology (polee fit-tree output)")
     ap.add_argument("--no-efflen-jacobian", action="store_true")
+    ap.add_argument("--approx-method", default="logit_skew_normal_ptt", choices=sorted(APPROX_METHODS) + ["optimize"],
+                    help="the approximation to fit (default logit_skew_normal_ptt); the others are the reference's baselines")
     ap.add_argument("--seed", type=int, default=123456789)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.approx_method == "optimize":
+        sys.exit("--approx-method optimize is not built as a prep method (core.optimize_likelihood is the point optimisation)")
+    if a.approx_method not in APPROX_METHODS_BUILT:
+        sys.exit("--approx-method %s is not built (built: %s)" % (a.approx_method, ", ".join(APPROX_METHODS_BUILT)))
+    alt = a.approx_method != "logit_skew_normal_ptt"
+    if alt:
+        print("Using alternative approximation. Some features not supported.", file=sys.stderr)  # (main.jl: the reference's warning)
+        if a.salmon is not None:
+            sys.exit("--salmon (the factored likelihood) is not built for --approx-method %s" % a.approx_method)
+        if a.no_efflen_jacobian:
+            print("--no-efflen-jacobian has no effect: the alternative approximations never apply the effective-length Jacobian",
+                  file=sys.stderr)
     if a.salmon is not None:
         if a.ptt_tree is None:
             ap.error("--salmon needs --ptt-tree (and --transcript-ids, unless the tree file holds transcript_ids)")
@@ -136,7 +177,7 @@ def main(argv=None):
         return 0
     if a.likelihood_matrix is None:
         ap.error("give a likelihood matrix or --salmon")
-    params = approximate_likelihood_to_file(LogitSkewNormalPTTApprox(a.tree_method), a.likelihood_matrix, a.output,
+    params = approximate_likelihood_to_file(select_approx_method(a.approx_method, a.tree_method), a.likelihood_matrix, a.output,
                                             use_efflen_jacobian=not a.no_efflen_jacobian,
                                             tree_topology_input_filename=a.ptt_tree, seed=a.seed,
                                             ctx=Context(a.device), args=" ".join(argv or sys.argv[1:]))
@@ -145,6 +186,8 @@ def main(argv=None):
         print(params["tree_note"])
     print("wrote %s (n=%d): read %.2f s, device layout and tree (%s) %.2f s, fit %.2f s"
           % (a.output, len(params["mu"]) + 1, t["read_s"], params["tree_method"], t["device_layout_and_tree_s"], t["fit_s"]))
+    if alt:
+        print("%s holds a %s: draw from it with polee_amd.sample_likap" % (a.output, APPROX_METHODS[a.approx_method].__name__))
     return 0
 
 

@@ -213,6 +213,8 @@ def polee_sample(prepared_sample_filename, output_filename=None, kallisto=False,
     if num_samples < 1 or batch < 1:
         raise ValueError("num_samples and batch must be positive")
     ps = h5io.read_prepared_sample(prepared_sample_filename)  # (runs the version check)
+    from .core import require_default_approximation
+    require_default_approximation(ps, prepared_sample_filename)
     n, m = ps["n"], ps["m"]
     ids, lens = resolve_names(n, transcript_ids, transcript_lengths, transformation, trim_prefix)
     if transformation is not None:
@@ -272,9 +274,13 @@ def main(argv=None):
     a = ap.parse_args(argv)
     ids = _read_lines(a.transcript_ids) if a.transcript_ids else None
     lens = np.array([int(v) for v in _read_lines(a.transcript_lengths)], np.int64) if a.transcript_lengths else None
-    polee_sample(a.prepared_sample, a.output, kallisto=a.kallisto, num_samples=a.num_samples, sample_counts=a.sample_counts,
-                 transformation=a.transformation, trim_prefix=a.trim_prefix, seed=a.seed, transcript_ids=ids,
-                 transcript_lengths=lens, batch=a.batch, call=" ".join(argv))
+    from .core import WrongApproximationError
+    try:
+        polee_sample(a.prepared_sample, a.output, kallisto=a.kallisto, num_samples=a.num_samples, sample_counts=a.sample_counts,
+                     transformation=a.transformation, trim_prefix=a.trim_prefix, seed=a.seed, transcript_ids=ids,
+                     transcript_lengths=lens, batch=a.batch, call=" ".join(argv))
+    except WrongApproximationError as e:
+        sys.exit(str(e))
     return 0
 
 
