@@ -620,7 +620,8 @@ polee_status polee_regression_fit(polee_regression *reg, int32_t niter, uint64_t
  *   parallel_intersection_loop (src/rnaseq_sample.jl:58-121), fragmentlength (src/transcripts.jl:273-446),
  *   effective_length / condfragprob (src/fragmodel.jl:119-169), sortperm + compact_indexes! + sparse
  *   (src/rnaseq_sample.jl:126-157, 470-489).
- * BAM / GFF parsing, bias models and read assignment stay upstream.  Coordinates are 1-based inclusive.
+ * BAM / GFF parsing and read assignment stay upstream; the bias model is trained here from training fragments
+ * (polee_bias_train_*, below).  Coordinates are 1-based inclusive.
  *   transcripts  j = 0..n-1 (= t.metadata.id - 1): sequence id, strand (+1 / -1), exons ascending and disjoint
  *   fragments    i = 0..m-1 = alignment pairs: sequence id, strand, the LEFTMOST mate (m1) and, for paired-end reads,
  *                the other one (m2; m2_left == 0: single-end); per mate its CIGAR as (operation code, length) pairs
@@ -657,8 +658,8 @@ typedef struct {
     float strand_specificity;
     int32_t alt_frag_model;
 } polee_xb_fragmodel;
-/* A TRAINED bias model for the reference's default BiasedFragModel (src/fragmodel.jl:174-445; training, src/bias.jl:266-786,
- * stays upstream).  tseq: the transcripts' spliced sequences in transcript orientation (t.metadata.seq), one code per base:
+/* A TRAINED bias model for the reference's default BiasedFragModel (src/fragmodel.jl:174-445; training, src/bias.jl:266-786:
+ * polee_bias_train_* below -- what still comes from upstream are the training fragments themselves).  tseq: the transcripts' spliced sequences in transcript orientation (t.metadata.seq), one code per base:
  * 0 A, 1 C, 2 G, 3 T, 4 anything else; tseq_ptr [n+1] (tseq_ptr[0] = 0, lengths = exonic lengths).  Sequence bias
  * (SeqBiasModel{:left} / {:right}, bias.jl:157-160, 419-456): seqbias_len = 20 positions, orders [20] (-1: position not in
  * the model), ps [20][4][ps_ctx] row-major (the reference's ps[i, c+1, ctx+1]), ps_ctx >= 4^(largest order).  gc_bins: the
@@ -1122,6 +1123,62 @@ polee_status polee_forest_build_host(const float *x, const int32_t *labels, int3
 polee_status polee_forest_votes_host(int32_t n, int32_t k, int32_t ntrees, const int64_t *tree_off, const int32_t *feature,
                                      const double *threshold, const int32_t *left, const int32_t *right, const int32_t *label,
                                      const float *x, int32_t R, int32_t *votes);
+
+/* ---- training of the fragment bias model (src/bias.jl; csrc/bias_train.hip, csrc/bias_train_host.cpp, csrc/bias_train_common.hpp;
+ * DESIGN.md section 3.16): from training fragments to the tables polee_xb_biasmodel takes.  The two sequence models by the greedy BIC
+ * search over variable-order Markov chains (SeqBiasModel, bias.jl:266-399), the GC histogram (SimpleHistogramModel, bias.jl:464-514) and
+ * the accuracy figure (bias.jl:788-828).  Not here: PositionalBiasModel (use_pos_bias = false in every caller of the reference), and the
+ * steps BEFORE the training fragments -- subsampling reads, the SimplisticFragModel's estimation, the EM assignment of each read to one
+ * transcript and its projection to (tpos, fraglen) (rnaseq_sample.jl:330-377, fragmodel.jl:205-246) -- which stay upstream.
+ * The model is this project's own exact definition where the reference is not reproducible: positions beyond a transcript's ends are
+ * Philox nucleotides (randdna in the reference, bias.jl:83-101), a drawn background position is a Philox draw (rand, fragmodel.jl:243),
+ * and the log of the loss is taken and summed in f64 in a fixed order (Float32 log and pairwise sum in bias.jl:254-257).  The device
+ * trainer, the host trainer (host = 1; POLEE_HOST_THREADS) and the NumPy restatement of the tests give the same model bit for bit; the
+ * loss trace agrees to the ulp error of log.
+ * 30 <= n_fg + n_bg (POLEE_ERR_BAD_ARG below: the reference leaves quantiles uninitialised) < 2^24 (POLEE_ERR_UNSUPPORTED from there:
+ * counts are exact f32 integers below). */
+typedef struct polee_bias_train polee_bias_train;
+typedef struct {
+    uint64_t seed;    /* keys the pads and the drawn background */
+    int32_t host;     /* 1: the host trainer; ctx may then be NULL */
+    int32_t reserved; /* 0 */
+} polee_bias_train_opts;
+/* Examples from fragments (BiasTrainingExample, bias.jl:21-80; extract_padded_seq, :88-102).  tseq_ptr [n+1] / tseq as in
+ * polee_xb_biasmodel.  Fragments are (transcript 0-based, tpos 1-based in transcript orientation, fraglen); required of each:
+ * fraglen >= 20, tpos >= 1, tpos + fraglen - 1 <= tlen (fragmodel.jl:227-234), else POLEE_ERR_BAD_ARG.  bg_transcript NULL: one
+ * background fragment per foreground fragment is drawn, same transcript and length, tpos uniform in 1 .. tlen - fraglen + 1
+ * (fragmodel.jl:243); n_bg, bg_tpos and bg_fraglen are then ignored.  opts NULL: seed 0, on the device. */
+polee_status polee_bias_train_create(polee_ctx *ctx, int32_t n, const int64_t *tseq_ptr, const uint8_t *tseq, int64_t n_fg,
+                                     const int32_t *fg_transcript, const int64_t *fg_tpos, const int32_t *fg_fraglen, int64_t n_bg,
+                                     const int32_t *bg_transcript, const int64_t *bg_tpos, const int32_t *bg_fraglen,
+                                     const polee_bias_train_opts *opts, polee_bias_train **out);
+/* Ready-made examples (the reference's --dump-bias-training-examples files, fragmodel.jl:306-339): left_seq / right_seq u8 [N][20]
+ * codes (0 A, 1 C, 2 G, 3 T, other -> A: nt2bit, bias.jl:176-181), frag_gc f64 [N] in 0 .. 1; N = n_fg + n_bg, foreground first. */
+polee_status polee_bias_train_create_from_examples(polee_ctx *ctx, int64_t n_fg, int64_t n_bg, const uint8_t *left_seq,
+                                                   const uint8_t *right_seq, const double *frag_gc, const polee_bias_train_opts *opts,
+                                                   polee_bias_train **out);
+void polee_bias_train_destroy(polee_bias_train *bt);
+/* BiasModel(...) (bias.jl:677-785): both sequence models, the GC model, the accuracy */
+polee_status polee_bias_train_run(polee_bias_train *bt);
+/* The trained model in polee_xb_biasmodel's layout (each pointer may be NULL): orders i32 [20]; ps f32 [20][4][4096] = ps_fg / ps_bg
+ * (bias.jl:398), 1.0 where the model never reads (order -1, contexts >= 4^order; NaN in the reference); gc_bins f32 [100] (bias.jl:505-511)
+ * and the 14 quantile boundaries behind them, gc_qs (bias.jl:476-489); accuracy (bias.jl:788-828) as a fraction. */
+polee_status polee_bias_train_get_model(polee_bias_train *bt, int32_t *orders_left, int32_t *orders_right, float *ps_left, float *ps_right,
+                                        float *gc_bins, float *gc_qs, double *accuracy);
+/* The examples as the trainer holds them (each pointer may be NULL): left / right u64 [N], 20 two-bit codes each, position 1 in bits
+ * 39:38 (bias.jl:283-293); frag_gc f64 [N] (bias.jl:63); bg_tpos i64 [n_bg], the background positions given or drawn
+ * (fragmodel.jl:243; POLEE_ERR_BAD_ARG for a trainer made from examples). */
+polee_status polee_bias_train_get_examples(polee_bias_train *bt, int64_t *n_fg, int64_t *n_bg, uint64_t *left, uint64_t *right,
+                                           double *frag_gc, int64_t *bg_tpos);
+/* The search of one side (0 left, 1 right; bias.jl:353-396): *rounds committed rounds (<= 140), positions i32 [rounds] (0-based, the
+ * position whose order each round raised), losses f64 [rounds + 1] (loss0 at the start, bias.jl:352, and after every round, :393). */
+polee_status polee_bias_train_get_trace(polee_bias_train *bt, int32_t side, int32_t *rounds, int32_t *positions, double *losses);
+/* Debug entry: scores ONE round (bias.jl:357-383) from a caller-given state.  orders_in i32 [20] (-1 .. 6, position j (1-based) + order
+ * <= 20); the tables and factor columns of that state are rebuilt, n_params = sum of 4^(1 + order) over the included positions;
+ * losses_out f64 [20] (+inf where no candidate is allowed, bias.jl:358), *loss0_out the loss of the state itself (bias.jl:243-263).
+ * Leaves a trained model untouched. */
+polee_status polee_bias_train_candidates(polee_bias_train *bt, int32_t side, const int32_t *orders_in, double *losses_out,
+                                         double *loss0_out);
 
 #ifdef __cplusplus
 }

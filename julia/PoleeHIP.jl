@@ -1805,4 +1805,99 @@ function ilr_coefficients(r::Vector{Int32}, s::Vector{Int32})
     return ab
 end
 
+# ---- training of the fragment bias model (src/bias.jl; csrc/bias_train.hip, csrc/bias_train_host.cpp): BiasModel(...) from fragments -------
+"mirror of `polee_bias_train_opts` (include/polee_hip.h): field order and types must stay in step with the header"
+struct BiasTrainOpts
+    seed::UInt64
+    host::Int32
+    reserved::Int32
+end
+"a trainer with its examples made; ctx === nothing runs the host trainer (POLEE_HOST_THREADS)"
+mutable struct BiasTrainer
+    h::Ptr{Cvoid}
+    ctx::Union{Nothing,Context}
+end
+_bt_ctx(ctx::Union{Nothing,Context}) = ctx === nothing ? C_NULL : ctx.h
+function _bt_finish(r::Ref{Ptr{Cvoid}}, ctx)
+    bt = BiasTrainer(r[], ctx)
+    finalizer(x -> ccall((:polee_bias_train_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.h), bt)
+    return bt
+end
+"""
+examples from fragments (BiasTrainingExample, bias.jl:21-80): tseq_ptr [n+1] 0-based offsets, tseq codes 0 A 1 C 2 G 3 T 4 other;
+fragments (transcript 0-based, tpos 1-based, fraglen); background === nothing draws one background fragment per foreground fragment
+"""
+function BiasTrainer(ctx::Union{Nothing,Context}, tseq_ptr::Vector{Int64}, tseq::Vector{UInt8}, transcript::Vector{Int32},
+                     tpos::Vector{Int64}, fraglen::Vector{Int32};
+                     background::Union{Nothing,Tuple{Vector{Int32},Vector{Int64},Vector{Int32}}}=nothing, seed::Integer=0)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    opts = Ref(BiasTrainOpts(seed, ctx === nothing ? 1 : 0, 0))
+    bt_, bp_, bf_ = background === nothing ? (Int32[], Int64[], Int32[]) : background
+    GC.@preserve tseq_ptr tseq transcript tpos fraglen bt_ bp_ bf_ check(
+        ccall((:polee_bias_train_create, LIB), Cint,
+              (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{UInt8}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int32},
+               Ref{BiasTrainOpts}, Ref{Ptr{Cvoid}}),
+              _bt_ctx(ctx), length(tseq_ptr) - 1, tseq_ptr, tseq, length(transcript), transcript, tpos, fraglen, length(bt_),
+              background === nothing ? C_NULL : pointer(bt_), background === nothing ? C_NULL : pointer(bp_),
+              background === nothing ? C_NULL : pointer(bf_), opts, r), _bt_ctx(ctx))
+    return _bt_finish(r, ctx)
+end
+"ready-made examples (--dump-bias-training-examples): left / right UInt8 [20, N] codes (column = example), frag_gc [N], the first n_fg foreground"
+function BiasTrainer(ctx::Union{Nothing,Context}, left::Matrix{UInt8}, right::Matrix{UInt8}, frag_gc::Vector{Float64}, n_fg::Integer;
+                     seed::Integer=0)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    opts = Ref(BiasTrainOpts(seed, ctx === nothing ? 1 : 0, 0))
+    GC.@preserve left right frag_gc check(
+        ccall((:polee_bias_train_create_from_examples, LIB), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ref{BiasTrainOpts}, Ref{Ptr{Cvoid}}),
+              _bt_ctx(ctx), n_fg, length(frag_gc) - n_fg, left, right, frag_gc, opts, r), _bt_ctx(ctx))
+    return _bt_finish(r, ctx)
+end
+"BiasModel(...) (bias.jl:677-785)"
+function train!(bt::BiasTrainer)
+    check(ccall((:polee_bias_train_run, LIB), Cint, (Ptr{Cvoid},), bt.h), _bt_ctx(bt.ctx))
+    return bt
+end
+"orders [20] x 2, ps Float32 [4096, 4, 20] x 2 (column-major view of the C [20][4][4096]), gc_bins [100], gc_qs [14], accuracy (a fraction)"
+function bias_model(bt::BiasTrainer)
+    ol, or_ = Vector{Int32}(undef, 20), Vector{Int32}(undef, 20)
+    pl, pr = Array{Float32}(undef, 4096, 4, 20), Array{Float32}(undef, 4096, 4, 20)
+    bins, qs, acc = Vector{Float32}(undef, 100), Vector{Float32}(undef, 14), Ref{Float64}(0)
+    GC.@preserve ol or_ pl pr bins qs check(
+        ccall((:polee_bias_train_get_model, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ref{Float64}),
+              bt.h, ol, or_, pl, pr, bins, qs, acc), _bt_ctx(bt.ctx))
+    return (orders_left=ol, orders_right=or_, ps_left=pl, ps_right=pr, gc_bins=bins, gc_qs=qs, accuracy=acc[])
+end
+"the packed examples: left / right UInt64 [N] (20 two-bit codes, position 1 highest), frag_gc [N], bg_tpos [n_bg] (positions: from fragments only)"
+function bias_examples(bt::BiasTrainer; positions::Bool=true)
+    nf, nb = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:polee_bias_train_get_examples, LIB), Cint,
+                (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Float64}, Ptr{Int64}),
+                bt.h, nf, nb, C_NULL, C_NULL, C_NULL, C_NULL), _bt_ctx(bt.ctx))
+    N = nf[] + nb[]
+    l, r, g, bp = Vector{UInt64}(undef, N), Vector{UInt64}(undef, N), Vector{Float64}(undef, N), Vector{Int64}(undef, positions ? nb[] : 0)
+    GC.@preserve l r g bp check(
+        ccall((:polee_bias_train_get_examples, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Float64}, Ptr{Int64}),
+              bt.h, C_NULL, C_NULL, l, r, g, positions ? pointer(bp) : C_NULL), _bt_ctx(bt.ctx))
+    return (n_fg=nf[], n_bg=nb[], left=l, right=r, frag_gc=g, bg_tpos=bp)
+end
+"the search of one side (0 left, 1 right): positions (0-based) of the committed rounds, losses [rounds + 1]"
+function bias_trace(bt::BiasTrainer, side::Integer)
+    rounds, pos, loss = Ref{Int32}(0), Vector{Int32}(undef, 140), Vector{Float64}(undef, 141)
+    GC.@preserve pos loss check(
+        ccall((:polee_bias_train_get_trace, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Int32}, Ptr{Float64}), bt.h, side, rounds, pos, loss),
+        _bt_ctx(bt.ctx))
+    return pos[1:rounds[]], loss[1:rounds[]+1]
+end
+"debug: the 20 candidate losses of ONE round from the state `orders` (-1 .. 6) and the loss of that state"
+function bias_candidates(bt::BiasTrainer, side::Integer, orders::Vector{Int32})
+    losses, loss0 = Vector{Float64}(undef, 20), Ref{Float64}(0)
+    GC.@preserve orders losses check(
+        ccall((:polee_bias_train_candidates, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ref{Float64}), bt.h, side, orders, losses, loss0),
+        _bt_ctx(bt.ctx))
+    return losses, loss0[]
+end
+
 end # module

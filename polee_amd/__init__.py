@@ -27,6 +27,8 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   polee_sample / ApproxSampleStream / multinomial_counts (`polee sample`)    src/main.jl:756-919
   read_fasta / kmer_sketches / build_polya_tree_transformation               src/kmersketch.jl, src/kmercluster.jl
   (`polee fit-tree`: python -m polee_amd.fit_tree)                           src/main.jl:638-660
+  train_bias_model / fragment_length_model (BiasModel, BiasedFragModel)      src/bias.jl:266-828, src/fragmodel.jl:263-343
+  (python -m polee_amd.bias)
 
 All numerics run in libpolee_hip.so on the GPU; nothing here computes on the CPU.
 """
@@ -75,6 +77,10 @@ def __getattr__(name):
     if name in ("read_fasta", "kmer_sketches", "kmer_tree", "kmer_candidate_edges", "kmer_round_select", "build_polya_tree_transformation"):
         from . import fit_tree
         return getattr(fit_tree, name)
+    if name in ("train_bias_model", "train_bias_model_from_examples", "fragment_length_model", "read_reference_dump",
+                "bias_training_examples", "bias_candidate_losses"):
+        from . import bias
+        return getattr(bias, name)
     if name in ("IsoformEffects", "estimate_isoform_effect_sizes", "build_design_matrix", "gene_map", "gene_initial_values",
                 "write_isoform_regression_effects", "write_aitchison_results", "write_expression", "load_kallisto_estimates"):
         from . import regression

@@ -64,6 +64,11 @@ class AltViStats(C.Structure):
     _fields_ = [("steps_done", C.c_int32), ("nonfinite_step", C.c_int32), ("last_elbo", C.c_double), ("last_lp_mean", C.c_double)]
 
 
+class BiasTrainOpts(C.Structure):
+    """polee_bias_train_opts (include/polee_hip.h)"""
+    _fields_ = [("seed", C.c_uint64), ("host", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LoglikInfo(C.Structure):
     _fields_ = [("m", C.c_int64), ("n", C.c_int64), ("nnz", C.c_int64), ("num_slices", C.c_int64),
                 ("num_tiles", C.c_int64), ("padded_nnz", C.c_int64), ("device_bytes", C.c_int64),
@@ -101,7 +106,7 @@ def lib():
         L.polee_ptt_n.argtypes = [C.c_void_p]
         for name in ("polee_ctx_destroy", "polee_ptt_destroy", "polee_loglik_destroy", "polee_vi_destroy",
                      "polee_approx_destroy", "polee_debug_psell_free", "polee_comm_destroy", "polee_devx_destroy",
-                     "polee_gibbs_destroy", "polee_em_destroy", "polee_altvi_destroy"):
+                     "polee_gibbs_destroy", "polee_em_destroy", "polee_altvi_destroy", "polee_bias_train_destroy"):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         L.polee_vi_default_opts.restype = None
@@ -131,6 +136,16 @@ def lib():
         L.polee_kmer_tree_rounds.argtypes = [C.c_void_p, C.c_int64, u64p, i32p, i32p, i64p]
         L.polee_fit_tree_rounds.argtypes = [C.c_void_p, C.c_int64, i64p, u8p, i32p, i32p, i64p]
         L.polee_debug_kmer_round_select.argtypes = [C.c_void_p, C.c_int64, C.c_int64, u32p, u32p, u64p, u8p, i32p]
+        # training of the bias model (polee_amd/bias.py)
+        L.polee_bias_train_create.argtypes = [C.c_void_p, C.c_int32, i64p, u8p, C.c_int64, i32p, i64p, i32p, C.c_int64, i32p, i64p, i32p,
+                                              C.POINTER(BiasTrainOpts), C.POINTER(C.c_void_p)]
+        L.polee_bias_train_create_from_examples.argtypes = [C.c_void_p, C.c_int64, C.c_int64, u8p, u8p, f64p, C.POINTER(BiasTrainOpts),
+                                                            C.POINTER(C.c_void_p)]
+        L.polee_bias_train_run.argtypes = [C.c_void_p]
+        L.polee_bias_train_get_model.argtypes = [C.c_void_p, i32p, i32p, f32p, f32p, f32p, f32p, f64p]
+        L.polee_bias_train_get_examples.argtypes = [C.c_void_p, i64p, i64p, u64p, u64p, f64p, i64p]
+        L.polee_bias_train_get_trace.argtypes = [C.c_void_p, C.c_int32, i32p, i32p, f64p]
+        L.polee_bias_train_candidates.argtypes = [C.c_void_p, C.c_int32, i32p, f64p, f64p]
         _lib = L
     return _lib
 
