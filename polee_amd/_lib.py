@@ -106,7 +106,9 @@ def lib():
         L.polee_ptt_n.argtypes = [C.c_void_p]
         for name in ("polee_ctx_destroy", "polee_ptt_destroy", "polee_loglik_destroy", "polee_vi_destroy",
                      "polee_approx_destroy", "polee_debug_psell_free", "polee_comm_destroy", "polee_devx_destroy",
-                     "polee_gibbs_destroy", "polee_em_destroy", "polee_altvi_destroy", "polee_bias_train_destroy"):
+                     "polee_gibbs_destroy", "polee_em_destroy", "polee_altvi_destroy", "polee_bias_train_destroy",
+                     "polee_regression_destroy", "polee_effects_destroy", "polee_sampler_destroy", "polee_classify_destroy",
+                     "polee_tsne_destroy", "polee_forest_destroy"):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         L.polee_vi_default_opts.restype = None
@@ -157,6 +159,25 @@ def check(status, ctx=None):
     if status == 4:
         raise NonFiniteError(status, msg)
     raise PoleeError(status, msg)
+
+
+class Handle:
+    """Owner of a library handle self._h, released by the entry point named _destroy (declared in lib()).
+    close() releases it now and may be called again; a class that holds more than its handle overrides close()
+    and ends with super().close()."""
+    _destroy = None
+    _h = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def ptr(a, typ):

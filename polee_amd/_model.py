@@ -3,8 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib as L
-from ._lib import arr
+from ._lib import Handle, arr  # (Handle: re-exported for the draw-fed models)
 
 DRAW_STRIDE = 0x9E3779B97F4A7C15  # POLEE_DRAW_STRIDE (csrc/common.hpp)
 MASK = (1 << 64) - 1
@@ -43,18 +42,3 @@ def make_opts(cls, default_fn, kw):
             raise TypeError("unknown option %r" % name)
         setattr(o, name, v)
     return o
-
-
-class Handle:
-    """Owner of a library handle self._h, released by the entry point named _destroy."""
-    _destroy = None
-
-    def __del__(self):
-        try:
-            if self._h:
-                f = getattr(L.lib(), self._destroy)
-                f.restype, f.argtypes = None, [C.c_void_p]
-                f(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass

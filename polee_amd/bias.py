@@ -23,22 +23,15 @@ SEQBIAS_LEN, PS_CTX, GC_EXPANDED, MAX_ROUNDS = 20, 4096, 100, 140
 MAX_FRAG_LEN, MIN_FRAG_LEN_COUNT, FALLBACK_FRAGLEN_MEAN, FALLBACK_FRAGLEN_SD, BIAS_EFFLEN_NUM_FRAGLENS = 2000, 1000, 150, 50, 200
 
 
-class BiasTrainer:
+class BiasTrainer(L.Handle):
     """A polee_bias_train handle: examples made (create), not yet trained."""
+    _destroy = "polee_bias_train_destroy"
 
     def __init__(self, h, ctx, host):
         self._h, self.ctx, self.host = h, ctx, host
 
     def _c(self):
         return None if self.host else self.ctx._h
-
-    def close(self):
-        if self._h:
-            L.lib().polee_bias_train_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
     def __enter__(self):
         return self

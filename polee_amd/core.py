@@ -77,9 +77,10 @@ def make_inverse_ptt_params(node_parent_idxs, node_js):
     return l, r, f
 
 
-class PolyaTreeTransform:
+class PolyaTreeTransform(L.Handle):
     """src/ptt.jl:6-27.  Built from the serialised tree (ptt.jl:89-116) or from the TF-op
     index arrays (left, right, leaf)."""
+    _destroy = "polee_ptt_destroy"
 
     def __init__(self, node_parent_idxs=None, node_js=None, ctx=None, index=None):
         self.ctx = ctx or default_context()
@@ -97,14 +98,6 @@ class PolyaTreeTransform:
             check(L.lib().polee_ptt_create(self.ctx._h, ptr(self.node_parent_idxs, i32p), ptr(self.node_js, i32p),
                                            int(self.node_js.size), C.byref(self._h)), self.ctx._h)
         self.n = int(L.lib().polee_ptt_n(self._h))
-
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_ptt_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def _rows(self, a, dtype, width):
         a = arr(a, dtype)
@@ -188,10 +181,11 @@ def inv_hsb_grad(y_grad, ladj_grad, y, left_index, right_index=None, leaf_index=
     return bp
 
 
-class DeviceX:
+class DeviceX(L.Handle):
     """X by columns (1-based CSC, the likelihood-matrix HDF5 arrays) in device memory, uploaded once for the two device builders
     that read it (polee_devx_upload): `RNASeqSample(..., devx=dx)` and `hclust(..., devx=dx)`.  Read-only: both may run at once,
     each on its own context of the same device."""
+    _destroy = "polee_devx_destroy"
 
     def __init__(self, m, n, colptr, rowval, nzval, ctx=None):
         self.ctx = ctx or default_context()
@@ -211,19 +205,12 @@ class DeviceX:
         nzval = arr(nzval, np.float32)
         check(L.lib().polee_devx_upload_values(self._h, ptr(nzval, f32p)), self.ctx._h)
 
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_devx_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
-
-class RNASeqSample:
+class RNASeqSample(L.Handle):
     """The numeric part of RNASeqSample (src/rnaseq_sample.jl:6-23): X (m x n CSC, 1-based
     colptr/rowval exactly as in the likelihood-matrix HDF5, :505-519) + effective_lengths,
     resident on the GPU.  `ks` = row multiplicities for the factored likelihood."""
+    _destroy = "polee_loglik_destroy"
 
     def __init__(self, m, n, colptr, rowval, nzval, effective_lengths=None, ks=None, ctx=None, xt=None, _xbuild=None, devx=None):
         self.ctx = ctx or default_context()
@@ -254,14 +241,6 @@ class RNASeqSample:
                                               ptr(rowval, u32p), ptr(nzval, f32p), ptr(ks_a, i64p),
                                               C.byref(self._h)), self.ctx._h)
         self.has_ks = ks is not None
-
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_loglik_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     @property
     def built_on_device(self):
@@ -551,11 +530,12 @@ ALT_APPROX_TYPES = (LogisticNormalApprox, KumaraswamyPTTApprox, LogitNormalPTTAp
 _ALT_BUILT = (LogisticNormalApprox, NormalILRApprox, NormalALRApprox)
 
 
-class Comm:
+class Comm(L.Handle):
     """RCCL communicator over the GPUs that share ONE sample by rows (polee_comm).
 
     `broadcast` distributes rank 0's 128-byte id: a callable bytes -> bytes (e.g. built on
     torch.distributed.broadcast_object_list or MPI); it may be None for a single rank."""
+    _destroy = "polee_comm_destroy"
 
     def __init__(self, ctx, world_size=1, rank=0, broadcast=None):
         self.ctx, self.world_size, self.rank = ctx, int(world_size), int(rank)
@@ -570,14 +550,6 @@ class Comm:
         uid = (C.c_uint8 * 128).from_buffer_copy(raw)
         self._h = C.c_void_p()
         check(L.lib().polee_comm_create(ctx._h, self.world_size, self.rank, uid, C.byref(self._h)), ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_comm_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def info(self):
         """What the transport reports (polee_comm_info): dict(transport "rccl" | "host", count, rank) -- for RCCL the
@@ -628,8 +600,9 @@ class HostComm(Comm):
         check(L.lib().polee_comm_create_host(ctx._h, self.world_size, self.rank, self._cb, None, C.byref(self._h)), ctx._h)
 
 
-class LikelihoodApproximationFit:
+class LikelihoodApproximationFit(L.Handle):
     """State of one fit (polee_vi): lets callers step the VI loop and inspect it."""
+    _destroy = "polee_vi_destroy"
 
     def __init__(self, sample, t, efflens=None, num_steps=LIKAP_NUM_STEPS, num_mc_samples=LIKAP_NUM_MC_SAMPLES,
                  use_efflen_jacobian=True, gradonly=True, seed=123456789, z0=None, profile=False, comm=None,
@@ -679,14 +652,6 @@ class LikelihoodApproximationFit:
         if comm is not None:  # `sample` holds this rank's block of fragments (cohort.shard_rows)
             check(L.lib().polee_vi_set_comm(self._h, comm._h), self.ctx._h)
 
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_vi_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
     def run(self, nsteps):
         check(L.lib().polee_vi_run(self._h, int(nsteps)), self.ctx._h)
 
@@ -732,9 +697,10 @@ class LikelihoodApproximationFit:
         return out
 
 
-class AltLikelihoodApproximationFit:
+class AltLikelihoodApproximationFit(L.Handle):
     """State of one fit of an alternative approximation (polee_altvi), with the shape of LikelihoodApproximationFit.  The two
     parameter vectors are mu and omega."""
+    _destroy = "polee_altvi_destroy"
 
     def __init__(self, sample, approx, t=None, num_steps=LIKAP_NUM_STEPS, num_mc_samples=LIKAP_NUM_MC_SAMPLES, gradonly=True,
                  seed=123456789, z0=None, adam=None):
@@ -767,14 +733,6 @@ class AltLikelihoodApproximationFit:
         self._h = C.c_void_p()
         check(L.lib().polee_altvi_create(sample._h, self.t._h if self.t is not None else None, C.byref(o), C.byref(self._h)),
               self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_altvi_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def run(self, nsteps):
         check(L.lib().polee_altvi_run(self._h, int(nsteps)), self.ctx._h)
@@ -1150,11 +1108,12 @@ class ApproxLikelihoodSampler:
         return out
 
 
-class RNASeqApproxLikelihood:
+class RNASeqApproxLikelihood(L.Handle):
     """RNASeqApproxLikelihoodDist (polee_approx_likelihood.py:326-450) for S samples.
     `vars` uses the keys of create_tensorflow_variables! (estimate.jl:502-556):
     efflen [S,n], la_mu/la_sigma/la_alpha [S,n-1], left_index/right_index/leaf_index [S,N]
     (or [1,N] / [N] for a shared tree)."""
+    _destroy = "polee_approx_destroy"
 
     def __init__(self, vars=None, ctx=None, **kw):
         v = dict(vars or {})
@@ -1171,14 +1130,6 @@ class RNASeqApproxLikelihood:
         check(L.lib().polee_approx_create(self.ctx._h, self.S, self.n, ptr(eff, f32p), ptr(mu, f32p), ptr(sg, f32p),
                                           ptr(al, f32p), ptr(li, i32p), ptr(ri, i32p), ptr(fi, i32p), shared,
                                           C.byref(self._h)), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_approx_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def log_prob(self, x, want_grad=False):
         """_log_prob (polee_approx_likelihood.py:367-450): x [S,n] -> lp [S] (and d lp/d x)."""

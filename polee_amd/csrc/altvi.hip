@@ -17,6 +17,7 @@
 // The softmax subtracts the maximum: it equals the reference's exp / sum / divide wherever the reference's Float32 exp
 // neither overflows nor underflows.  No float atomics and no host synchronisation inside polee_altvi_run; the number of
 // launches does not depend on the tree.
+#include "adam.hpp"
 #include "loglik_internal.hpp"
 #include "ptt_internal.hpp"
 #include "rng.hpp"
@@ -249,12 +250,8 @@ struct AltPrefixEmit {
 };
 
 // ---- update ----------------------------------------------------------------------------------------------------------------
-struct AltAdam {
-    double lr, rm, rv, eps, inv_m_denom, inv_v_denom, max0, max1;
-    int first;
-};
 // adam_update_mv! and adam_update_params! (likelihood-approximation.jl:116-146)
-__device__ inline void alt_adam_one(float &p, float &m, float &v, float grad, const AltAdam &a, double max_step)
+__device__ inline void alt_adam_one(float &p, float &m, float &v, float grad, const AdamConsts &a, double max_step)
 {
     if (a.first) {
         m = grad;
@@ -277,7 +274,7 @@ struct AltUpd {
     const double *st, *P, *ab;
     const int32_t *lo, *mid, *hi1;
     float *mu, *omega, *m0, *v0, *m1, *v1;
-    AltAdam adam;
+    AdamConsts adam;  // (max_mu, max_omega: the caps of the two parameter vectors)
     int *flag;
     double *ygrad;        // hook: [K][n-1] or null
     float *mug, *omg;     // hook: [n-1] or null
@@ -321,12 +318,12 @@ __global__ __launch_bounds__(ALT_THREADS) void alt_update_kernel(AltUpd u)
         atomicCAS(u.flag, 0, u.step);
     } else if (u.apply) {
         float p = u.mu[j], m = u.m0[j], v = u.v0[j];
-        alt_adam_one(p, m, v, mug, u.adam, u.adam.max0);
+        alt_adam_one(p, m, v, mug, u.adam, u.adam.max_mu);
         u.mu[j] = p;
         u.m0[j] = m;
         u.v0[j] = v;
         p = u.omega[j], m = u.m1[j], v = u.v1[j];
-        alt_adam_one(p, m, v, omg, u.adam, u.adam.max1);
+        alt_adam_one(p, m, v, omg, u.adam, u.adam.max_omega);
         u.omega[j] = p;
         u.m1[j] = m;
         u.v1[j] = v;
@@ -530,17 +527,9 @@ polee_status polee_altvi::one_step(bool apply, bool want_values, bool hook)
         const AltLeafGradLoad ld{e, core.d_ms.p, d_st.p, core.d_x.p, d_g.p, (int)K};
         POLEE_HIP_TRY(ctx, run_scan<double>(st, K, (int64_t)n, core.d_chunk.p, ld, AltPrefixEmit{(int64_t)n, d_P.p}));
     }
-    AltAdam a;
-    // adam_learning_rate(step_num - 1) (likelihood-approximation.jl:107-110)
-    a.lr = std::max(o.adam_min_learning_rate, o.adam_initial_learning_rate * std::exp(-o.adam_learning_rate_decay * (double)(step_num - 1)));
-    a.rm = o.adam_rm;
-    a.rv = o.adam_rv;
-    a.eps = o.adam_eps;
-    a.inv_m_denom = 1.0 / (1 - std::pow(o.adam_rm, (double)step_num));
-    a.inv_v_denom = 1.0 / (1 - std::pow(o.adam_rv, (double)step_num));
-    a.max0 = o.max_step0;
-    a.max1 = o.max_step1;
-    a.first = step_num == 1;
+    AdamConsts a = adam_schedule(o, step_num);
+    a.max_mu = o.max_step0;
+    a.max_omega = o.max_step1;
     const bool noise_next = apply && !o.z0;
     AltUpd u;
     u.method = core.method;
@@ -584,10 +573,7 @@ extern "C" {
 
 polee_status polee_altvi_create(polee_loglik *ll, polee_ptt *t, const polee_altvi_opts *opts, polee_altvi **out)
 {
-    if (!ll) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_create: null likelihood handle");
-    polee_ctx *ctx = ll->ctx;
-    return guarded(ctx, "polee_altvi_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ll, "polee_altvi_create", [&](polee_ctx *ctx) -> polee_status {
         if (!out || !opts) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_altvi_create: null argument");
         if (opts->num_steps < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "num_steps must be >= 0");
         if (!(opts->eps > 0.0 && opts->eps < 0.5)) return fail(ctx, POLEE_ERR_BAD_ARG, "eps must lie in (0, 0.5)");
@@ -647,124 +633,117 @@ void polee_altvi_destroy(polee_altvi *A)
 
 polee_status polee_altvi_run(polee_altvi *A, int32_t nsteps)
 {
-    if (!A) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_run: null handle");
-    POLEE_TRY(use_device(A->ctx));
-    for (int32_t i = 0; i < nsteps; ++i) POLEE_TRY(A->one_step(true, !A->o.gradonly, false));
-    return POLEE_OK;
+    return entry(A, "polee_altvi_run", [&](polee_ctx *ctx) -> polee_status {
+        for (int32_t i = 0; i < nsteps; ++i) POLEE_TRY(A->one_step(true, !A->o.gradonly, false));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_altvi_sync(polee_altvi *A)
 {
-    if (!A) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_sync: null handle");
-    polee_ctx *ctx = A->ctx;
-    POLEE_TRY(use_device(ctx));
-    int flag = 0;
-    POLEE_TRY(A->d_flag.download(ctx, &flag, 1));
-    if (flag != 0) return fail(ctx, POLEE_ERR_NONFINITE, "non-finite gradient at step %d of the alternative approximation", flag);
-    return POLEE_OK;
+    return entry(A, "polee_altvi_sync", [&](polee_ctx *ctx) -> polee_status {
+        int flag = 0;
+        POLEE_TRY(A->d_flag.download(ctx, &flag, 1));
+        if (flag != 0) return fail(ctx, POLEE_ERR_NONFINITE, "non-finite gradient at step %d of the alternative approximation", flag);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_altvi_get_params(polee_altvi *A, float *p0, float *p1)
 {
-    if (!A) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_get_params: null handle");
-    polee_ctx *ctx = A->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (p0) POLEE_TRY(A->core.d_mu.download(ctx, p0, (size_t)A->n - 1));
-    if (p1) POLEE_TRY(A->core.d_omega.download(ctx, p1, (size_t)A->n - 1));
-    return POLEE_OK;
+    return entry(A, "polee_altvi_get_params", [&](polee_ctx *ctx) -> polee_status {
+        if (p0) POLEE_TRY(A->core.d_mu.download(ctx, p0, (size_t)A->n - 1));
+        if (p1) POLEE_TRY(A->core.d_omega.download(ctx, p1, (size_t)A->n - 1));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_altvi_set_params(polee_altvi *A, const float *p0, const float *p1)
 {
-    if (!A) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_set_params: null handle");
-    polee_ctx *ctx = A->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (p0) POLEE_TRY(A->core.d_mu.upload(ctx, p0, (size_t)A->n - 1));
-    if (p1) POLEE_TRY(A->core.d_omega.upload(ctx, p1, (size_t)A->n - 1));
-    return POLEE_OK;
+    return entry(A, "polee_altvi_set_params", [&](polee_ctx *ctx) -> polee_status {
+        if (p0) POLEE_TRY(A->core.d_mu.upload(ctx, p0, (size_t)A->n - 1));
+        if (p1) POLEE_TRY(A->core.d_omega.upload(ctx, p1, (size_t)A->n - 1));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_altvi_get_stats(polee_altvi *A, polee_altvi_stats *stats)
 {
-    if (!A || !stats) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_get_stats: null argument");
-    polee_ctx *ctx = A->ctx;
-    POLEE_TRY(use_device(ctx));
-    memset(stats, 0, sizeof(*stats));
-    stats->steps_done = A->step;
-    POLEE_TRY(A->d_flag.download(ctx, &stats->nonfinite_step, 1));
-    if (!A->o.gradonly && A->step > 0 && A->step <= A->trace_cap) {
-        POLEE_HIP_TRY(ctx, hipMemcpy(&stats->last_elbo, A->d_elbo.p + (A->step - 1), sizeof(double), hipMemcpyDeviceToHost));
-        POLEE_HIP_TRY(ctx, hipMemcpy(&stats->last_lp_mean, A->d_lptrace.p + (A->step - 1), sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return POLEE_OK;
+    return entry(A, "polee_altvi_get_stats", [&](polee_ctx *ctx) -> polee_status {
+        if (!stats) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_altvi_get_stats: null argument");
+        memset(stats, 0, sizeof(*stats));
+        stats->steps_done = A->step;
+        POLEE_TRY(A->d_flag.download(ctx, &stats->nonfinite_step, 1));
+        if (!A->o.gradonly && A->step > 0 && A->step <= A->trace_cap) {
+            POLEE_HIP_TRY(ctx, hipMemcpy(&stats->last_elbo, A->d_elbo.p + (A->step - 1), sizeof(double), hipMemcpyDeviceToHost));
+            POLEE_HIP_TRY(ctx, hipMemcpy(&stats->last_lp_mean, A->d_lptrace.p + (A->step - 1), sizeof(double), hipMemcpyDeviceToHost));
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_altvi_get_trace(polee_altvi *A, double *elbo, double *lp_mean)
 {
-    if (!A) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_get_trace: null handle");
-    polee_ctx *ctx = A->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (A->o.gradonly) return fail(ctx, POLEE_ERR_BAD_ARG, "no trace is recorded in gradonly mode");
-    const size_t cnt = (size_t)std::min(A->step, A->trace_cap);
-    if (elbo) POLEE_TRY(A->d_elbo.download(ctx, elbo, cnt));
-    if (lp_mean) POLEE_TRY(A->d_lptrace.download(ctx, lp_mean, cnt));
-    return POLEE_OK;
+    return entry(A, "polee_altvi_get_trace", [&](polee_ctx *ctx) -> polee_status {
+        if (A->o.gradonly) return fail(ctx, POLEE_ERR_BAD_ARG, "no trace is recorded in gradonly mode");
+        const size_t cnt = (size_t)std::min(A->step, A->trace_cap);
+        if (elbo) POLEE_TRY(A->d_elbo.download(ctx, elbo, cnt));
+        if (lp_mean) POLEE_TRY(A->d_lptrace.download(ctx, lp_mean, cnt));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_altvi_export_noise(polee_altvi *A, int32_t step, float *z0)
 {
-    if (!A || !z0 || step < 1) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_export_noise: bad argument");
-    polee_ctx *ctx = A->ctx;
-    POLEE_TRY(use_device(ctx));
-    const int64_t nm1 = (int64_t)A->n - 1;
-    const size_t cnt = (size_t)A->K * nm1;
-    if (A->o.z0) {
-        if (step > A->o.num_steps) return fail(ctx, POLEE_ERR_BAD_ARG, "step beyond the supplied noise");
-        POLEE_HIP_TRY(ctx, hipMemcpyAsync(z0, A->d_z0.p + (size_t)(step - 1) * cnt, cnt * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return POLEE_OK;
-    }
-    DevBuf<float> tmp;
-    POLEE_TRY(tmp.alloc(ctx, cnt));
-    hipLaunchKernelGGL(alt_noise_kernel, dim3((unsigned)ceil_div(nm1, 256), A->K), dim3(256), 0, ctx->stream, A->o.seed, (int)step, nm1, tmp.p);
-    POLEE_KERNEL_CHECK(ctx);
-    return tmp.download(ctx, z0, cnt);
+    return entry(A, "polee_altvi_export_noise", [&](polee_ctx *ctx) -> polee_status {
+        if (!z0 || step < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_altvi_export_noise: bad argument");
+        const int64_t nm1 = (int64_t)A->n - 1;
+        const size_t cnt = (size_t)A->K * nm1;
+        if (A->o.z0) {
+            if (step > A->o.num_steps) return fail(ctx, POLEE_ERR_BAD_ARG, "step beyond the supplied noise");
+            POLEE_HIP_TRY(ctx, hipMemcpyAsync(z0, A->d_z0.p + (size_t)(step - 1) * cnt, cnt * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            return POLEE_OK;
+        }
+        DevBuf<float> tmp;
+        POLEE_TRY(tmp.alloc(ctx, cnt));
+        hipLaunchKernelGGL(alt_noise_kernel, dim3((unsigned)ceil_div(nm1, 256), A->K), dim3(256), 0, ctx->stream, A->o.seed, (int)step, nm1, tmp.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return tmp.download(ctx, z0, cnt);
+    });
 }
 
 polee_status polee_altvi_eval_gradients(polee_altvi *A, float *xs, double *x_grad, double *y_grad, float *p0_grad, float *p1_grad, double *lp,
                                         double *ladj)
 {
-    if (!A) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_altvi_eval_gradients: null handle");
-    polee_ctx *ctx = A->ctx;
-    POLEE_TRY(use_device(ctx));
-    const size_t n = (size_t)A->n, nm1 = n - 1, K = (size_t)A->K;
-    POLEE_TRY(A->one_step(false, true, true));
-    const unsigned nb = (unsigned)ceil_div((int64_t)(n * K), 256);
-    hipLaunchKernelGGL(alt_rows_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)A->core.d_x.p, (int)K, (int64_t)n, A->d_x_rows.p,
-                       (double *)nullptr);
-    hipLaunchKernelGGL(alt_rows_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)A->d_g.p, (int)K, (int64_t)n, (float *)nullptr,
-                       A->d_xgrad_rows.p);
-    POLEE_KERNEL_CHECK(ctx);
-    if (xs) POLEE_TRY(A->d_x_rows.download(ctx, xs, n * K));
-    if (x_grad) POLEE_TRY(A->d_xgrad_rows.download(ctx, x_grad, n * K));
-    if (y_grad) POLEE_TRY(A->d_ygrad.download(ctx, y_grad, nm1 * K));
-    if (p0_grad) POLEE_TRY(A->d_mug.download(ctx, p0_grad, nm1));
-    if (p1_grad) POLEE_TRY(A->d_omg.download(ctx, p1_grad, nm1));
-    if (lp) POLEE_TRY(A->d_lp.download(ctx, lp, K));
-    if (ladj) {
-        std::vector<double> st(K * 4);
-        POLEE_TRY(A->d_st.download(ctx, st.data(), K * 4));
-        for (size_t d = 0; d < K; ++d) ladj[d] = st[d * 4 + 2];
-    }
-    return POLEE_OK;
+    return entry(A, "polee_altvi_eval_gradients", [&](polee_ctx *ctx) -> polee_status {
+        const size_t n = (size_t)A->n, nm1 = n - 1, K = (size_t)A->K;
+        POLEE_TRY(A->one_step(false, true, true));
+        const unsigned nb = (unsigned)ceil_div((int64_t)(n * K), 256);
+        hipLaunchKernelGGL(alt_rows_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)A->core.d_x.p, (int)K, (int64_t)n, A->d_x_rows.p,
+                           (double *)nullptr);
+        hipLaunchKernelGGL(alt_rows_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)A->d_g.p, (int)K, (int64_t)n, (float *)nullptr,
+                           A->d_xgrad_rows.p);
+        POLEE_KERNEL_CHECK(ctx);
+        if (xs) POLEE_TRY(A->d_x_rows.download(ctx, xs, n * K));
+        if (x_grad) POLEE_TRY(A->d_xgrad_rows.download(ctx, x_grad, n * K));
+        if (y_grad) POLEE_TRY(A->d_ygrad.download(ctx, y_grad, nm1 * K));
+        if (p0_grad) POLEE_TRY(A->d_mug.download(ctx, p0_grad, nm1));
+        if (p1_grad) POLEE_TRY(A->d_omg.download(ctx, p1_grad, nm1));
+        if (lp) POLEE_TRY(A->d_lp.download(ctx, lp, K));
+        if (ladj) {
+            std::vector<double> st(K * 4);
+            POLEE_TRY(A->d_st.download(ctx, st.data(), K * 4));
+            for (size_t d = 0; d < K; ++d) ladj[d] = st[d * 4 + 2];
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_alt_sample(polee_ctx *ctx, int32_t method, polee_ptt *t, int32_t n, const float *p0, const float *p1, const float *efflens,
                               int32_t refidx, int32_t count, uint64_t seed, const float *z0, float *out)
 {
-    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_alt_sample: null context");
-    return guarded(ctx, "polee_alt_sample", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_alt_sample", [&]() -> polee_status {
         if (!p0 || !p1 || !efflens || !out || count < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_alt_sample: bad argument");
         const int32_t B = std::min<int32_t>(count, PSELL_MAX_K);
         AltCore core;

@@ -5,6 +5,8 @@
 
 #include <cmath>
 
+using polee::host_entry;
+
 extern "C" {
 
 void polee_altvi_default_opts(int32_t method, polee_altvi_opts *o)
@@ -35,16 +37,18 @@ void polee_altvi_default_opts(int32_t method, polee_altvi_opts *o)
 // (isometric_log_ratios.jl:62-66); ab [count][2]
 polee_status polee_ilr_coefficients(const int32_t *r, const int32_t *s, int64_t count, double *ab)
 {
-    if (count < 0 || (count > 0 && (!r || !s || !ab))) return polee::fail(nullptr, POLEE_ERR_BAD_ARG, "polee_ilr_coefficients: bad argument");
-    for (int64_t k = 0; k < count; ++k) {
-        if (r[k] < 1 || s[k] < 1)
-            return polee::fail(nullptr, POLEE_ERR_BAD_ARG, "polee_ilr_coefficients: node %lld has %d and %d leaves below its children", (long long)k,
-                               r[k], s[k]);
-        const double rr = (double)r[k], ss = (double)s[k];
-        ab[2 * k + 0] = std::sqrt(ss / (rr * (rr + ss)));
-        ab[2 * k + 1] = -std::sqrt(rr / (ss * (rr + ss)));
-    }
-    return POLEE_OK;
+    return host_entry("polee_ilr_coefficients", [&]() -> polee_status {
+        if (count < 0 || (count > 0 && (!r || !s || !ab))) return polee::fail(nullptr, POLEE_ERR_BAD_ARG, "polee_ilr_coefficients: bad argument");
+        for (int64_t k = 0; k < count; ++k) {
+            if (r[k] < 1 || s[k] < 1)
+                return polee::fail(nullptr, POLEE_ERR_BAD_ARG, "polee_ilr_coefficients: node %lld has %d and %d leaves below its children", (long long)k,
+                                   r[k], s[k]);
+            const double rr = (double)r[k], ss = (double)s[k];
+            ab[2 * k + 0] = std::sqrt(ss / (rr * (rr + ss)));
+            ab[2 * k + 1] = -std::sqrt(rr / (ss * (rr + ss)));
+        }
+        return POLEE_OK;
+    });
 }
 
 }  // extern "C"

@@ -480,95 +480,96 @@ polee_status polee_approx_create(polee_ctx *ctx, int32_t S, int32_t n, const flo
                                  const int32_t *right_index, const int32_t *leaf_index, int shared_tree,
                                  polee_approx **out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!out || !efflens || !la_mu || !la_sigma || !la_alpha || !left_index || !right_index || !leaf_index || S < 1 ||
-        n < 2)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_create: bad argument");
-    polee_approx *ap = new (std::nothrow) polee_approx();
-    if (!ap) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
-    ap->ctx = ctx;
-    ctx_retain(ctx);
-    ap->S = S;
-    ap->n = n;
-    const size_t sn = (size_t)S * n, sk = (size_t)S * (n - 1);
-    std::vector<double> sll(S, 0.0);
-    for (int32_t s = 0; s < S; ++s)
-        for (int32_t j = 0; j < n; ++j) sll[s] += (double)logf(efflens[(size_t)s * n + j]);
-    polee_status st = ptt_create_multi(ctx, left_index, right_index, leaf_index, shared_tree ? 1 : S, 2 * n - 1, &ap->t);
-    auto A = [&](polee_status r) {
-        if (st == POLEE_OK) st = r;
-    };
-    A(ap->d_efflens.upload(ctx, efflens, sn));
-    A(ap->d_mu.upload(ctx, la_mu, sk));
-    A(ap->d_sigma.upload(ctx, la_sigma, sk));
-    A(ap->d_alpha.upload(ctx, la_alpha, sk));
-    A(ap->d_sum_log_l.upload(ctx, sll));
-    A(ap->d_acc.alloc(ctx, (size_t)S * 8));
-    A(ap->d_npart.alloc(ctx, (size_t)S * (size_t)ceil_div(n - 1, 256)));
-    A(ap->d_dots.alloc(ctx, (size_t)S * 2));
-    A(ap->d_tpair.alloc(ctx, 2 * sk));
-    A(ap->d_bp.alloc(ctx, sn));
-    A(ap->d_x.alloc(ctx, sn));
-    A(ap->d_xgrad.alloc(ctx, sn));
-    A(ap->d_lp.alloc(ctx, S));
-    if (st == POLEE_OK) st = ap->t->reserve(S);
-    if (st == POLEE_OK && !getenv("POLEE_APPROX_NO_CHUNKS")) {  // (A/B: the three-phase leaf scan + approx_nodes_kernel)
-        // tables of approx_leaf_nodes_kernel, per tree: internal nodes in DFS pre-order have non-decreasing lo
-        const int nch = (int)ceil_div(n, APX_CH), need_words = (n + 1 + 31) / 32 + 1;
-        std::vector<int32_t> node_start, cross, cross_ptr(1, 0);
-        std::vector<uint32_t> need;
-        bool ok = true;
-        int max_cross = 0;
-        for (const PttPlan &pl : ap->t->plans) {
-            const size_t ns0 = node_start.size(), nd0 = need.size();
-            node_start.resize(ns0 + (size_t)nch + 1, (int32_t)(n - 1));
-            need.resize(nd0 + (size_t)need_words, 0u);
-            int c = 0;
-            for (int k = 0; k + 1 < n; ++k) {
-                if (k > 0 && pl.lo[(size_t)k] < pl.lo[(size_t)k - 1]) ok = false;
-                for (; c <= pl.lo[(size_t)k] / APX_CH; ++c) node_start[ns0 + (size_t)c] = k;
-                const int64_t end = std::min<int64_t>(((int64_t)pl.lo[(size_t)k] / APX_CH + 1) * APX_CH, (int64_t)n);
-                if (pl.hi1[(size_t)k] > end) {
-                    cross.push_back(k);
-                    for (int32_t b : {pl.lo[(size_t)k], pl.mid[(size_t)k], pl.hi1[(size_t)k]}) need[nd0 + ((size_t)b >> 5)] |= 1u << (b & 31);
+    return ctx_entry(ctx, "polee_approx_create", [&]() -> polee_status {
+        if (!out || !efflens || !la_mu || !la_sigma || !la_alpha || !left_index || !right_index || !leaf_index || S < 1 ||
+            n < 2)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_create: bad argument");
+        polee_approx *ap = new (std::nothrow) polee_approx();
+        if (!ap) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
+        ap->ctx = ctx;
+        ctx_retain(ctx);
+        ap->S = S;
+        ap->n = n;
+        const size_t sn = (size_t)S * n, sk = (size_t)S * (n - 1);
+        std::vector<double> sll(S, 0.0);
+        for (int32_t s = 0; s < S; ++s)
+            for (int32_t j = 0; j < n; ++j) sll[s] += (double)logf(efflens[(size_t)s * n + j]);
+        polee_status st = ptt_create_multi(ctx, left_index, right_index, leaf_index, shared_tree ? 1 : S, 2 * n - 1, &ap->t);
+        auto A = [&](polee_status r) {
+            if (st == POLEE_OK) st = r;
+        };
+        A(ap->d_efflens.upload(ctx, efflens, sn));
+        A(ap->d_mu.upload(ctx, la_mu, sk));
+        A(ap->d_sigma.upload(ctx, la_sigma, sk));
+        A(ap->d_alpha.upload(ctx, la_alpha, sk));
+        A(ap->d_sum_log_l.upload(ctx, sll));
+        A(ap->d_acc.alloc(ctx, (size_t)S * 8));
+        A(ap->d_npart.alloc(ctx, (size_t)S * (size_t)ceil_div(n - 1, 256)));
+        A(ap->d_dots.alloc(ctx, (size_t)S * 2));
+        A(ap->d_tpair.alloc(ctx, 2 * sk));
+        A(ap->d_bp.alloc(ctx, sn));
+        A(ap->d_x.alloc(ctx, sn));
+        A(ap->d_xgrad.alloc(ctx, sn));
+        A(ap->d_lp.alloc(ctx, S));
+        if (st == POLEE_OK) st = ap->t->reserve(S);
+        if (st == POLEE_OK && !getenv("POLEE_APPROX_NO_CHUNKS")) {  // (A/B: the three-phase leaf scan + approx_nodes_kernel)
+            // tables of approx_leaf_nodes_kernel, per tree: internal nodes in DFS pre-order have non-decreasing lo
+            const int nch = (int)ceil_div(n, APX_CH), need_words = (n + 1 + 31) / 32 + 1;
+            std::vector<int32_t> node_start, cross, cross_ptr(1, 0);
+            std::vector<uint32_t> need;
+            bool ok = true;
+            int max_cross = 0;
+            for (const PttPlan &pl : ap->t->plans) {
+                const size_t ns0 = node_start.size(), nd0 = need.size();
+                node_start.resize(ns0 + (size_t)nch + 1, (int32_t)(n - 1));
+                need.resize(nd0 + (size_t)need_words, 0u);
+                int c = 0;
+                for (int k = 0; k + 1 < n; ++k) {
+                    if (k > 0 && pl.lo[(size_t)k] < pl.lo[(size_t)k - 1]) ok = false;
+                    for (; c <= pl.lo[(size_t)k] / APX_CH; ++c) node_start[ns0 + (size_t)c] = k;
+                    const int64_t end = std::min<int64_t>(((int64_t)pl.lo[(size_t)k] / APX_CH + 1) * APX_CH, (int64_t)n);
+                    if (pl.hi1[(size_t)k] > end) {
+                        cross.push_back(k);
+                        for (int32_t b : {pl.lo[(size_t)k], pl.mid[(size_t)k], pl.hi1[(size_t)k]}) need[nd0 + ((size_t)b >> 5)] |= 1u << (b & 31);
+                    }
                 }
+                max_cross = std::max(max_cross, (int)cross.size() - cross_ptr.back());
+                cross_ptr.push_back((int32_t)cross.size());
             }
-            max_cross = std::max(max_cross, (int)cross.size() - cross_ptr.back());
-            cross_ptr.push_back((int32_t)cross.size());
+            if (ok) {
+                if (cross.empty()) cross.push_back(0);
+                ap->nch = nch;
+                ap->need_words = need_words;
+                ap->max_cross_blocks = (int)ceil_div(max_cross, 256);
+                A(ap->d_node_start.upload(ctx, node_start));
+                A(ap->d_need.upload(ctx, need));
+                A(ap->d_cross.upload(ctx, cross));
+                A(ap->d_cross_ptr.upload(ctx, cross_ptr));
+                A(ap->d_chunk_tot.alloc(ctx, (size_t)S * ((size_t)nch + 1)));
+                A(ap->d_npart.alloc(ctx, (size_t)S * (size_t)std::max<int64_t>(ceil_div(n - 1, 256), (int64_t)nch + ap->max_cross_blocks)));
+            }
         }
-        if (ok) {
-            if (cross.empty()) cross.push_back(0);
-            ap->nch = nch;
-            ap->need_words = need_words;
-            ap->max_cross_blocks = (int)ceil_div(max_cross, 256);
-            A(ap->d_node_start.upload(ctx, node_start));
-            A(ap->d_need.upload(ctx, need));
-            A(ap->d_cross.upload(ctx, cross));
-            A(ap->d_cross_ptr.upload(ctx, cross_ptr));
-            A(ap->d_chunk_tot.alloc(ctx, (size_t)S * ((size_t)nch + 1)));
-            A(ap->d_npart.alloc(ctx, (size_t)S * (size_t)std::max<int64_t>(ceil_div(n - 1, 256), (int64_t)nch + ap->max_cross_blocks)));
+        if (st == POLEE_OK && !getenv("POLEE_APPROX_NO_OPEN_LISTS")) {  // (A/B)
+            // the gradient scan's chunk offsets from the trees (build_open_lists): kept unless the trees are so deep that the lists
+            // would pass 32 M entries in all -- the three-phase scan stays for those
+            std::vector<uint32_t> optr, ocode;
+            bool ok = true;
+            for (const PttPlan &pl : ap->t->plans)
+                ok = ok && (int64_t)pl.tour_code.size() == ap->t->TL &&
+                     build_open_lists(pl.tour_code.data(), ap->t->TL, SCAN_CHUNK, (size_t)32 << 20, optr, ocode);
+            if (ok) {
+                if (ocode.empty()) ocode.push_back(4u | TOUR_LEAF);  // (never read)
+                A(ap->d_open_ptr.upload(ctx, optr));
+                A(ap->d_open_code.upload(ctx, ocode));
+            }
         }
-    }
-    if (st == POLEE_OK && !getenv("POLEE_APPROX_NO_OPEN_LISTS")) {  // (A/B)
-        // the gradient scan's chunk offsets from the trees (build_open_lists): kept unless the trees are so deep that the lists
-        // would pass 32 M entries in all -- the three-phase scan stays for those
-        std::vector<uint32_t> optr, ocode;
-        bool ok = true;
-        for (const PttPlan &pl : ap->t->plans)
-            ok = ok && (int64_t)pl.tour_code.size() == ap->t->TL &&
-                 build_open_lists(pl.tour_code.data(), ap->t->TL, SCAN_CHUNK, (size_t)32 << 20, optr, ocode);
-        if (ok) {
-            if (ocode.empty()) ocode.push_back(4u | TOUR_LEAF);  // (never read)
-            A(ap->d_open_ptr.upload(ctx, optr));
-            A(ap->d_open_code.upload(ctx, ocode));
+        if (st != POLEE_OK) {
+            polee_approx_destroy(ap);
+            return st;
         }
-    }
-    if (st != POLEE_OK) {
-        polee_approx_destroy(ap);
-        return st;
-    }
-    *out = ap;
-    return POLEE_OK;
+        *out = ap;
+        return POLEE_OK;
+    });
 }
 
 void polee_approx_destroy(polee_approx *ap)
@@ -583,117 +584,113 @@ void polee_approx_destroy(polee_approx *ap)
 
 polee_status polee_approx_logprob_device(polee_approx *ap, const float *d_x, float *d_lp, float *d_x_grad)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ap->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!d_x || !d_lp) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ptt *t = ap->t;
-    hipStream_t st = ctx->stream;
-    const int S = ap->S, n = ap->n;
-    const int64_t nm1 = n - 1;
-    const bool grad = d_x_grad != nullptr;
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(ap->d_acc.p, 0, sizeof(double) * S * 8, st));
-    // few blocks per sample: each ends in three same-address f64 atomics, which serialise (256 deep they cost ~20 us)
-    const unsigned nb = (unsigned)std::min<int64_t>(ceil_div(n, 256), 40);
-    hipLaunchKernelGGL(approx_sums_kernel, dim3(nb, S), dim3(256), 0, st, ap->view(), d_x, ap->d_acc.p);
-    POLEE_KERNEL_CHECK(ctx);
-    int nblk = (int)ceil_div(nm1, 256);
-    if (ap->d_node_start.p) {
-        const ApproxChunkTables T{ap->d_node_start.p, ap->d_need.p, ap->d_cross.p, ap->d_cross_ptr.p, ap->nch, ap->need_words, ap->max_cross_blocks};
-        nblk = ap->nch + ap->max_cross_blocks;
-        hipLaunchKernelGGL(approx_leaf_nodes_kernel, dim3((unsigned)ap->nch, S), dim3(256), 0, st, t->view(), ap->view(), T, d_x,
-                           (const double *)ap->d_acc.p, t->d_C.p, ap->d_chunk_tot.p, ap->d_npart.p, nblk, grad ? ap->d_tpair.p : nullptr);
-        if (ap->max_cross_blocks > 0) {
-            hipLaunchKernelGGL((scan_spine_kernel<dd>), dim3(S), dim3(SCAN_THREADS), 0, st, ap->d_chunk_tot.p, ap->nch + 1);
-            hipLaunchKernelGGL(approx_cross_nodes_kernel, dim3((unsigned)ap->max_cross_blocks, S), dim3(256), 0, st, t->view(), ap->view(), T,
-                               (const dd *)t->d_C.p, (const dd *)ap->d_chunk_tot.p, ap->d_npart.p, nblk, grad ? ap->d_tpair.p : nullptr);
-        }
-    } else {
-        ApproxLeafLoad load{t->view(), ap->view(), d_x, ap->d_acc.p};
-        LeafPrefixEmit emit{n, t->d_C.p};
-        hipError_t e0 = run_scan_partial<dd>(st, S, n, t->d_chunk.p, nullptr, load, emit);
-        if (e0 != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e0));
-        hipLaunchKernelGGL(approx_nodes_kernel, dim3((unsigned)ceil_div(nm1, 256), S), dim3(256), 0, st, t->view(),
-                           ap->view(), t->d_C.p, ap->d_npart.p, grad ? ap->d_tpair.p : nullptr);
-    }
-    hipError_t e = hipSuccess;
-    if (!grad)
-        hipLaunchKernelGGL(approx_finish_lp_kernel, dim3(S), dim3(256), 0, st, ap->view(), ap->d_acc.p, ap->d_npart.p,
-                           nblk, ap->d_sum_log_l.p, d_lp, (const double *)nullptr, 0, (double *)nullptr);
-    POLEE_KERNEL_CHECK(ctx);
-    if (grad) {
-        ApproxGradLoad gl{t->view(), ap->d_tpair.p};
-        ApproxGradEmit ge{gl, ap->view(), d_x, ap->d_acc.p, ap->d_bp.p};
-        if (ap->d_open_ptr.p) {
-            // (chunk offsets from the trees' open-edge lists: the reduce launch and the spine of the three-phase scan are not needed)
-            const int nch = scan_num_chunks(t->TL);
-            hipLaunchKernelGGL((scan_apply_partial_open_kernel<ApproxGradLoad, ApproxGradEmit>), dim3(nch, S), dim3(SCAN_THREADS), 0, st, gl, ge,
-                               t->TL, nch, (const uint32_t *)ap->d_open_ptr.p, (const uint32_t *)ap->d_open_code.p, t->T == 1 ? 0 : 1, t->d_part.p);
-            e = hipGetLastError();
-        } else {
-            e = run_scan_partial<dd>(st, S, t->TL, t->d_chunk.p, t->d_part.p, gl, ge);
-        }
-        if (e != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
-        // (lp and the scan's two dot products in one single-workgroup launch per sample)
-        hipLaunchKernelGGL(approx_finish_lp_kernel, dim3(S), dim3(256), 0, st, ap->view(), ap->d_acc.p, ap->d_npart.p,
-                           nblk, ap->d_sum_log_l.p, d_lp, (const double *)t->d_part.p, scan_num_chunks(t->TL),
-                           ap->d_dots.p);
-        hipLaunchKernelGGL(approx_finish_grad_kernel, dim3((unsigned)ceil_div(n, 256), S), dim3(256), 0, st,
-                           ap->view(), d_x, ap->d_acc.p, ap->d_dots.p, ap->d_bp.p, d_x_grad);
+    return entry(ap, "polee_approx_logprob_device", [&](polee_ctx *ctx) -> polee_status {
+        if (!d_x || !d_lp) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_logprob_device: null argument");
+        polee_ptt *t = ap->t;
+        hipStream_t st = ctx->stream;
+        const int S = ap->S, n = ap->n;
+        const int64_t nm1 = n - 1;
+        const bool grad = d_x_grad != nullptr;
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(ap->d_acc.p, 0, sizeof(double) * S * 8, st));
+        // few blocks per sample: each ends in three same-address f64 atomics, which serialise (256 deep they cost ~20 us)
+        const unsigned nb = (unsigned)std::min<int64_t>(ceil_div(n, 256), 40);
+        hipLaunchKernelGGL(approx_sums_kernel, dim3(nb, S), dim3(256), 0, st, ap->view(), d_x, ap->d_acc.p);
         POLEE_KERNEL_CHECK(ctx);
-    }
-    return POLEE_OK;
+        int nblk = (int)ceil_div(nm1, 256);
+        if (ap->d_node_start.p) {
+            const ApproxChunkTables T{ap->d_node_start.p, ap->d_need.p, ap->d_cross.p, ap->d_cross_ptr.p, ap->nch, ap->need_words, ap->max_cross_blocks};
+            nblk = ap->nch + ap->max_cross_blocks;
+            hipLaunchKernelGGL(approx_leaf_nodes_kernel, dim3((unsigned)ap->nch, S), dim3(256), 0, st, t->view(), ap->view(), T, d_x,
+                               (const double *)ap->d_acc.p, t->d_C.p, ap->d_chunk_tot.p, ap->d_npart.p, nblk, grad ? ap->d_tpair.p : nullptr);
+            if (ap->max_cross_blocks > 0) {
+                hipLaunchKernelGGL((scan_spine_kernel<dd>), dim3(S), dim3(SCAN_THREADS), 0, st, ap->d_chunk_tot.p, ap->nch + 1);
+                hipLaunchKernelGGL(approx_cross_nodes_kernel, dim3((unsigned)ap->max_cross_blocks, S), dim3(256), 0, st, t->view(), ap->view(), T,
+                                   (const dd *)t->d_C.p, (const dd *)ap->d_chunk_tot.p, ap->d_npart.p, nblk, grad ? ap->d_tpair.p : nullptr);
+            }
+        } else {
+            ApproxLeafLoad load{t->view(), ap->view(), d_x, ap->d_acc.p};
+            LeafPrefixEmit emit{n, t->d_C.p};
+            hipError_t e0 = run_scan_partial<dd>(st, S, n, t->d_chunk.p, nullptr, load, emit);
+            if (e0 != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e0));
+            hipLaunchKernelGGL(approx_nodes_kernel, dim3((unsigned)ceil_div(nm1, 256), S), dim3(256), 0, st, t->view(),
+                               ap->view(), t->d_C.p, ap->d_npart.p, grad ? ap->d_tpair.p : nullptr);
+        }
+        hipError_t e = hipSuccess;
+        if (!grad)
+            hipLaunchKernelGGL(approx_finish_lp_kernel, dim3(S), dim3(256), 0, st, ap->view(), ap->d_acc.p, ap->d_npart.p,
+                               nblk, ap->d_sum_log_l.p, d_lp, (const double *)nullptr, 0, (double *)nullptr);
+        POLEE_KERNEL_CHECK(ctx);
+        if (grad) {
+            ApproxGradLoad gl{t->view(), ap->d_tpair.p};
+            ApproxGradEmit ge{gl, ap->view(), d_x, ap->d_acc.p, ap->d_bp.p};
+            if (ap->d_open_ptr.p) {
+                // (chunk offsets from the trees' open-edge lists: the reduce launch and the spine of the three-phase scan are not needed)
+                const int nch = scan_num_chunks(t->TL);
+                hipLaunchKernelGGL((scan_apply_partial_open_kernel<ApproxGradLoad, ApproxGradEmit>), dim3(nch, S), dim3(SCAN_THREADS), 0, st, gl, ge,
+                                   t->TL, nch, (const uint32_t *)ap->d_open_ptr.p, (const uint32_t *)ap->d_open_code.p, t->T == 1 ? 0 : 1, t->d_part.p);
+                e = hipGetLastError();
+            } else {
+                e = run_scan_partial<dd>(st, S, t->TL, t->d_chunk.p, t->d_part.p, gl, ge);
+            }
+            if (e != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
+            // (lp and the scan's two dot products in one single-workgroup launch per sample)
+            hipLaunchKernelGGL(approx_finish_lp_kernel, dim3(S), dim3(256), 0, st, ap->view(), ap->d_acc.p, ap->d_npart.p,
+                               nblk, ap->d_sum_log_l.p, d_lp, (const double *)t->d_part.p, scan_num_chunks(t->TL),
+                               ap->d_dots.p);
+            hipLaunchKernelGGL(approx_finish_grad_kernel, dim3((unsigned)ceil_div(n, 256), S), dim3(256), 0, st,
+                               ap->view(), d_x, ap->d_acc.p, ap->d_dots.p, ap->d_bp.p, d_x_grad);
+            POLEE_KERNEL_CHECK(ctx);
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_approx_logprob(polee_approx *ap, const float *x, float *lp, float *x_grad)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ap->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!x || !lp) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
-    const size_t sn = (size_t)ap->S * ap->n;
-    POLEE_TRY(ap->d_x.upload(ctx, x, sn));
-    POLEE_TRY(polee_approx_logprob_device(ap, ap->d_x.p, ap->d_lp.p, x_grad ? ap->d_xgrad.p : nullptr));
-    POLEE_TRY(ap->d_lp.download(ctx, lp, ap->S));
-    if (x_grad) POLEE_TRY(ap->d_xgrad.download(ctx, x_grad, sn));
-    return POLEE_OK;
+    return entry(ap, "polee_approx_logprob", [&](polee_ctx *ctx) -> polee_status {
+        if (!x || !lp) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_logprob: null argument");
+        const size_t sn = (size_t)ap->S * ap->n;
+        POLEE_TRY(ap->d_x.upload(ctx, x, sn));
+        POLEE_TRY(polee_approx_logprob_device(ap, ap->d_x.p, ap->d_lp.p, x_grad ? ap->d_xgrad.p : nullptr));
+        POLEE_TRY(ap->d_lp.download(ctx, lp, ap->S));
+        if (x_grad) POLEE_TRY(ap->d_xgrad.download(ctx, x_grad, sn));
+        return POLEE_OK;
+    });
 }
 
 // test hook (include/polee_hip_debug.h): the node terms and the tree gradient the last call with a gradient left on the device
 polee_status polee_debug_approx_node_terms(polee_approx *ap, double *tpair, float *bp)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ap->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!tpair || !bp) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
-    POLEE_TRY(ap->d_tpair.download(ctx, tpair, 2 * (size_t)ap->S * (size_t)(ap->n - 1)));
-    return ap->d_bp.download(ctx, bp, (size_t)ap->S * (size_t)ap->n);
+    return entry(ap, "polee_debug_approx_node_terms", [&](polee_ctx *ctx) -> polee_status {
+        if (!tpair || !bp) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_approx_node_terms: null argument");
+        POLEE_TRY(ap->d_tpair.download(ctx, tpair, 2 * (size_t)ap->S * (size_t)(ap->n - 1)));
+        return ap->d_bp.download(ctx, bp, (size_t)ap->S * (size_t)ap->n);
+    });
 }
 
 polee_status polee_approx_gene_logprob(polee_approx *ap, const float *x_gene, const float *x_isoform,
                                        const int32_t *gene_of, int32_t G, float *lp, float *gene_grad,
                                        float *isoform_grad)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ap->ctx;
-    POLEE_TRY(use_device(ctx));
-    const int S = ap->S, n = ap->n;
-    if (!x_gene || !x_isoform || !gene_of || !lp) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if ((gene_grad == nullptr) != (isoform_grad == nullptr))
-        return fail(ctx, POLEE_ERR_BAD_ARG, "ask for both gradients or for none");
-    POLEE_TRY(approx_set_genes(ap, gene_of, G));
-    DevBuf<float> d_xg, d_xi, d_gg;
-    const size_t sn = (size_t)S * n, sg = (size_t)S * G;
-    POLEE_TRY(d_xg.upload(ctx, x_gene, sg));
-    POLEE_TRY(d_xi.upload(ctx, x_isoform, sn));
-    if (gene_grad) POLEE_TRY(d_gg.alloc(ctx, sg));
-    POLEE_TRY(approx_gene_logprob_device(ap, d_xg.p, d_xi.p, ap->d_lp.p, gene_grad ? d_gg.p : nullptr));
-    POLEE_TRY(ap->d_lp.download(ctx, lp, S));
-    if (gene_grad) {
-        POLEE_TRY(d_gg.download(ctx, gene_grad, sg));
-        POLEE_TRY(d_xi.download(ctx, isoform_grad, sn));
-    }
-    return POLEE_OK;
+    return entry(ap, "polee_approx_gene_logprob", [&](polee_ctx *ctx) -> polee_status {
+        const int S = ap->S, n = ap->n;
+        if (!x_gene || !x_isoform || !gene_of || !lp) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_gene_logprob: bad argument");
+        if ((gene_grad == nullptr) != (isoform_grad == nullptr))
+            return fail(ctx, POLEE_ERR_BAD_ARG, "ask for both gradients or for none");
+        POLEE_TRY(approx_set_genes(ap, gene_of, G));
+        DevBuf<float> d_xg, d_xi, d_gg;
+        const size_t sn = (size_t)S * n, sg = (size_t)S * G;
+        POLEE_TRY(d_xg.upload(ctx, x_gene, sg));
+        POLEE_TRY(d_xi.upload(ctx, x_isoform, sn));
+        if (gene_grad) POLEE_TRY(d_gg.alloc(ctx, sg));
+        POLEE_TRY(approx_gene_logprob_device(ap, d_xg.p, d_xi.p, ap->d_lp.p, gene_grad ? d_gg.p : nullptr));
+        POLEE_TRY(ap->d_lp.download(ctx, lp, S));
+        if (gene_grad) {
+            POLEE_TRY(d_gg.download(ctx, gene_grad, sg));
+            POLEE_TRY(d_xi.download(ctx, isoform_grad, sn));
+        }
+        return POLEE_OK;
+    });
 }
 
 }  // extern "C"
@@ -729,14 +726,13 @@ extern "C" {
 
 polee_status polee_approx_sample(polee_approx *ap, const float *z0, uint64_t seed, float *x)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ap->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!x) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
-    const size_t sn = (size_t)ap->S * ap->n, sk = (size_t)ap->S * (ap->n - 1);
-    if (z0) POLEE_TRY(ap->d_z0.upload(ctx, z0, sk));
-    POLEE_TRY(approx_sample_device(ap, z0 ? ap->d_z0.p : nullptr, seed));
-    return ap->d_x.download(ctx, x, sn);
+    return entry(ap, "polee_approx_sample", [&](polee_ctx *ctx) -> polee_status {
+        if (!x) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_sample: null argument");
+        const size_t sn = (size_t)ap->S * ap->n, sk = (size_t)ap->S * (ap->n - 1);
+        if (z0) POLEE_TRY(ap->d_z0.upload(ctx, z0, sk));
+        POLEE_TRY(approx_sample_device(ap, z0 ? ap->d_z0.p : nullptr, seed));
+        return ap->d_x.download(ctx, x, sn);
+    });
 }
 
 // ---- feature (gene) expression approximated by a normal, from sampler draws (polee_gene_expression.py:157-222)
@@ -830,22 +826,21 @@ polee_status polee_approx_feature_moments(polee_approx *ap, const int32_t *featu
                                           int64_t num_pairs, int32_t F, int32_t num_mean_draws, int32_t num_var_draws,
                                           uint64_t seed, const float *z0, float *loc, float *scale)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ap->ctx;
-    POLEE_TRY(use_device(ctx));
-    const int n = ap->n;
-    if (!feature_idxs || !transcript_idxs || !loc || !scale || num_pairs < 1 || F < 1 || num_mean_draws < 1 ||
-        num_var_draws < 1)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    std::vector<int32_t> fi((size_t)num_pairs), ti((size_t)num_pairs);
-    for (int64_t p = 0; p < num_pairs; ++p) {  // 1-based, as the reference passes them
-        if (feature_idxs[p] < 1 || feature_idxs[p] > F || transcript_idxs[p] < 1 || transcript_idxs[p] > n)
-            return fail(ctx, POLEE_ERR_BAD_ARG, "pair %lld (%d, %d) out of range", (long long)p, feature_idxs[p],
-                        transcript_idxs[p]);
-        fi[(size_t)p] = feature_idxs[p] - 1;
-        ti[(size_t)p] = transcript_idxs[p] - 1;
-    }
-    return feature_moments_impl(ap, fi, ti, {}, {}, F, num_mean_draws, num_var_draws, seed, z0, loc, scale);
+    return entry(ap, "polee_approx_feature_moments", [&](polee_ctx *ctx) -> polee_status {
+        const int n = ap->n;
+        if (!feature_idxs || !transcript_idxs || !loc || !scale || num_pairs < 1 || F < 1 || num_mean_draws < 1 ||
+            num_var_draws < 1)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_feature_moments: bad argument");
+        std::vector<int32_t> fi((size_t)num_pairs), ti((size_t)num_pairs);
+        for (int64_t p = 0; p < num_pairs; ++p) {  // 1-based, as the reference passes them
+            if (feature_idxs[p] < 1 || feature_idxs[p] > F || transcript_idxs[p] < 1 || transcript_idxs[p] > n)
+                return fail(ctx, POLEE_ERR_BAD_ARG, "pair %lld (%d, %d) out of range", (long long)p, feature_idxs[p],
+                            transcript_idxs[p]);
+            fi[(size_t)p] = feature_idxs[p] - 1;
+            ti[(size_t)p] = transcript_idxs[p] - 1;
+        }
+        return feature_moments_impl(ap, fi, ti, {}, {}, F, num_mean_draws, num_var_draws, seed, z0, loc, scale);
+    });
 }
 
 polee_status polee_approx_splicing_moments(polee_approx *ap, const int32_t *feature_indices, int64_t num_feature_pairs,
@@ -853,27 +848,26 @@ polee_status polee_approx_splicing_moments(polee_approx *ap, const int32_t *feat
                                            int32_t num_mean_draws, int32_t num_var_draws, uint64_t seed, const float *z0,
                                            float *loc, float *scale)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ap->ctx;
-    POLEE_TRY(use_device(ctx));
-    const int n = ap->n;
-    if (!feature_indices || !antifeature_indices || !loc || !scale || num_feature_pairs < 1 || num_antifeature_pairs < 1 ||
-        F < 1 || num_mean_draws < 1 || num_var_draws < 1)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    auto unpack = [&](const int32_t *pairs, int64_t cnt, std::vector<int32_t> &f, std::vector<int32_t> &t) -> bool {
-        f.resize((size_t)cnt);
-        t.resize((size_t)cnt);
-        for (int64_t p = 0; p < cnt; ++p) {  // rows (feature, transcript), 0-based (polee_splicing.py:69-80)
-            f[(size_t)p] = pairs[2 * p];
-            t[(size_t)p] = pairs[2 * p + 1];
-            if (f[(size_t)p] < 0 || f[(size_t)p] >= F || t[(size_t)p] < 0 || t[(size_t)p] >= n) return false;
-        }
-        return true;
-    };
-    std::vector<int32_t> fi, ti, afi, ati;
-    if (!unpack(feature_indices, num_feature_pairs, fi, ti) || !unpack(antifeature_indices, num_antifeature_pairs, afi, ati))
-        return fail(ctx, POLEE_ERR_BAD_ARG, "feature / antifeature index out of range");
-    return feature_moments_impl(ap, fi, ti, afi, ati, F, num_mean_draws, num_var_draws, seed, z0, loc, scale);
+    return entry(ap, "polee_approx_splicing_moments", [&](polee_ctx *ctx) -> polee_status {
+        const int n = ap->n;
+        if (!feature_indices || !antifeature_indices || !loc || !scale || num_feature_pairs < 1 || num_antifeature_pairs < 1 ||
+            F < 1 || num_mean_draws < 1 || num_var_draws < 1)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_approx_splicing_moments: bad argument");
+        auto unpack = [&](const int32_t *pairs, int64_t cnt, std::vector<int32_t> &f, std::vector<int32_t> &t) -> bool {
+            f.resize((size_t)cnt);
+            t.resize((size_t)cnt);
+            for (int64_t p = 0; p < cnt; ++p) {  // rows (feature, transcript), 0-based (polee_splicing.py:69-80)
+                f[(size_t)p] = pairs[2 * p];
+                t[(size_t)p] = pairs[2 * p + 1];
+                if (f[(size_t)p] < 0 || f[(size_t)p] >= F || t[(size_t)p] < 0 || t[(size_t)p] >= n) return false;
+            }
+            return true;
+        };
+        std::vector<int32_t> fi, ti, afi, ati;
+        if (!unpack(feature_indices, num_feature_pairs, fi, ti) || !unpack(antifeature_indices, num_antifeature_pairs, afi, ati))
+            return fail(ctx, POLEE_ERR_BAD_ARG, "feature / antifeature index out of range");
+        return feature_moments_impl(ap, fi, ti, afi, ati, F, num_mean_draws, num_var_draws, seed, z0, loc, scale);
+    });
 }
 
 }  // extern "C"

@@ -233,17 +233,6 @@ struct polee_bias_train {
 
 namespace {
 
-template <class F>
-polee_status bt_entry(polee_bias_train *bt, const char *name, F &&f)
-{
-    if (!bt) return fail(nullptr, POLEE_ERR_BAD_ARG, "%s: null handle", name);
-    polee_ctx *ctx = bt->ctx;
-    return guarded(ctx, name, [&]() -> polee_status {
-        if (!bt->host) POLEE_TRY(use_device(ctx));
-        return f(ctx);
-    });
-}
-
 SearchState fresh_state()
 {
     SearchState s;
@@ -480,9 +469,9 @@ polee_status polee_bias_train_create(polee_ctx *ctx, int32_t n, const int64_t *t
                                      const int32_t *bg_transcript, const int64_t *bg_tpos, const int32_t *bg_fraglen,
                                      const polee_bias_train_opts *opts, polee_bias_train **out)
 {
-    const bool host = opts && opts->host != 0;
-    polee_ctx *ectx = host ? nullptr : ctx;
-    return guarded(ectx, "polee_bias_train_create", [&]() -> polee_status {
+    return host_entry("polee_bias_train_create", [&]() -> polee_status {
+        const bool host = opts && opts->host != 0;
+        polee_ctx *ectx = host ? nullptr : ctx;
         if (!out) return fail(ectx, POLEE_ERR_BAD_ARG, "polee_bias_train_create: null output");
         *out = nullptr;
         if (!host) POLEE_TRY(use_device(ctx));
@@ -536,9 +525,9 @@ polee_status polee_bias_train_create(polee_ctx *ctx, int32_t n, const int64_t *t
 polee_status polee_bias_train_create_from_examples(polee_ctx *ctx, int64_t n_fg, int64_t n_bg, const uint8_t *left_seq, const uint8_t *right_seq,
                                                    const double *frag_gc, const polee_bias_train_opts *opts, polee_bias_train **out)
 {
-    const bool host = opts && opts->host != 0;
-    polee_ctx *ectx = host ? nullptr : ctx;
-    return guarded(ectx, "polee_bias_train_create_from_examples", [&]() -> polee_status {
+    return host_entry("polee_bias_train_create_from_examples", [&]() -> polee_status {
+        const bool host = opts && opts->host != 0;
+        polee_ctx *ectx = host ? nullptr : ctx;
         if (!out) return fail(ectx, POLEE_ERR_BAD_ARG, "polee_bias_train_create_from_examples: null output");
         *out = nullptr;
         if (!host) POLEE_TRY(use_device(ctx));
@@ -582,7 +571,7 @@ void polee_bias_train_destroy(polee_bias_train *bt)
 
 polee_status polee_bias_train_run(polee_bias_train *bt)
 {
-    return bt_entry(bt, "polee_bias_train_run", [&](polee_ctx *) -> polee_status {
+    return entry(bt, "polee_bias_train_run", [&](polee_ctx *ctx) -> polee_status {
         if (bt->host) {
             bt->ht.run();
             return POLEE_OK;
@@ -595,7 +584,7 @@ polee_status polee_bias_train_run(polee_bias_train *bt)
 
 polee_status polee_bias_train_candidates(polee_bias_train *bt, int32_t side, const int32_t *orders_in, double *losses_out, double *loss0_out)
 {
-    return bt_entry(bt, "polee_bias_train_candidates", [&](polee_ctx *ctx) -> polee_status {
+    return entry(bt, "polee_bias_train_candidates", [&](polee_ctx *ctx) -> polee_status {
         if ((side != 0 && side != 1) || !orders_in || !losses_out || !loss0_out)
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_bias_train_candidates: bad argument");
         for (int j = 0; j < BT_K; ++j)
@@ -614,7 +603,7 @@ polee_status polee_bias_train_candidates(polee_bias_train *bt, int32_t side, con
 polee_status polee_bias_train_get_model(polee_bias_train *bt, int32_t *orders_left, int32_t *orders_right, float *ps_left, float *ps_right,
                                         float *gc_bins, float *gc_qs, double *accuracy)
 {
-    return bt_entry(bt, "polee_bias_train_get_model", [&](polee_ctx *ctx) -> polee_status {
+    return entry(bt, "polee_bias_train_get_model", [&](polee_ctx *ctx) -> polee_status {
         const Model &m = bt->host ? bt->ht.model : bt->model;
         if (!m.trained) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_bias_train_get_model: polee_bias_train_run has not completed");
         if (orders_left) std::copy(m.orders[0], m.orders[0] + BT_K, orders_left);
@@ -631,7 +620,7 @@ polee_status polee_bias_train_get_model(polee_bias_train *bt, int32_t *orders_le
 polee_status polee_bias_train_get_examples(polee_bias_train *bt, int64_t *n_fg, int64_t *n_bg, uint64_t *left, uint64_t *right, double *frag_gc,
                                            int64_t *bg_tpos)
 {
-    return bt_entry(bt, "polee_bias_train_get_examples", [&](polee_ctx *ctx) -> polee_status {
+    return entry(bt, "polee_bias_train_get_examples", [&](polee_ctx *ctx) -> polee_status {
         const size_t N = (size_t)bt->N();
         if (n_fg) *n_fg = bt->n_fg;
         if (n_bg) *n_bg = bt->n_bg;
@@ -654,7 +643,7 @@ polee_status polee_bias_train_get_examples(polee_bias_train *bt, int64_t *n_fg, 
 
 polee_status polee_bias_train_get_trace(polee_bias_train *bt, int32_t side, int32_t *rounds, int32_t *positions, double *losses)
 {
-    return bt_entry(bt, "polee_bias_train_get_trace", [&](polee_ctx *ctx) -> polee_status {
+    return entry(bt, "polee_bias_train_get_trace", [&](polee_ctx *ctx) -> polee_status {
         const Model &m = bt->host ? bt->ht.model : bt->model;
         if (side != 0 && side != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_bias_train_get_trace: side must be 0 (left) or 1 (right)");
         if (!m.trained) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_bias_train_get_trace: polee_bias_train_run has not completed");

@@ -321,9 +321,7 @@ void polee_classify_default_opts(polee_classify_opts *o)
 
 polee_status polee_classify_create(polee_ctx *ctx, int32_t n, int32_t k, const polee_classify_opts *opts, polee_classify **out)
 {
-    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_create: null context");
-    return guarded(ctx, "polee_classify_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_classify_create", [&]() -> polee_status {
         if (!out || n < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_create: bad argument");
         if (k < 2 || k > 16)
             return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_classify_create: %d classes; the kernels are built for 2..16", k);
@@ -382,11 +380,12 @@ void polee_classify_destroy(polee_classify *cl)
 
 polee_status polee_classify_set_opts(polee_classify *cl, const polee_classify_opts *opts)
 {
-    if (!cl) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_classify_set_opts: null handle");
-    if (!opts) return fail(cl->ctx, POLEE_ERR_BAD_ARG, "polee_classify_set_opts: null argument");
-    POLEE_TRY(check_opts(cl->ctx, *opts));
-    cl->o = *opts;
-    return POLEE_OK;
+    return entry(cl, "polee_classify_set_opts", [&](polee_ctx *ctx) -> polee_status {
+        if (!opts) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_classify_set_opts: null argument");
+        POLEE_TRY(check_opts(ctx, *opts));
+        cl->o = *opts;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_classify_get_params(polee_classify *cl, float *w, float *x_bias, float *z_bias)

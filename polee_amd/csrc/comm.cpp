@@ -118,63 +118,67 @@ extern "C" {
 
 polee_status polee_comm_unique_id(uint8_t id[POLEE_COMM_ID_BYTES])
 {
-    if (!id) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    std::string err;
-    Rccl *r = rccl(err);
-    if (!r) return fail(nullptr, POLEE_ERR_UNSUPPORTED, "%s", err.c_str());
-    static_assert(sizeof(ncclUniqueId) == POLEE_COMM_ID_BYTES, "ncclUniqueId is 128 bytes");
-    ncclUniqueId uid;
-    const ncclResult_t rc = r->GetUniqueId(&uid);
-    if (rc != ncclSuccess) return fail(nullptr, POLEE_ERR_HIP, "ncclGetUniqueId failed (%d)", (int)rc);
-    memcpy(id, &uid, POLEE_COMM_ID_BYTES);
-    return POLEE_OK;
+    return host_entry("polee_comm_unique_id", [&]() -> polee_status {
+        if (!id) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_comm_unique_id: null argument");
+        std::string err;
+        Rccl *r = rccl(err);
+        if (!r) return fail(nullptr, POLEE_ERR_UNSUPPORTED, "%s", err.c_str());
+        static_assert(sizeof(ncclUniqueId) == POLEE_COMM_ID_BYTES, "ncclUniqueId is 128 bytes");
+        ncclUniqueId uid;
+        const ncclResult_t rc = r->GetUniqueId(&uid);
+        if (rc != ncclSuccess) return fail(nullptr, POLEE_ERR_HIP, "ncclGetUniqueId failed (%d)", (int)rc);
+        memcpy(id, &uid, POLEE_COMM_ID_BYTES);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_comm_create(polee_ctx *ctx, int32_t nranks, int32_t rank, const uint8_t id[POLEE_COMM_ID_BYTES],
                                polee_comm **out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!out || !id || nranks < 1 || rank < 0 || rank >= nranks)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_comm_create: bad argument (rank %d of %d)", rank, nranks);
-    std::string err;
-    Rccl *r = rccl(err);
-    if (!r) return fail(ctx, POLEE_ERR_UNSUPPORTED, "%s", err.c_str());
-    ncclUniqueId uid;
-    memcpy(&uid, id, POLEE_COMM_ID_BYTES);
-    ncclComm_t comm = nullptr;
-    const ncclResult_t rc = r->CommInitRank(&comm, nranks, uid, rank);
-    if (rc != ncclSuccess || !comm)
-        return fail(ctx, POLEE_ERR_HIP, "ncclCommInitRank failed: %s", r->GetErrorString ? r->GetErrorString(rc) : "?");
-    polee_comm *c = new (std::nothrow) polee_comm();
-    if (!c) {
-        r->CommDestroy(comm);
-        return fail(ctx, POLEE_ERR_OOM, "out of host memory");
-    }
-    c->ctx = ctx;
-    c->comm = comm;
-    c->nranks = nranks;
-    c->rank = rank;
-    ctx_retain(ctx);
-    *out = c;
-    return POLEE_OK;
+    return ctx_entry(ctx, "polee_comm_create", [&]() -> polee_status {
+        if (!out || !id || nranks < 1 || rank < 0 || rank >= nranks)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_comm_create: bad argument (rank %d of %d)", rank, nranks);
+        std::string err;
+        Rccl *r = rccl(err);
+        if (!r) return fail(ctx, POLEE_ERR_UNSUPPORTED, "%s", err.c_str());
+        ncclUniqueId uid;
+        memcpy(&uid, id, POLEE_COMM_ID_BYTES);
+        ncclComm_t comm = nullptr;
+        const ncclResult_t rc = r->CommInitRank(&comm, nranks, uid, rank);
+        if (rc != ncclSuccess || !comm)
+            return fail(ctx, POLEE_ERR_HIP, "ncclCommInitRank failed: %s", r->GetErrorString ? r->GetErrorString(rc) : "?");
+        polee_comm *c = new (std::nothrow) polee_comm();
+        if (!c) {
+            r->CommDestroy(comm);
+            return fail(ctx, POLEE_ERR_OOM, "out of host memory");
+        }
+        c->ctx = ctx;
+        c->comm = comm;
+        c->nranks = nranks;
+        c->rank = rank;
+        ctx_retain(ctx);
+        *out = c;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_comm_create_host(polee_ctx *ctx, int32_t nranks, int32_t rank, polee_host_allreduce_fn allreduce, void *user,
                                     polee_comm **out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!out || !allreduce || nranks < 1 || rank < 0 || rank >= nranks)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_comm_create_host: bad argument (rank %d of %d)", rank, nranks);
-    polee_comm *c = new (std::nothrow) polee_comm();
-    if (!c) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
-    c->ctx = ctx;
-    c->host_allreduce = allreduce;
-    c->host_user = user;
-    c->nranks = nranks;
-    c->rank = rank;
-    ctx_retain(ctx);
-    *out = c;
-    return POLEE_OK;
+    return ctx_entry(ctx, "polee_comm_create_host", [&]() -> polee_status {
+        if (!out || !allreduce || nranks < 1 || rank < 0 || rank >= nranks)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_comm_create_host: bad argument (rank %d of %d)", rank, nranks);
+        polee_comm *c = new (std::nothrow) polee_comm();
+        if (!c) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
+        c->ctx = ctx;
+        c->host_allreduce = allreduce;
+        c->host_user = user;
+        c->nranks = nranks;
+        c->rank = rank;
+        ctx_retain(ctx);
+        *out = c;
+        return POLEE_OK;
+    });
 }
 
 void polee_comm_destroy(polee_comm *c)
@@ -197,43 +201,41 @@ void polee_comm_destroy(polee_comm *c)
 // bracketed by HIP events: *ms_avg = the exchange's own time per call (what a row-sharded pass or a regression step adds)
 polee_status polee_debug_comm_allreduce_ms(polee_comm *c, int64_t count, int32_t reps, double *ms_avg)
 {
-    if (!c) return fail(nullptr, POLEE_ERR_BAD_ARG, "null communicator");
-    polee_ctx *ctx = c->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (count < 1 || reps < 1 || !ms_avg) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    DevBuf<float> d;
-    POLEE_TRY(d.alloc(ctx, (size_t)count));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(d.p, 0, sizeof(float) * (size_t)count, ctx->stream));
-    POLEE_TRY(comm_allreduce_device(c, d.p, (size_t)count, false));  // (first call: connection set-up, not timed)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    POLEE_HIP_TRY(ctx, hipEventCreate(&e0));
-    hipError_t he = hipEventCreate(&e1);
-    polee_status st = POLEE_OK;
-    if (he == hipSuccess) he = hipEventRecord(e0, ctx->stream);
-    for (int32_t i = 0; i < reps && he == hipSuccess && st == POLEE_OK; ++i) st = comm_allreduce_device(c, d.p, (size_t)count, false);
-    if (he == hipSuccess) he = hipEventRecord(e1, ctx->stream);
-    if (he == hipSuccess) he = hipEventSynchronize(e1);
-    float ms = 0.0f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (st != POLEE_OK) return st;
-    if (he != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "all-reduce timing failed: %s", hipGetErrorString(he));
-    *ms_avg = (double)ms / reps;
-    return POLEE_OK;
+    return entry(c, "polee_debug_comm_allreduce_ms", [&](polee_ctx *ctx) -> polee_status {
+        if (count < 1 || reps < 1 || !ms_avg) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_comm_allreduce_ms: bad argument");
+        DevBuf<float> d;
+        POLEE_TRY(d.alloc(ctx, (size_t)count));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(d.p, 0, sizeof(float) * (size_t)count, ctx->stream));
+        POLEE_TRY(comm_allreduce_device(c, d.p, (size_t)count, false));  // (first call: connection set-up, not timed)
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        POLEE_HIP_TRY(ctx, hipEventCreate(&e0));
+        hipError_t he = hipEventCreate(&e1);
+        polee_status st = POLEE_OK;
+        if (he == hipSuccess) he = hipEventRecord(e0, ctx->stream);
+        for (int32_t i = 0; i < reps && he == hipSuccess && st == POLEE_OK; ++i) st = comm_allreduce_device(c, d.p, (size_t)count, false);
+        if (he == hipSuccess) he = hipEventRecord(e1, ctx->stream);
+        if (he == hipSuccess) he = hipEventSynchronize(e1);
+        float ms = 0.0f;
+        if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (st != POLEE_OK) return st;
+        if (he != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "all-reduce timing failed: %s", hipGetErrorString(he));
+        *ms_avg = (double)ms / reps;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_allreduce_sum_f32(polee_comm *c, float *buf, int64_t count)
 {
-    if (!c) return fail(nullptr, POLEE_ERR_BAD_ARG, "null communicator");
-    polee_ctx *ctx = c->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!buf || count < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (count == 0) return POLEE_OK;
-    DevBuf<float> d;
-    POLEE_TRY(d.upload(ctx, buf, (size_t)count));
-    POLEE_TRY(comm_allreduce_device(c, d.p, (size_t)count, false));
-    return d.download(ctx, buf, (size_t)count);
+    return entry(c, "polee_allreduce_sum_f32", [&](polee_ctx *ctx) -> polee_status {
+        if (!buf || count < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_allreduce_sum_f32: bad argument");
+        if (count == 0) return POLEE_OK;
+        DevBuf<float> d;
+        POLEE_TRY(d.upload(ctx, buf, (size_t)count));
+        POLEE_TRY(comm_allreduce_device(c, d.p, (size_t)count, false));
+        return d.download(ctx, buf, (size_t)count);
+    });
 }
 
 // What the TRANSPORT says (first-contact evidence for the multi-GPU runs nobody could make yet):
@@ -241,21 +243,22 @@ polee_status polee_allreduce_sum_f32(polee_comm *c, float *buf, int64_t count)
 // communicator (the creation arguments for a host communicator).
 polee_status polee_comm_info(const polee_comm *c, int32_t *transport, int32_t *count, int32_t *user_rank)
 {
-    if (!c) return fail(nullptr, POLEE_ERR_BAD_ARG, "null communicator");
-    int t = c->host_allreduce ? 2 : 1, n = c->nranks, rk = c->rank;
-    if (!c->host_allreduce && c->comm) {
-        std::string err;
-        Rccl *r = rccl(err);
-        if (r && r->CommCount && r->CommUserRank) {
-            if (r->CommCount(static_cast<ncclComm_t>(c->comm), &n) != ncclSuccess ||
-                r->CommUserRank(static_cast<ncclComm_t>(c->comm), &rk) != ncclSuccess)
-                return fail(c->ctx, POLEE_ERR_COMM, "ncclCommCount / ncclCommUserRank failed");
+    return entry(c, "polee_comm_info", [&](polee_ctx *ctx) -> polee_status {
+        int t = c->host_allreduce ? 2 : 1, n = c->nranks, rk = c->rank;
+        if (!c->host_allreduce && c->comm) {
+            std::string err;
+            Rccl *r = rccl(err);
+            if (r && r->CommCount && r->CommUserRank) {
+                if (r->CommCount(static_cast<ncclComm_t>(c->comm), &n) != ncclSuccess ||
+                    r->CommUserRank(static_cast<ncclComm_t>(c->comm), &rk) != ncclSuccess)
+                    return fail(ctx, POLEE_ERR_COMM, "ncclCommCount / ncclCommUserRank failed");
+            }
         }
-    }
-    if (transport) *transport = t;
-    if (count) *count = n;
-    if (user_rank) *user_rank = rk;
-    return POLEE_OK;
+        if (transport) *transport = t;
+        if (count) *count = n;
+        if (user_rank) *user_rank = rk;
+        return POLEE_OK;
+    });
 }
 
 int32_t polee_comm_rank(const polee_comm *c) { return c ? c->rank : -1; }

@@ -639,24 +639,52 @@ inline polee_status guarded(polee_ctx *ctx, const char *what, F &&f)
     }
 }
 
-// How an entry point on a handle H (a struct with a ctx member) opens: a null handle fails, nothing unwinds through the C ABI, the
-// context's device is current.  f(ctx) is the entry's body.
+// the context of a handle: its ctx member; the approximation handle's struct is private to approx.hip
+polee_ctx *approx_ctx(const polee_approx *ap);
+template <class H>
+inline polee_ctx *handle_ctx(const H *h)
+{
+    return h->ctx;
+}
+inline polee_ctx *handle_ctx(const polee_approx *ap) { return approx_ctx(ap); }
+
+// How every extern "C" function that returns a status opens: with exactly one of the three below as its first statement
+// (tests/test_entry_points.py reads the sources for it).
+// On a handle H: a null handle fails, nothing unwinds through the C ABI, the device of the handle's context is current.  f(ctx) is
+// the entry's body.
 template <class H, class F>
 inline polee_status entry(H *h, const char *name, F &&f)
 {
     if (!h) return fail(nullptr, POLEE_ERR_BAD_ARG, "%s: null handle", name);
-    polee_ctx *ctx = h->ctx;
+    polee_ctx *ctx = handle_ctx(h);
     return guarded(ctx, name, [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+        if (ctx) POLEE_TRY(use_device(ctx));  // (no context: a bias trainer on the host, the one handle that works on no device)
         return f(ctx);
     });
+}
+
+// On a context (creators, context-level functions): the same with the context itself.  f() is the body.
+template <class F>
+inline polee_status ctx_entry(polee_ctx *ctx, const char *name, F &&f)
+{
+    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "%s: null context", name);
+    return guarded(ctx, name, [&]() -> polee_status {
+        POLEE_TRY(use_device(ctx));
+        return f();
+    });
+}
+
+// With neither (host builders, and creators that may work without a device): nothing unwinds, and that is all.
+template <class F>
+inline polee_status host_entry(const char *name, F &&f)
+{
+    return guarded(nullptr, name, std::forward<F>(f));
 }
 
 // draw i of a call under `seed` is made under seed + POLEE_DRAW_STRIDE * i (polee_approx_feature_moments and the draw-fed models)
 constexpr uint64_t POLEE_DRAW_STRIDE = 0x9E3779B97F4A7C15ull;
 
-// accessors of the approximation handle (approx.hip) for its consumers
-polee_ctx *approx_ctx(const polee_approx *ap);
+// accessors of the approximation handle (approx.hip) for its consumers (approx_ctx: above)
 void approx_dims(const polee_approx *ap, int32_t *S, int32_t *n);
 polee_status approx_set_genes(polee_approx *ap, const int32_t *gene_of, int32_t G);
 polee_status approx_gene_logprob_device(polee_approx *ap, const float *d_xg, float *d_xi, float *d_lp, float *d_gg);

@@ -19,20 +19,22 @@ polee_status polee_debug_ptt_plan(const int32_t *node_parent_idxs, const int32_t
                                   uint32_t *tour_code, int32_t *tour_tgt, int32_t *leaf_tid, int32_t *lo,
                                   int32_t *mid, int32_t *hi1, int32_t *max_depth)
 {
-    if (!node_parent_idxs || !node_js) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    std::vector<int32_t> l, r, f;
-    std::string err = children_from_parents(node_parent_idxs, node_js, N, l, r, f);
-    PttPlan pl;
-    if (err.empty()) err = build_ptt_plan(l.data(), r.data(), f.data(), N, pl);
-    if (!err.empty()) return fail(nullptr, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
-    if (tour_code) std::copy(pl.tour_code.begin(), pl.tour_code.end(), tour_code);
-    if (tour_tgt) std::copy(pl.tour_tgt.begin(), pl.tour_tgt.end(), tour_tgt);
-    if (leaf_tid) std::copy(pl.leaf_tid.begin(), pl.leaf_tid.end(), leaf_tid);
-    if (lo) std::copy(pl.lo.begin(), pl.lo.end(), lo);
-    if (mid) std::copy(pl.mid.begin(), pl.mid.end(), mid);
-    if (hi1) std::copy(pl.hi1.begin(), pl.hi1.end(), hi1);
-    if (max_depth) *max_depth = pl.max_depth;
-    return POLEE_OK;
+    return host_entry("polee_debug_ptt_plan", [&]() -> polee_status {
+        if (!node_parent_idxs || !node_js) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_debug_ptt_plan: null argument");
+        std::vector<int32_t> l, r, f;
+        std::string err = children_from_parents(node_parent_idxs, node_js, N, l, r, f);
+        PttPlan pl;
+        if (err.empty()) err = build_ptt_plan(l.data(), r.data(), f.data(), N, pl);
+        if (!err.empty()) return fail(nullptr, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
+        if (tour_code) std::copy(pl.tour_code.begin(), pl.tour_code.end(), tour_code);
+        if (tour_tgt) std::copy(pl.tour_tgt.begin(), pl.tour_tgt.end(), tour_tgt);
+        if (leaf_tid) std::copy(pl.leaf_tid.begin(), pl.leaf_tid.end(), leaf_tid);
+        if (lo) std::copy(pl.lo.begin(), pl.lo.end(), lo);
+        if (mid) std::copy(pl.mid.begin(), pl.mid.end(), mid);
+        if (hi1) std::copy(pl.hi1.begin(), pl.hi1.end(), hi1);
+        if (max_depth) *max_depth = pl.max_depth;
+        return POLEE_OK;
+    });
 }
 
 static polee_status debug_psell_build_impl(int64_t m, int64_t n, const void *colptr, int colptr_bytes,
@@ -142,51 +144,56 @@ static polee_status debug_psell_build_device_impl(polee_ctx *ctx, int64_t m, int
 polee_status polee_debug_psell_build(int64_t m, int64_t n, const void *colptr, int colptr_bytes, const uint32_t *rowval,
                                      const float *nzval, const int64_t *ks, polee_psell_debug **out)
 {
-    return guarded(nullptr, "polee_debug_psell_build", [&] { return debug_psell_build_impl(m, n, colptr, colptr_bytes, rowval, nzval, ks, out); });
+    return host_entry("polee_debug_psell_build", [&]() -> polee_status {
+        return debug_psell_build_impl(m, n, colptr, colptr_bytes, rowval, nzval, ks, out);
+    });
 }
 polee_status polee_debug_psell_build_device(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes,
                                             const uint32_t *rowval, const float *nzval, const int64_t *ks, int device_stages,
                                             polee_psell_debug **out)
 {
-    return guarded(ctx, "polee_debug_psell_build_device",
-                   [&] { return debug_psell_build_device_impl(ctx, m, n, colptr, colptr_bytes, rowval, nzval, ks, device_stages, out); });
+    return ctx_entry(ctx, "polee_debug_psell_build_device", [&]() -> polee_status {
+        return debug_psell_build_device_impl(ctx, m, n, colptr, colptr_bytes, rowval, nzval, ks, device_stages, out);
+    });
 }
 
 polee_status polee_debug_psell_view(const polee_psell_debug *p, polee_psell_view *v)
 {
-    if (!p || !v) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    const PsellHost &h = p->h;
-    v->m = h.m; v->n = h.n; v->nnz = h.nnz;
-    v->num_slices = h.num_slices; v->num_tiles = h.num_tiles; v->padded_nnz = h.padded_nnz;
-    v->num_empty_rows = h.empty_rows;
-    v->data_bytes = (int64_t)h.data.size(); v->dict_len = (int64_t)h.dict.size();
-    v->max_row_nnz = h.max_row; v->max_tile_cols = h.max_tile_cols;
-    v->data = h.data.data(); v->slice_off = h.slice_off.data(); v->tile_slice = h.tile_slice.data();
-    v->tile_dict = h.tile_dict.data(); v->dict = h.dict.data(); v->row_order = h.row_order.data();
-    v->slice_ks = h.slice_ks.empty() ? nullptr : h.slice_ks.data();
-    v->slice_flags = h.slice_flags.data();
-    v->num_tiles_a = h.num_tiles_a;
-    v->num_tiles_a1 = h.num_tiles_a1;
-    v->num_tiles_a1m = h.num_tiles_a1m;
-    v->num_tiles_a2 = h.num_tiles_a2;
-    v->num_tiles_s = h.num_tiles_s;
-    v->slice_w = h.slice_w.data();
-    for (int i = 0; i < 8; ++i) v->stream_rows[i] = v->stream_nnz[i] = v->stream_bytes[i] = 0;
-    v->csr_num_rows = (int64_t)h.csr_rows.size();
-    v->csr_rowptr = h.csr_rowptr.data();
-    v->csr_col = h.csr_col.data();
-    v->csr_val = h.csr_val.data();
-    v->csr_rows = h.csr_rows.data();
-    v->single_num_rows = (int64_t)h.single_rows.size();
-    v->single_rows = h.single_rows.data();
-    v->single_cnt = h.single_cnt.empty() ? nullptr : h.single_cnt.data();
-    v->single_logsum = h.single_logsum;
-    for (int i = 0; i < PSELL_NSTREAMS; ++i) {
-        v->stream_rows[i] = h.stream_rows[i];
-        v->stream_nnz[i] = h.stream_nnz[i];
-        v->stream_bytes[i] = h.stream_bytes[i];
-    }
-    return POLEE_OK;
+    return host_entry("polee_debug_psell_view", [&]() -> polee_status {
+        if (!p || !v) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_debug_psell_view: null argument");
+        const PsellHost &h = p->h;
+        v->m = h.m; v->n = h.n; v->nnz = h.nnz;
+        v->num_slices = h.num_slices; v->num_tiles = h.num_tiles; v->padded_nnz = h.padded_nnz;
+        v->num_empty_rows = h.empty_rows;
+        v->data_bytes = (int64_t)h.data.size(); v->dict_len = (int64_t)h.dict.size();
+        v->max_row_nnz = h.max_row; v->max_tile_cols = h.max_tile_cols;
+        v->data = h.data.data(); v->slice_off = h.slice_off.data(); v->tile_slice = h.tile_slice.data();
+        v->tile_dict = h.tile_dict.data(); v->dict = h.dict.data(); v->row_order = h.row_order.data();
+        v->slice_ks = h.slice_ks.empty() ? nullptr : h.slice_ks.data();
+        v->slice_flags = h.slice_flags.data();
+        v->num_tiles_a = h.num_tiles_a;
+        v->num_tiles_a1 = h.num_tiles_a1;
+        v->num_tiles_a1m = h.num_tiles_a1m;
+        v->num_tiles_a2 = h.num_tiles_a2;
+        v->num_tiles_s = h.num_tiles_s;
+        v->slice_w = h.slice_w.data();
+        for (int i = 0; i < 8; ++i) v->stream_rows[i] = v->stream_nnz[i] = v->stream_bytes[i] = 0;
+        v->csr_num_rows = (int64_t)h.csr_rows.size();
+        v->csr_rowptr = h.csr_rowptr.data();
+        v->csr_col = h.csr_col.data();
+        v->csr_val = h.csr_val.data();
+        v->csr_rows = h.csr_rows.data();
+        v->single_num_rows = (int64_t)h.single_rows.size();
+        v->single_rows = h.single_rows.data();
+        v->single_cnt = h.single_cnt.empty() ? nullptr : h.single_cnt.data();
+        v->single_logsum = h.single_logsum;
+        for (int i = 0; i < PSELL_NSTREAMS; ++i) {
+            v->stream_rows[i] = h.stream_rows[i];
+            v->stream_nnz[i] = h.stream_nnz[i];
+            v->stream_bytes[i] = h.stream_bytes[i];
+        }
+        return POLEE_OK;
+    });
 }
 
 void polee_debug_psell_free(polee_psell_debug *p) { delete p; }

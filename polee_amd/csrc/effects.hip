@@ -228,9 +228,7 @@ extern "C" {
 
 polee_status polee_effects_create(polee_ctx *ctx, int32_t n, int32_t G, const int32_t *gene_of, int32_t F, polee_effects **out)
 {
-    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_effects_create: null context");
-    return guarded(ctx, "polee_effects_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_effects_create", [&]() -> polee_status {
         if (!out || !gene_of || n < 1 || G < 1 || F < 1 || F > 65535)
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_effects_create: bad argument (n = %d, G = %d, F = %d; 1 <= F <= 65535)", n, G, F);
         // transcripts by gene: a counting sort, ascending transcript index inside a gene
@@ -279,10 +277,7 @@ polee_status polee_effects_run(polee_effects *fx, const float *qw_loc, const flo
                                const float *zw_or_null, int64_t zw_len, float *min_effect_sizes, float *mean_effect_sizes, float *prob_de,
                                float *aitchison_min, float *aitchison_mean, float *aitchison_prob_de, double *kernel_ms_or_null)
 {
-    if (!fx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_effects_run: null handle");
-    polee_ctx *ctx = fx->ctx;
-    return guarded(ctx, "polee_effects_run", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(fx, "polee_effects_run", [&](polee_ctx *ctx) -> polee_status {
         const size_t n = (size_t)fx->n, F = (size_t)fx->F, G = (size_t)fx->G;
         if (!qw_loc || !qw_scale || !qx_bias_loc || !qx_bias_scale || !min_effect_sizes || !mean_effect_sizes || !prob_de ||
             !aitchison_min || !aitchison_mean || !aitchison_prob_de)

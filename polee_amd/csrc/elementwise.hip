@@ -192,190 +192,199 @@ extern "C" {
 polee_status polee_logit_normal_transform(polee_ctx *ctx, const float *mu, const float *sigma, const float *zs,
                                           int64_t len, double *ys, double *ladj)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!mu || !sigma || !zs || !ys || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (len == 0) return POLEE_OK;
-    Scratch s;
-    POLEE_TRY(s.f[0].upload(ctx, mu, len));
-    POLEE_TRY(s.f[1].upload(ctx, sigma, len));
-    POLEE_TRY(s.f[2].upload(ctx, zs, len));
-    POLEE_TRY(s.d[0].alloc(ctx, len));
-    POLEE_TRY(s.d[1].alloc(ctx, 1));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(s.d[1].p, 0, sizeof(double), ctx->stream));
-    hipLaunchKernelGGL(logit_normal_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p, s.f[2].p,
-                       len, s.d[0].p, ladj ? s.d[1].p : nullptr);
-    POLEE_KERNEL_CHECK(ctx);
-    POLEE_TRY(s.d[0].download(ctx, ys, len));
-    if (ladj) POLEE_TRY(s.d[1].download(ctx, ladj, 1));
-    return POLEE_OK;
+    return ctx_entry(ctx, "polee_logit_normal_transform", [&]() -> polee_status {
+        if (!mu || !sigma || !zs || !ys || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_logit_normal_transform: bad argument");
+        if (len == 0) return POLEE_OK;
+        Scratch s;
+        POLEE_TRY(s.f[0].upload(ctx, mu, len));
+        POLEE_TRY(s.f[1].upload(ctx, sigma, len));
+        POLEE_TRY(s.f[2].upload(ctx, zs, len));
+        POLEE_TRY(s.d[0].alloc(ctx, len));
+        POLEE_TRY(s.d[1].alloc(ctx, 1));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(s.d[1].p, 0, sizeof(double), ctx->stream));
+        hipLaunchKernelGGL(logit_normal_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p, s.f[2].p,
+                           len, s.d[0].p, ladj ? s.d[1].p : nullptr);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(s.d[0].download(ctx, ys, len));
+        if (ladj) POLEE_TRY(s.d[1].download(ctx, ladj, 1));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_logit_normal_transform_gradients(polee_ctx *ctx, const float *zs, const double *ys,
                                                     const float *sigma, const float *y_grad, int64_t len,
                                                     float *z_grad_or_null, float *mu_grad, float *sigma_grad)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!zs || !ys || !sigma || !y_grad || !mu_grad || !sigma_grad || len < 0)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (len == 0) return POLEE_OK;
-    Scratch s;
-    POLEE_TRY(s.f[0].upload(ctx, zs, len));
-    POLEE_TRY(s.d[0].upload(ctx, ys, len));
-    POLEE_TRY(s.f[1].upload(ctx, sigma, len));
-    POLEE_TRY(s.f[2].upload(ctx, y_grad, len));
-    POLEE_TRY(s.f[3].upload(ctx, mu_grad, len));
-    POLEE_TRY(s.f[4].upload(ctx, sigma_grad, len));
-    if (z_grad_or_null) POLEE_TRY(s.f[5].upload(ctx, z_grad_or_null, len));
-    hipLaunchKernelGGL(logit_normal_grad_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.d[0].p,
-                       s.f[1].p, s.f[2].p, len, z_grad_or_null ? s.f[5].p : nullptr, s.f[3].p, s.f[4].p);
-    POLEE_KERNEL_CHECK(ctx);
-    POLEE_TRY(s.f[3].download(ctx, mu_grad, len));
-    POLEE_TRY(s.f[4].download(ctx, sigma_grad, len));
-    if (z_grad_or_null) POLEE_TRY(s.f[5].download(ctx, z_grad_or_null, len));
-    return POLEE_OK;
+    return ctx_entry(ctx, "polee_logit_normal_transform_gradients", [&]() -> polee_status {
+        if (!zs || !ys || !sigma || !y_grad || !mu_grad || !sigma_grad || len < 0)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_logit_normal_transform_gradients: bad argument");
+        if (len == 0) return POLEE_OK;
+        Scratch s;
+        POLEE_TRY(s.f[0].upload(ctx, zs, len));
+        POLEE_TRY(s.d[0].upload(ctx, ys, len));
+        POLEE_TRY(s.f[1].upload(ctx, sigma, len));
+        POLEE_TRY(s.f[2].upload(ctx, y_grad, len));
+        POLEE_TRY(s.f[3].upload(ctx, mu_grad, len));
+        POLEE_TRY(s.f[4].upload(ctx, sigma_grad, len));
+        if (z_grad_or_null) POLEE_TRY(s.f[5].upload(ctx, z_grad_or_null, len));
+        hipLaunchKernelGGL(logit_normal_grad_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.d[0].p,
+                           s.f[1].p, s.f[2].p, len, z_grad_or_null ? s.f[5].p : nullptr, s.f[3].p, s.f[4].p);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(s.f[3].download(ctx, mu_grad, len));
+        POLEE_TRY(s.f[4].download(ctx, sigma_grad, len));
+        if (z_grad_or_null) POLEE_TRY(s.f[5].download(ctx, z_grad_or_null, len));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_sinh_asinh_transform(polee_ctx *ctx, const float *alpha, const float *zs0, int64_t len, float *zs,
                                         double *ladj)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!alpha || !zs0 || !zs || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (len == 0) return POLEE_OK;
-    Scratch s;
-    POLEE_TRY(s.f[0].upload(ctx, alpha, len));
-    POLEE_TRY(s.f[1].upload(ctx, zs0, len));
-    POLEE_TRY(s.f[2].alloc(ctx, len));
-    POLEE_TRY(s.d[1].alloc(ctx, 1));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(s.d[1].p, 0, sizeof(double), ctx->stream));
-    hipLaunchKernelGGL(sinh_asinh_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p, len,
-                       s.f[2].p, ladj ? s.d[1].p : nullptr);
-    POLEE_KERNEL_CHECK(ctx);
-    POLEE_TRY(s.f[2].download(ctx, zs, len));
-    if (ladj) POLEE_TRY(s.d[1].download(ctx, ladj, 1));
-    return POLEE_OK;
+    return ctx_entry(ctx, "polee_sinh_asinh_transform", [&]() -> polee_status {
+        if (!alpha || !zs0 || !zs || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sinh_asinh_transform: bad argument");
+        if (len == 0) return POLEE_OK;
+        Scratch s;
+        POLEE_TRY(s.f[0].upload(ctx, alpha, len));
+        POLEE_TRY(s.f[1].upload(ctx, zs0, len));
+        POLEE_TRY(s.f[2].alloc(ctx, len));
+        POLEE_TRY(s.d[1].alloc(ctx, 1));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(s.d[1].p, 0, sizeof(double), ctx->stream));
+        hipLaunchKernelGGL(sinh_asinh_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p, len,
+                           s.f[2].p, ladj ? s.d[1].p : nullptr);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(s.f[2].download(ctx, zs, len));
+        if (ladj) POLEE_TRY(s.d[1].download(ctx, ladj, 1));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_sinh_asinh_transform_gradients(polee_ctx *ctx, const float *zs0, const float *alpha,
                                                   const float *z_grad, int64_t len, float *alpha_grad)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!zs0 || !alpha || !z_grad || !alpha_grad || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (len == 0) return POLEE_OK;
-    Scratch s;
-    POLEE_TRY(s.f[0].upload(ctx, zs0, len));
-    POLEE_TRY(s.f[1].upload(ctx, alpha, len));
-    POLEE_TRY(s.f[2].upload(ctx, z_grad, len));
-    POLEE_TRY(s.f[3].upload(ctx, alpha_grad, len));
-    hipLaunchKernelGGL(sinh_asinh_grad_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p,
-                       s.f[2].p, len, s.f[3].p);
-    POLEE_KERNEL_CHECK(ctx);
-    return s.f[3].download(ctx, alpha_grad, len);
+    return ctx_entry(ctx, "polee_sinh_asinh_transform_gradients", [&]() -> polee_status {
+        if (!zs0 || !alpha || !z_grad || !alpha_grad || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sinh_asinh_transform_gradients: bad argument");
+        if (len == 0) return POLEE_OK;
+        Scratch s;
+        POLEE_TRY(s.f[0].upload(ctx, zs0, len));
+        POLEE_TRY(s.f[1].upload(ctx, alpha, len));
+        POLEE_TRY(s.f[2].upload(ctx, z_grad, len));
+        POLEE_TRY(s.f[3].upload(ctx, alpha_grad, len));
+        hipLaunchKernelGGL(sinh_asinh_grad_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p,
+                           s.f[2].p, len, s.f[3].p);
+        POLEE_KERNEL_CHECK(ctx);
+        return s.f[3].download(ctx, alpha_grad, len);
+    });
 }
 
 polee_status polee_kumaraswamy_transform(polee_ctx *ctx, const float *as, const float *bs, const float *zs, int64_t len,
                                          double *ys, double *ladj)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!as || !bs || !zs || !ys || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (len == 0) return POLEE_OK;
-    Scratch s;
-    POLEE_TRY(s.f[0].upload(ctx, as, len));
-    POLEE_TRY(s.f[1].upload(ctx, bs, len));
-    POLEE_TRY(s.f[2].upload(ctx, zs, len));
-    POLEE_TRY(s.d[0].alloc(ctx, len));
-    POLEE_TRY(s.d[1].alloc(ctx, 1));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(s.d[1].p, 0, sizeof(double), ctx->stream));
-    hipLaunchKernelGGL(kumaraswamy_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p, s.f[2].p,
-                       len, s.d[0].p, ladj ? s.d[1].p : nullptr);
-    POLEE_KERNEL_CHECK(ctx);
-    POLEE_TRY(s.d[0].download(ctx, ys, len));
-    if (ladj) {
-        POLEE_TRY(s.d[1].download(ctx, ladj, 1));
-        if (!std::isfinite(*ladj)) return fail(ctx, POLEE_ERR_NONFINITE, "kumaraswamy ladj is not finite (kumaraswamy.jl:49)");
-    }
-    return POLEE_OK;
+    return ctx_entry(ctx, "polee_kumaraswamy_transform", [&]() -> polee_status {
+        if (!as || !bs || !zs || !ys || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_kumaraswamy_transform: bad argument");
+        if (len == 0) return POLEE_OK;
+        Scratch s;
+        POLEE_TRY(s.f[0].upload(ctx, as, len));
+        POLEE_TRY(s.f[1].upload(ctx, bs, len));
+        POLEE_TRY(s.f[2].upload(ctx, zs, len));
+        POLEE_TRY(s.d[0].alloc(ctx, len));
+        POLEE_TRY(s.d[1].alloc(ctx, 1));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(s.d[1].p, 0, sizeof(double), ctx->stream));
+        hipLaunchKernelGGL(kumaraswamy_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p, s.f[2].p,
+                           len, s.d[0].p, ladj ? s.d[1].p : nullptr);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(s.d[0].download(ctx, ys, len));
+        if (ladj) {
+            POLEE_TRY(s.d[1].download(ctx, ladj, 1));
+            if (!std::isfinite(*ladj)) return fail(ctx, POLEE_ERR_NONFINITE, "kumaraswamy ladj is not finite (kumaraswamy.jl:49)");
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_kumaraswamy_transform_gradients(polee_ctx *ctx, const float *zs, const float *as, const float *bs,
                                                    const float *y_grad, int64_t len, float *a_grad, float *b_grad)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!zs || !as || !bs || !y_grad || !a_grad || !b_grad || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (len == 0) return POLEE_OK;
-    Scratch s;
-    POLEE_TRY(s.f[0].upload(ctx, zs, len));
-    POLEE_TRY(s.f[1].upload(ctx, as, len));
-    POLEE_TRY(s.f[2].upload(ctx, bs, len));
-    POLEE_TRY(s.f[3].upload(ctx, y_grad, len));
-    POLEE_TRY(s.f[4].upload(ctx, a_grad, len));
-    POLEE_TRY(s.f[5].upload(ctx, b_grad, len));
-    hipLaunchKernelGGL(kumaraswamy_grad_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p,
-                       s.f[2].p, s.f[3].p, len, s.f[4].p, s.f[5].p);
-    POLEE_KERNEL_CHECK(ctx);
-    POLEE_TRY(s.f[4].download(ctx, a_grad, len));
-    return s.f[5].download(ctx, b_grad, len);
+    return ctx_entry(ctx, "polee_kumaraswamy_transform_gradients", [&]() -> polee_status {
+        if (!zs || !as || !bs || !y_grad || !a_grad || !b_grad || len < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_kumaraswamy_transform_gradients: bad argument");
+        if (len == 0) return POLEE_OK;
+        Scratch s;
+        POLEE_TRY(s.f[0].upload(ctx, zs, len));
+        POLEE_TRY(s.f[1].upload(ctx, as, len));
+        POLEE_TRY(s.f[2].upload(ctx, bs, len));
+        POLEE_TRY(s.f[3].upload(ctx, y_grad, len));
+        POLEE_TRY(s.f[4].upload(ctx, a_grad, len));
+        POLEE_TRY(s.f[5].upload(ctx, b_grad, len));
+        hipLaunchKernelGGL(kumaraswamy_grad_kernel, dim3(blocks(len)), dim3(256), 0, ctx->stream, s.f[0].p, s.f[1].p,
+                           s.f[2].p, s.f[3].p, len, s.f[4].p, s.f[5].p);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(s.f[4].download(ctx, a_grad, len));
+        return s.f[5].download(ctx, b_grad, len);
+    });
 }
 
 polee_status polee_gene_noninformative_prior(polee_ctx *ctx, const float *efflens, const float *xls, const float *xs,
                                              int32_t K, int64_t n, const int32_t *gene_of, double *x_grad)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!efflens || !xls || !xs || !gene_of || !x_grad || K < 1 || n < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    int32_t num_genes = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (gene_of[i] < -1) return fail(ctx, POLEE_ERR_BAD_ARG, "gene_of[%lld] = %d", (long long)i, gene_of[i]);
-        num_genes = std::max(num_genes, gene_of[i] + 1);
-    }
-    if (num_genes == 0) return POLEE_OK;  // no gene information: nothing to add (likelihood-approximation.jl:489-492)
-    const size_t tot = (size_t)n * K;
-    DevBuf<float> d_l, d_xls, d_xs;
-    DevBuf<int32_t> d_gene;
-    DevBuf<int> d_k;
-    DevBuf<double> d_c, d_sums, d_g;
-    POLEE_TRY(d_l.upload(ctx, efflens, n));
-    POLEE_TRY(d_xls.upload(ctx, xls, tot));
-    POLEE_TRY(d_xs.upload(ctx, xs, tot));
-    POLEE_TRY(d_gene.upload(ctx, gene_of, n));
-    POLEE_TRY(d_g.upload(ctx, x_grad, tot));
-    POLEE_TRY(d_c.alloc(ctx, (size_t)num_genes * K));
-    POLEE_TRY(d_k.alloc(ctx, num_genes));
-    POLEE_TRY(d_sums.alloc(ctx, 2 * (size_t)K));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(d_c.p, 0, sizeof(double) * num_genes * K, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(d_k.p, 0, sizeof(int) * num_genes, ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(d_sums.p, 0, sizeof(double) * 2 * K, ctx->stream));
-    const dim3 grid(blocks(n), (unsigned)K);
-    hipLaunchKernelGGL(gene_prior_sums_kernel, grid, dim3(256), 0, ctx->stream, d_l.p, d_xls.p, d_xs.p, d_gene.p, n, K,
-                       d_c.p, d_k.p, d_sums.p);
-    hipLaunchKernelGGL(gene_prior_offdiag_kernel, grid, dim3(256), 0, ctx->stream, d_xls.p, d_gene.p, n, K, d_c.p, d_k.p,
-                       d_sums.p + K);
-    hipLaunchKernelGGL(gene_prior_apply_kernel, grid, dim3(256), 0, ctx->stream, d_l.p, d_gene.p, n, K, d_c.p, d_k.p,
-                       d_sums.p, d_sums.p + K, d_g.p);
-    POLEE_KERNEL_CHECK(ctx);
-    return d_g.download(ctx, x_grad, tot);
+    return ctx_entry(ctx, "polee_gene_noninformative_prior", [&]() -> polee_status {
+        if (!efflens || !xls || !xs || !gene_of || !x_grad || K < 1 || n < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gene_noninformative_prior: bad argument");
+        int32_t num_genes = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            if (gene_of[i] < -1) return fail(ctx, POLEE_ERR_BAD_ARG, "gene_of[%lld] = %d", (long long)i, gene_of[i]);
+            num_genes = std::max(num_genes, gene_of[i] + 1);
+        }
+        if (num_genes == 0) return POLEE_OK;  // no gene information: nothing to add (likelihood-approximation.jl:489-492)
+        const size_t tot = (size_t)n * K;
+        DevBuf<float> d_l, d_xls, d_xs;
+        DevBuf<int32_t> d_gene;
+        DevBuf<int> d_k;
+        DevBuf<double> d_c, d_sums, d_g;
+        POLEE_TRY(d_l.upload(ctx, efflens, n));
+        POLEE_TRY(d_xls.upload(ctx, xls, tot));
+        POLEE_TRY(d_xs.upload(ctx, xs, tot));
+        POLEE_TRY(d_gene.upload(ctx, gene_of, n));
+        POLEE_TRY(d_g.upload(ctx, x_grad, tot));
+        POLEE_TRY(d_c.alloc(ctx, (size_t)num_genes * K));
+        POLEE_TRY(d_k.alloc(ctx, num_genes));
+        POLEE_TRY(d_sums.alloc(ctx, 2 * (size_t)K));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(d_c.p, 0, sizeof(double) * num_genes * K, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(d_k.p, 0, sizeof(int) * num_genes, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(d_sums.p, 0, sizeof(double) * 2 * K, ctx->stream));
+        const dim3 grid(blocks(n), (unsigned)K);
+        hipLaunchKernelGGL(gene_prior_sums_kernel, grid, dim3(256), 0, ctx->stream, d_l.p, d_xls.p, d_xs.p, d_gene.p, n, K,
+                           d_c.p, d_k.p, d_sums.p);
+        hipLaunchKernelGGL(gene_prior_offdiag_kernel, grid, dim3(256), 0, ctx->stream, d_xls.p, d_gene.p, n, K, d_c.p, d_k.p,
+                           d_sums.p + K);
+        hipLaunchKernelGGL(gene_prior_apply_kernel, grid, dim3(256), 0, ctx->stream, d_l.p, d_gene.p, n, K, d_c.p, d_k.p,
+                           d_sums.p, d_sums.p + K, d_g.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return d_g.download(ctx, x_grad, tot);
+    });
 }
 
 // test hook (include/polee_hip_debug.h): the forward kernel's double-precision exp, element-wise
 polee_status polee_debug_fast_exp(polee_ctx *ctx, const double *x, int64_t count, double *out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!x || !out || count < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    DevBuf<double> d;
-    POLEE_TRY(d.upload(ctx, x, (size_t)count));
-    hipLaunchKernelGGL(fast_exp_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, d.p, count);
-    POLEE_KERNEL_CHECK(ctx);
-    return d.download(ctx, out, (size_t)count);
+    return ctx_entry(ctx, "polee_debug_fast_exp", [&]() -> polee_status {
+        if (!x || !out || count < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_fast_exp: bad argument");
+        DevBuf<double> d;
+        POLEE_TRY(d.upload(ctx, x, (size_t)count));
+        hipLaunchKernelGGL(fast_exp_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, d.p, count);
+        POLEE_KERNEL_CHECK(ctx);
+        return d.download(ctx, out, (size_t)count);
+    });
 }
 
 // test hook (include/polee_hip_debug.h): the tree kernels' double-precision log, element-wise
 polee_status polee_debug_fast_log(polee_ctx *ctx, const double *x, int64_t count, double *out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!x || !out || count < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    DevBuf<double> d;
-    POLEE_TRY(d.upload(ctx, x, (size_t)count));
-    hipLaunchKernelGGL(fast_log_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, d.p, count);
-    POLEE_KERNEL_CHECK(ctx);
-    return d.download(ctx, out, (size_t)count);
+    return ctx_entry(ctx, "polee_debug_fast_log", [&]() -> polee_status {
+        if (!x || !out || count < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_fast_log: bad argument");
+        DevBuf<double> d;
+        POLEE_TRY(d.upload(ctx, x, (size_t)count));
+        hipLaunchKernelGGL(fast_log_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, d.p, count);
+        POLEE_KERNEL_CHECK(ctx);
+        return d.download(ctx, out, (size_t)count);
+    });
 }
 
 }  // extern "C"

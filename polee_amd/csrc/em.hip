@@ -477,10 +477,7 @@ extern "C" {
 
 polee_status polee_em_create(polee_loglik *ll, const float *y0, polee_em **out)
 {
-    if (!ll) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_em_create: null likelihood handle");
-    polee_ctx *ctx = ll->ctx;
-    return guarded(ctx, "polee_em_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ll, "polee_em_create", [&](polee_ctx *ctx) -> polee_status {
         if (!out) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_create: null output pointer");
         polee_em *E = new (std::nothrow) polee_em();
         if (!E) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
@@ -524,20 +521,14 @@ void polee_em_destroy(polee_em *E)
 
 polee_status polee_em_reset(polee_em *E, const float *y0)
 {
-    if (!E) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_em_reset: null handle");
-    polee_ctx *ctx = E->ctx;
-    return guarded(ctx, "polee_em_reset", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(E, "polee_em_reset", [&](polee_ctx *ctx) -> polee_status {
         return em_set_start(E, y0, "polee_em_reset");
     });
 }
 
 polee_status polee_em_run(polee_em *E, int32_t max_iters, double tol, int32_t check_every)
 {
-    if (!E) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_em_run: null handle");
-    polee_ctx *ctx = E->ctx;
-    return guarded(ctx, "polee_em_run", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(E, "polee_em_run", [&](polee_ctx *ctx) -> polee_status {
         if (max_iters < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_run: max_iters < 0");
         if (check_every < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_run: check_every < 1");
         if (std::isnan(tol)) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_run: tol is NaN");
@@ -560,29 +551,25 @@ polee_status polee_em_run(polee_em *E, int32_t max_iters, double tol, int32_t ch
 
 polee_status polee_em_sync(polee_em *E)
 {
-    if (!E) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_em_sync: null handle");
-    POLEE_TRY(use_device(E->ctx));
-    POLEE_TRY(em_read_state(E));
-    if (E->h.bad) return em_nonfinite(E);
-    return POLEE_OK;
+    return entry(E, "polee_em_sync", [&](polee_ctx *ctx) -> polee_status {
+        POLEE_TRY(em_read_state(E));
+        if (E->h.bad) return em_nonfinite(E);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_em_get_mixture(polee_em *E, float *y)
 {
-    if (!E || !y) return fail(E ? E->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_em_get_mixture: null argument");
-    polee_ctx *ctx = E->ctx;
-    return guarded(ctx, "polee_em_get_mixture", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(E, "polee_em_get_mixture", [&](polee_ctx *ctx) -> polee_status {
+        if (!y) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_get_mixture: null argument");
         return em_normalised(E, nullptr, 1.0, y);
     });
 }
 
 polee_status polee_em_get_tpm(polee_em *E, const float *efflens, float *tpm)
 {
-    if (!E || !tpm) return fail(E ? E->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_em_get_tpm: null argument");
-    polee_ctx *ctx = E->ctx;
-    return guarded(ctx, "polee_em_get_tpm", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(E, "polee_em_get_tpm", [&](polee_ctx *ctx) -> polee_status {
+        if (!tpm) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_get_tpm: null argument");
         DevBuf<float> d_l;
         if (efflens) {
             for (int64_t j = 0; j < E->n; ++j)
@@ -597,21 +584,18 @@ polee_status polee_em_get_tpm(polee_em *E, const float *efflens, float *tpm)
 
 polee_status polee_em_get_trace(polee_em *E, double *lp, int64_t capacity, int64_t *count)
 {
-    if (!E) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_em_get_trace: null handle");
-    polee_ctx *ctx = E->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (capacity < 0 || (capacity > 0 && !lp)) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_get_trace: capacity < 0 or a null buffer");
-    POLEE_TRY(em_read_state(E));
-    if (count) *count = E->h.traced;
-    return E->trace.download(ctx, lp, (size_t)std::min<int64_t>(capacity, E->h.traced));
+    return entry(E, "polee_em_get_trace", [&](polee_ctx *ctx) -> polee_status {
+        if (capacity < 0 || (capacity > 0 && !lp)) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_get_trace: capacity < 0 or a null buffer");
+        POLEE_TRY(em_read_state(E));
+        if (count) *count = E->h.traced;
+        return E->trace.download(ctx, lp, (size_t)std::min<int64_t>(capacity, E->h.traced));
+    });
 }
 
 polee_status polee_em_get_info(polee_em *E, int compute_kkt, polee_em_info *info)
 {
-    if (!E || !info) return fail(E ? E->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_em_get_info: null argument");
-    polee_ctx *ctx = E->ctx;
-    return guarded(ctx, "polee_em_get_info", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(E, "polee_em_get_info", [&](polee_ctx *ctx) -> polee_status {
+        if (!info) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_em_get_info: null argument");
         if (compute_kkt) POLEE_TRY(em_residual64(E));
         POLEE_TRY(em_read_state(E));
         info->n = E->n;

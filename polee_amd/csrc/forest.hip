@@ -765,9 +765,7 @@ extern "C" {
 
 polee_status polee_forest_create(polee_ctx *ctx, int32_t n, int32_t k, const polee_forest_opts *opts, polee_forest **out)
 {
-    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_create: null context");
-    return guarded(ctx, "polee_forest_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_forest_create", [&]() -> polee_status {
         if (!out || n < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_create: bad argument");
         if (k < 2 || k > FO_MAX_K) return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_forest_create: %d classes; the kernels are built for 2..16", k);
         polee_forest_opts o;
@@ -834,27 +832,29 @@ polee_status polee_forest_fit(polee_forest *f, polee_approx *ap, const int32_t *
 
 polee_status polee_forest_node_count(polee_forest *f, int32_t *ntrees, int64_t *nnodes)
 {
-    if (!f) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_node_count: null handle");
-    if (!ntrees || !nnodes) return fail(f->ctx, POLEE_ERR_BAD_ARG, "polee_forest_node_count: null argument");
-    *ntrees = f->ntrees;
-    *nnodes = f->ntrees ? f->tree_off[(size_t)f->ntrees] : 0;
-    return POLEE_OK;
+    return entry(f, "polee_forest_node_count", [&](polee_ctx *ctx) -> polee_status {
+        if (!ntrees || !nnodes) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_node_count: null argument");
+        *ntrees = f->ntrees;
+        *nnodes = f->ntrees ? f->tree_off[(size_t)f->ntrees] : 0;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_forest_get_nodes(polee_forest *f, int64_t *tree_off, int32_t *feature, double *threshold, int32_t *left, int32_t *right,
                                     int32_t *label)
 {
-    if (!f) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_get_nodes: null handle");
-    if (!tree_off || !feature || !threshold || !left || !right || !label)
-        return fail(f->ctx, POLEE_ERR_BAD_ARG, "polee_forest_get_nodes: null argument");
-    if (!f->ntrees) return fail(f->ctx, POLEE_ERR_BAD_ARG, "polee_forest_get_nodes: no forest yet");
-    std::copy(f->tree_off.begin(), f->tree_off.end(), tree_off);
-    std::copy(f->feature.begin(), f->feature.end(), feature);
-    std::copy(f->threshold.begin(), f->threshold.end(), threshold);
-    std::copy(f->left.begin(), f->left.end(), left);
-    std::copy(f->right.begin(), f->right.end(), right);
-    std::copy(f->label.begin(), f->label.end(), label);
-    return POLEE_OK;
+    return entry(f, "polee_forest_get_nodes", [&](polee_ctx *ctx) -> polee_status {
+        if (!tree_off || !feature || !threshold || !left || !right || !label)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_get_nodes: null argument");
+        if (!f->ntrees) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_get_nodes: no forest yet");
+        std::copy(f->tree_off.begin(), f->tree_off.end(), tree_off);
+        std::copy(f->feature.begin(), f->feature.end(), feature);
+        std::copy(f->threshold.begin(), f->threshold.end(), threshold);
+        std::copy(f->left.begin(), f->left.end(), left);
+        std::copy(f->right.begin(), f->right.end(), right);
+        std::copy(f->label.begin(), f->label.end(), label);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_forest_set_nodes(polee_forest *f, int32_t ntrees, const int64_t *tree_off, const int32_t *feature,
@@ -911,10 +911,7 @@ polee_status polee_forest_predict(polee_forest *f, polee_approx *ap, int32_t ndr
 
 polee_status polee_forest_log_draws(polee_approx *ap, int32_t ndraws, uint64_t seed, const float *z0, float *out)
 {
-    if (!ap) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_log_draws: null approximation handle");
-    polee_ctx *ctx = approx_ctx(ap);
-    return guarded(ctx, "polee_forest_log_draws", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(ap, "polee_forest_log_draws", [&](polee_ctx *ctx) -> polee_status {
         int32_t S = 0, n = 0;
         approx_dims(ap, &S, &n);
         if (!out || ndraws < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_forest_log_draws: bad argument");

@@ -150,7 +150,7 @@ polee_status polee_forest_build_host(const float *x, const int32_t *labels, int3
                                      const polee_forest_opts *opts, uint64_t seed, int64_t capacity, int64_t *nnodes, int64_t *tree_off,
                                      int32_t *feature, double *threshold, int32_t *left, int32_t *right, int32_t *label)
 {
-    return guarded(nullptr, "polee_forest_build_host", [&]() -> polee_status {
+    return host_entry("polee_forest_build_host", [&]() -> polee_status {
         if (!x || !labels || !nnodes || N < 1) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_build_host: bad argument");
         polee_forest_opts o;
         polee_forest_default_opts(&o);
@@ -203,7 +203,7 @@ polee_status polee_forest_votes_host(int32_t n, int32_t k, int32_t ntrees, const
                                      const double *threshold, const int32_t *left, const int32_t *right, const int32_t *label,
                                      const float *x, int32_t R, int32_t *votes)
 {
-    return guarded(nullptr, "polee_forest_votes_host", [&]() -> polee_status {
+    return host_entry("polee_forest_votes_host", [&]() -> polee_status {
         if (!tree_off || !feature || !threshold || !left || !right || !label || !x || !votes || n < 1 || k < 1 || ntrees < 1 || R < 1)
             return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_forest_votes_host: bad argument");
         int32_t bt = 0;

@@ -512,8 +512,7 @@ extern "C" {
 polee_status polee_gibbs_create(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes, const uint32_t *rowval,
                                 const float *nzval, const float *efflens, int32_t num_chains, uint64_t seed, polee_gibbs **out)
 {
-    return guarded(ctx, "polee_gibbs_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_gibbs_create", [&]() -> polee_status {
         if (!colptr) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_create: bad argument");
         POLEE_TRY(gb_check_create_args(ctx, m, n, efflens, num_chains, out));
         PsellDevCSR X;
@@ -527,8 +526,7 @@ polee_status polee_gibbs_create(polee_ctx *ctx, int64_t m, int64_t n, const void
 polee_status polee_gibbs_create_from_xt(polee_ctx *ctx, int64_t m, int64_t n, const uint64_t *tcolptr, const uint32_t *trowval,
                                         const float *tnzval, const float *efflens, int32_t num_chains, uint64_t seed, polee_gibbs **out)
 {
-    return guarded(ctx, "polee_gibbs_create_from_xt", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_gibbs_create_from_xt", [&]() -> polee_status {
         if (!tcolptr) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_create_from_xt: bad argument");
         POLEE_TRY(gb_check_create_args(ctx, m, n, efflens, num_chains, out));
         if (tcolptr[0] != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_create_from_xt: tcolptr[0] must be 1 (1-based)");
@@ -554,10 +552,7 @@ void polee_gibbs_destroy(polee_gibbs *G)
 
 polee_status polee_gibbs_set_state(polee_gibbs *G, const float *g0)
 {
-    if (!G) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_set_state: null handle");
-    polee_ctx *ctx = G->ctx;
-    return guarded(ctx, "polee_gibbs_set_state", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(G, "polee_gibbs_set_state", [&](polee_ctx *ctx) -> polee_status {
         if (!g0) {
             POLEE_TRY(gb_init_state(G));
             GB_HIP(hipStreamSynchronize(ctx->stream));
@@ -579,10 +574,7 @@ polee_status polee_gibbs_set_state(polee_gibbs *G, const float *g0)
 
 polee_status polee_gibbs_reserve(polee_gibbs *G, int32_t draws_per_chain)
 {
-    if (!G) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_reserve: null handle");
-    polee_ctx *ctx = G->ctx;
-    return guarded(ctx, "polee_gibbs_reserve", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(G, "polee_gibbs_reserve", [&](polee_ctx *ctx) -> polee_status {
         if (draws_per_chain < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_reserve: draws_per_chain < 0");
         GB_HIP(hipStreamSynchronize(ctx->stream));
         G->store.release();
@@ -597,10 +589,7 @@ polee_status polee_gibbs_reserve(polee_gibbs *G, int32_t draws_per_chain)
 
 polee_status polee_gibbs_run(polee_gibbs *G, int32_t nsweeps, int32_t stride)
 {
-    if (!G) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_run: null handle");
-    polee_ctx *ctx = G->ctx;
-    return guarded(ctx, "polee_gibbs_run", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(G, "polee_gibbs_run", [&](polee_ctx *ctx) -> polee_status {
         if (nsweeps < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_run: nsweeps < 0");
         if (stride < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_run: stride < 0 (0 = burn-in, nothing stored)");
         if (stride == 0 || stride != G->phase_stride) G->phase = 0;
@@ -641,46 +630,44 @@ polee_status polee_gibbs_run(polee_gibbs *G, int32_t nsweeps, int32_t stride)
 
 polee_status polee_gibbs_sync(polee_gibbs *G)
 {
-    if (!G) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_sync: null handle");
-    polee_ctx *ctx = G->ctx;
-    POLEE_TRY(use_device(ctx));
-    uint32_t bad = 0;
-    GB_HIP(hipMemcpyAsync(&bad, G->bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GB_HIP(hipStreamSynchronize(ctx->stream));
-    if (bad) return fail(ctx, POLEE_ERR_NONFINITE, "polee_gibbs: a mixture draw was not finite");
-    return POLEE_OK;
+    return entry(G, "polee_gibbs_sync", [&](polee_ctx *ctx) -> polee_status {
+        uint32_t bad = 0;
+        GB_HIP(hipMemcpyAsync(&bad, G->bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        GB_HIP(hipStreamSynchronize(ctx->stream));
+        if (bad) return fail(ctx, POLEE_ERR_NONFINITE, "polee_gibbs: a mixture draw was not finite");
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_gibbs_num_stored(const polee_gibbs *G, int32_t *draws_per_chain)
 {
-    if (!G || !draws_per_chain) return fail(G ? G->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_num_stored: null argument");
-    *draws_per_chain = G->stored;
-    return POLEE_OK;
+    return entry(G, "polee_gibbs_num_stored", [&](polee_ctx *ctx) -> polee_status {
+        if (!draws_per_chain) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_num_stored: null argument");
+        *draws_per_chain = G->stored;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_gibbs_get_draws(polee_gibbs *G, int32_t first, int32_t count, float *out)
 {
-    if (!G) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_get_draws: null handle");
-    polee_ctx *ctx = G->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (first < 0 || count < 0 || first + count > G->stored || (count > 0 && !out))
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_get_draws: draws [%d, %d) outside the %d stored", (int)first, (int)(first + count),
-                    (int)G->stored);
-    POLEE_TRY(polee_gibbs_sync(G));
-    if (count == 0) return POLEE_OK;
-    const size_t row = (size_t)count * G->n * sizeof(float);
-    GB_HIP(hipMemcpy2DAsync(out, row, G->store.p + (size_t)first * G->n, (size_t)G->cap * G->n * sizeof(float), row, (size_t)G->C,
-                            hipMemcpyDeviceToHost, ctx->stream));
-    GB_HIP(hipStreamSynchronize(ctx->stream));
-    return POLEE_OK;
+    return entry(G, "polee_gibbs_get_draws", [&](polee_ctx *ctx) -> polee_status {
+        if (first < 0 || count < 0 || first + count > G->stored || (count > 0 && !out))
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_get_draws: draws [%d, %d) outside the %d stored", (int)first, (int)(first + count),
+                        (int)G->stored);
+        POLEE_TRY(polee_gibbs_sync(G));
+        if (count == 0) return POLEE_OK;
+        const size_t row = (size_t)count * G->n * sizeof(float);
+        GB_HIP(hipMemcpy2DAsync(out, row, G->store.p + (size_t)first * G->n, (size_t)G->cap * G->n * sizeof(float), row, (size_t)G->C,
+                                hipMemcpyDeviceToHost, ctx->stream));
+        GB_HIP(hipStreamSynchronize(ctx->stream));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_gibbs_get_counts(polee_gibbs *G, uint32_t *counts)
 {
-    if (!G || !counts) return fail(G ? G->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_get_counts: null argument");
-    polee_ctx *ctx = G->ctx;
-    return guarded(ctx, "polee_gibbs_get_counts", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(G, "polee_gibbs_get_counts", [&](polee_ctx *ctx) -> polee_status {
+        if (!counts) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_get_counts: null argument");
         const int64_t nC = G->n * G->C;
         DevBuf<uint32_t> tmp;
         POLEE_TRY(tmp.alloc(ctx, (size_t)nC));
@@ -693,10 +680,8 @@ polee_status polee_gibbs_get_counts(polee_gibbs *G, uint32_t *counts)
 
 polee_status polee_gibbs_rhat(polee_gibbs *G, float *rhat)
 {
-    if (!G || !rhat) return fail(G ? G->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_rhat: null argument");
-    polee_ctx *ctx = G->ctx;
-    return guarded(ctx, "polee_gibbs_rhat", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(G, "polee_gibbs_rhat", [&](polee_ctx *ctx) -> polee_status {
+        if (!rhat) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_rhat: null argument");
         if (G->stored < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_rhat: no stored draws");
         DevBuf<float> tmp;
         POLEE_TRY(tmp.alloc(ctx, (size_t)G->n));
@@ -708,27 +693,27 @@ polee_status polee_gibbs_rhat(polee_gibbs *G, float *rhat)
 
 polee_status polee_gibbs_get_info(const polee_gibbs *G, polee_gibbs_info *info)
 {
-    if (!G || !info) return fail(G ? G->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_gibbs_get_info: null argument");
-    info->m = G->m;
-    info->n = G->n;
-    info->nnz = G->nnz;
-    info->num_chains = G->C;
-    info->num_multi_rows = G->M;
-    info->num_single_rows = G->num_single;
-    info->num_empty_rows = G->num_empty;
-    info->multi_nnz = G->M > 0 ? (int64_t)G->col.n : 0;
-    info->num_tiles = G->num_tiles;
-    info->rows_per_tile = G->rows_per_tile;
-    info->sweeps_done = (int64_t)G->sweep;
-    return POLEE_OK;
+    return entry(G, "polee_gibbs_get_info", [&](polee_ctx *ctx) -> polee_status {
+        if (!info) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_gibbs_get_info: null argument");
+        info->m = G->m;
+        info->n = G->n;
+        info->nnz = G->nnz;
+        info->num_chains = G->C;
+        info->num_multi_rows = G->M;
+        info->num_single_rows = G->num_single;
+        info->num_empty_rows = G->num_empty;
+        info->multi_nnz = G->M > 0 ? (int64_t)G->col.n : 0;
+        info->num_tiles = G->num_tiles;
+        info->rows_per_tile = G->rows_per_tile;
+        info->sweeps_done = (int64_t)G->sweep;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_debug_gibbs_assignments(polee_gibbs *G, int32_t chain, int32_t *z)
 {
-    if (!G || !z) return fail(G ? G->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_debug_gibbs_assignments: null argument");
-    polee_ctx *ctx = G->ctx;
-    return guarded(ctx, "polee_debug_gibbs_assignments", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(G, "polee_debug_gibbs_assignments", [&](polee_ctx *ctx) -> polee_status {
+        if (!z) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_gibbs_assignments: null argument");
         if (chain < 0 || chain >= G->C) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_gibbs_assignments: chain out of range");
         if (G->sweep == 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_gibbs_assignments: no sweep has run");
         DevBuf<uint32_t> dz;

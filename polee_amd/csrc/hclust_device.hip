@@ -1076,33 +1076,35 @@ polee_status hclust_rounds_device_from_xt(polee_ctx *ctx, int64_t m, int64_t n, 
 
 }  // namespace polee
 
+using polee::ctx_entry;
+
 extern "C" polee_status polee_hclust_parallel_device(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes, const uint32_t *rowval,
                                                      int32_t *node_parent_idxs, int32_t *node_js)
 {
-    return polee::guarded(ctx, "polee_hclust_parallel_device",
-                          [&] { return polee::hclust_rounds_device(ctx, m, n, colptr, colptr_bytes, rowval, node_parent_idxs, node_js); });
+    return ctx_entry(ctx, "polee_hclust_parallel_device", [&]() -> polee_status {
+        return polee::hclust_rounds_device(ctx, m, n, colptr, colptr_bytes, rowval, node_parent_idxs, node_js);
+    });
 }
 
 extern "C" polee_status polee_hclust_parallel_device_from_devx(polee_ctx *ctx, const polee_devx *dx, int32_t *node_parent_idxs, int32_t *node_js)
 {
-    return polee::guarded(ctx, "polee_hclust_parallel_device_from_devx", [&]() -> polee_status {
-        if (!ctx || !dx || !node_parent_idxs || !node_js) return polee::fail(ctx, POLEE_ERR_BAD_ARG, "polee_hclust_parallel_device_from_devx: null argument");
+    return ctx_entry(ctx, "polee_hclust_parallel_device_from_devx", [&]() -> polee_status {
+        if (!dx || !node_parent_idxs || !node_js) return polee::fail(ctx, POLEE_ERR_BAD_ARG, "polee_hclust_parallel_device_from_devx: null argument");
         if (dx->ctx->device != ctx->device) return polee::fail(ctx, POLEE_ERR_BAD_ARG, "polee_hclust_parallel_device_from_devx: X lives on another device");
-        POLEE_TRY(polee::use_device(ctx));
         return polee::hclust_rounds_device_core(ctx, dx->m, dx->n, dx->cp.p, dx->nnz, dx->rowval.p, node_parent_idxs, node_js);
     });
 }
 
 extern "C" polee_status polee_hclust_parallel_device_from_xbuild(polee_ctx *ctx, const polee_xbuild *xb, int32_t *node_parent_idxs, int32_t *node_js)
 {
-    return polee::guarded(ctx, "polee_hclust_parallel_device_from_xbuild", [&]() -> polee_status {
+    return ctx_entry(ctx, "polee_hclust_parallel_device_from_xbuild", [&]() -> polee_status {
         polee_ctx *xctx = nullptr;
         int64_t m = 0, n = 0;
         const uint64_t *tcolptr = nullptr;
         const uint32_t *trowval = nullptr;
         const float *tnzval = nullptr;
         POLEE_TRY(polee::xbuild_device_view(xb, &xctx, &m, &n, &tcolptr, &trowval, &tnzval));
-        if (!ctx || xctx->device != ctx->device) return polee::fail(ctx, POLEE_ERR_BAD_ARG, "polee_hclust_parallel_device_from_xbuild: the xbuild result lives on another device");
+        if (xctx->device != ctx->device) return polee::fail(ctx, POLEE_ERR_BAD_ARG, "polee_hclust_parallel_device_from_xbuild: the xbuild result lives on another device");
         POLEE_HIP_TRY(ctx, hipStreamSynchronize(xctx->stream));
         return polee::hclust_rounds_device_from_xt(ctx, m, n, tcolptr, trowval, node_parent_idxs, node_js);
     });

@@ -214,9 +214,9 @@ using namespace polee;
 
 extern "C" polee_status polee_kmer_tree_rounds_host(int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js, int64_t *stats)
 {
-    if (n < 1 || n > POLEE_KMER_MAX_N || !sketches || !node_parent_idxs || !node_js)
-        return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_tree_rounds_host: null argument, or n outside 1 .. %lld", (long long)POLEE_KMER_MAX_N);
-    return guarded(nullptr, "polee_kmer_tree_rounds_host", [&]() -> polee_status {
+    return host_entry("polee_kmer_tree_rounds_host", [&]() -> polee_status {
+        if (n < 1 || n > POLEE_KMER_MAX_N || !sketches || !node_parent_idxs || !node_js)
+            return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_tree_rounds_host: null argument, or n outside 1 .. %lld", (long long)POLEE_KMER_MAX_N);
         KmerClock clk;
         KmerIndex ix;
         POLEE_TRY(kmer_index_host(n, sketches, ix));

@@ -499,8 +499,7 @@ using namespace polee;
 
 extern "C" polee_status polee_kmer_tree_rounds(polee_ctx *ctx, int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js, int64_t *stats)
 {
-    return guarded(ctx, "polee_kmer_tree_rounds", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_kmer_tree_rounds", [&]() -> polee_status {
         if (n < 1 || n > POLEE_KMER_MAX_N || !sketches || !node_parent_idxs || !node_js)
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_kmer_tree_rounds: null argument, or n outside 1 .. %lld", (long long)POLEE_KMER_MAX_N);
         POLEE_TRY(kmer_validate_sketches(ctx, n, sketches));
@@ -515,8 +514,7 @@ extern "C" polee_status polee_kmer_tree_rounds(polee_ctx *ctx, int64_t n, const 
 extern "C" polee_status polee_fit_tree_rounds(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, int32_t *node_parent_idxs,
                                               int32_t *node_js, int64_t *stats)
 {
-    return guarded(ctx, "polee_fit_tree_rounds", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_fit_tree_rounds", [&]() -> polee_status {
         POLEE_TRY(kmer_check_offsets(ctx, n, offsets, bases, "polee_fit_tree_rounds"));
         if (!node_parent_idxs || !node_js) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_fit_tree_rounds: null output");
         KmerClock clk;
@@ -526,10 +524,11 @@ extern "C" polee_status polee_fit_tree_rounds(polee_ctx *ctx, int64_t n, const i
     });
 }
 
+// (a context or null = the selection on the host threads: host_entry, not ctx_entry, and the device branch selects the device itself)
 extern "C" polee_status polee_debug_kmer_round_select(polee_ctx *ctx, int64_t num_nodes, int64_t E, const uint32_t *u, const uint32_t *v, const uint64_t *key,
                                                       uint8_t *merged_flags, int32_t *order)
 {
-    return guarded(ctx, "polee_debug_kmer_round_select", [&]() -> polee_status {
+    return host_entry("polee_debug_kmer_round_select", [&]() -> polee_status {
         if (num_nodes < 1 || num_nodes > 2 * POLEE_KMER_MAX_N || E < 0 || E >= (1LL << 31) || (E && (!u || !v || !key || !merged_flags || !order)))
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_kmer_round_select: null argument, or a count out of range");
         std::vector<KmerREdge> edges((size_t)E);

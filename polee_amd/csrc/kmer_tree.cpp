@@ -253,11 +253,11 @@ using namespace polee;
 
 extern "C" polee_status polee_kmer_sketch_host(int64_t n, const int64_t *offsets, const uint8_t *bases, uint64_t *sketches)
 {
-    if (n < 0 || !offsets || !sketches) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_sketch_host: null argument or negative n");
-    for (int64_t t = 0; t < n; ++t)
-        if (offsets[t] < 0 || offsets[t + 1] < offsets[t]) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_sketch_host: offsets must not decrease");
-    if (n && offsets[n] > 0 && !bases) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_sketch_host: null bases");
-    return guarded(nullptr, "polee_kmer_sketch_host", [&]() -> polee_status {
+    return host_entry("polee_kmer_sketch_host", [&]() -> polee_status {
+        if (n < 0 || !offsets || !sketches) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_sketch_host: null argument or negative n");
+        for (int64_t t = 0; t < n; ++t)
+            if (offsets[t] < 0 || offsets[t + 1] < offsets[t]) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_sketch_host: offsets must not decrease");
+        if (n && offsets[n] > 0 && !bases) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_sketch_host: null bases");
         parallel_chunks((size_t)n, 64, [&](size_t lo, size_t hi, unsigned) {
             for (size_t t = lo; t < hi; ++t) sketch_one(bases + offsets[t], offsets[t + 1] - offsets[t], sketches + t * KMER_H);
         });
@@ -267,9 +267,9 @@ extern "C" polee_status polee_kmer_sketch_host(int64_t n, const int64_t *offsets
 
 extern "C" polee_status polee_kmer_tree_host(int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js)
 {
-    if (n < 1 || n > POLEE_KMER_MAX_N || !sketches || !node_parent_idxs || !node_js)
-        return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_tree_host: null argument, or n outside 1 .. %lld", (long long)POLEE_KMER_MAX_N);
-    return guarded(nullptr, "polee_kmer_tree_host", [&]() -> polee_status {
+    return host_entry("polee_kmer_tree_host", [&]() -> polee_status {
+        if (n < 1 || n > POLEE_KMER_MAX_N || !sketches || !node_parent_idxs || !node_js)
+            return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_kmer_tree_host: null argument, or n outside 1 .. %lld", (long long)POLEE_KMER_MAX_N);
         KmerClock clk;
         KmerIndex ix;
         POLEE_TRY(kmer_index_host(n, sketches, ix));

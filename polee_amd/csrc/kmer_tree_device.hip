@@ -378,9 +378,10 @@ polee_status tree_from_device_sketches(polee_ctx *ctx, int64_t n, const uint64_t
     return POLEE_OK;
 }
 
-polee_status index_any(polee_ctx *ctx, int64_t n, const uint64_t *sketches, KmerIndex &ix)
+// (a null context: the host's index)
+polee_status index_any(polee_ctx *ctx, const char *what, int64_t n, const uint64_t *sketches, KmerIndex &ix)
 {
-    if (n < 1 || n > POLEE_KMER_MAX_N || !sketches) return fail(ctx, POLEE_ERR_BAD_ARG, "k-mer tree: null sketches, or n outside 1 .. %lld", (long long)POLEE_KMER_MAX_N);
+    if (n < 1 || n > POLEE_KMER_MAX_N || !sketches) return fail(ctx, POLEE_ERR_BAD_ARG, "%s: null sketches, or n outside 1 .. %lld", what, (long long)POLEE_KMER_MAX_N);
     if (!ctx) return kmer_index_host(n, sketches, ix);
     POLEE_TRY(use_device(ctx));
     POLEE_TRY(kmer_validate_sketches(ctx, n, sketches));
@@ -396,8 +397,7 @@ using namespace polee;
 
 extern "C" polee_status polee_kmer_sketch(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, uint64_t *sketches)
 {
-    return guarded(ctx, "polee_kmer_sketch", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_kmer_sketch", [&]() -> polee_status {
         POLEE_TRY(kmer_check_offsets(ctx, n, offsets, bases, "polee_kmer_sketch"));
         if (!sketches) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_kmer_sketch: null output");
         KmerClock clk;
@@ -409,8 +409,7 @@ extern "C" polee_status polee_kmer_sketch(polee_ctx *ctx, int64_t n, const int64
 
 extern "C" polee_status polee_kmer_tree(polee_ctx *ctx, int64_t n, const uint64_t *sketches, int32_t *node_parent_idxs, int32_t *node_js)
 {
-    return guarded(ctx, "polee_kmer_tree", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_kmer_tree", [&]() -> polee_status {
         if (n < 1 || n > POLEE_KMER_MAX_N || !sketches || !node_parent_idxs || !node_js)
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_kmer_tree: null argument, or n outside 1 .. %lld", (long long)POLEE_KMER_MAX_N);
         POLEE_TRY(kmer_validate_sketches(ctx, n, sketches));
@@ -424,8 +423,7 @@ extern "C" polee_status polee_kmer_tree(polee_ctx *ctx, int64_t n, const uint64_
 
 extern "C" polee_status polee_fit_tree(polee_ctx *ctx, int64_t n, const int64_t *offsets, const uint8_t *bases, int32_t *node_parent_idxs, int32_t *node_js)
 {
-    return guarded(ctx, "polee_fit_tree", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_fit_tree", [&]() -> polee_status {
         POLEE_TRY(kmer_check_offsets(ctx, n, offsets, bases, "polee_fit_tree"));
         if (!node_parent_idxs || !node_js) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_fit_tree: null output");
         KmerClock clk;
@@ -435,12 +433,14 @@ extern "C" polee_status polee_fit_tree(polee_ctx *ctx, int64_t n, const int64_t 
     });
 }
 
+// (the two debug hooks below take a context or null = the host's index, so they open through host_entry, not ctx_entry, and
+// index_any selects the device; an exception is then recorded in the thread's error only, not in the context's)
 extern "C" polee_status polee_debug_kmer_edges_count(polee_ctx *ctx, int64_t n, const uint64_t *sketches, int64_t *count)
 {
-    return guarded(ctx, "polee_debug_kmer_edges_count", [&]() -> polee_status {
+    return host_entry("polee_debug_kmer_edges_count", [&]() -> polee_status {
         if (!count) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_kmer_edges_count: null count");
         KmerIndex ix;
-        POLEE_TRY(index_any(ctx, n, sketches, ix));
+        POLEE_TRY(index_any(ctx, "polee_debug_kmer_edges_count", n, sketches, ix));
         *count = (int64_t)ix.edges.size();
         return POLEE_OK;
     });
@@ -449,9 +449,9 @@ extern "C" polee_status polee_debug_kmer_edges_count(polee_ctx *ctx, int64_t n, 
 extern "C" polee_status polee_debug_kmer_edges_fill(polee_ctx *ctx, int64_t n, const uint64_t *sketches, int64_t capacity, uint32_t *u, uint32_t *v,
                                                     uint32_t *mat, uint32_t *empt)
 {
-    return guarded(ctx, "polee_debug_kmer_edges_fill", [&]() -> polee_status {
+    return host_entry("polee_debug_kmer_edges_fill", [&]() -> polee_status {
         KmerIndex ix;
-        POLEE_TRY(index_any(ctx, n, sketches, ix));
+        POLEE_TRY(index_any(ctx, "polee_debug_kmer_edges_fill", n, sketches, ix));
         if ((int64_t)ix.edges.size() > capacity || (ix.edges.size() && (!u || !v || !mat || !empt)))
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_kmer_edges_fill: %zu edges, room for %lld", ix.edges.size(), (long long)capacity);
         for (size_t i = 0; i < ix.edges.size(); ++i) {

@@ -853,74 +853,76 @@ extern "C" {
 
 polee_status polee_loglik_set_deterministic(polee_loglik *ll, int on)
 {
-    if (!ll) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    ll->deterministic = on != 0;
-    return POLEE_OK;
+    return entry(ll, "polee_loglik_set_deterministic", [&](polee_ctx *ctx) -> polee_status {
+        ll->deterministic = on != 0;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_debug_loglik_force_mixed(polee_loglik *ll, int on)
 {
-    if (!ll) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    ll->force_mixed = on != 0;
-    return POLEE_OK;
+    return entry(ll, "polee_debug_loglik_force_mixed", [&](polee_ctx *ctx) -> polee_status {
+        ll->force_mixed = on != 0;
+        return POLEE_OK;
+    });
 }
 
 void polee_loglik_destroy(polee_loglik *ll) { loglik_release(ll); }
 
 polee_status polee_loglik_eval(polee_loglik *ll, const float *xs, int32_t K, double *x_grad, double *lp)
 {
-    if (!ll) return fail(nullptr, POLEE_ERR_BAD_ARG, "null likelihood handle");
-    polee_ctx *ctx = ll->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!xs || !x_grad || K < 1 || K > PSELL_MAX_K)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_loglik_eval: bad argument (K must be 1..8)");
-    const size_t n = ll->n, tot = n * K;
-    POLEE_TRY(ll->d_x_rows.upload(ctx, xs, tot));
-    POLEE_TRY(ll->d_x_aos.alloc(ctx, tot));
-    POLEE_TRY(ll->d_g_aos.alloc(ctx, tot));
-    POLEE_TRY(ll->d_g_rows.alloc(ctx, tot));
-    POLEE_TRY(ll->d_lp.alloc(ctx, PSELL_MAX_K));
-    const unsigned nb = (unsigned)ceil_div(tot, 256);
-    hipLaunchKernelGGL(rows_to_aos_kernel, dim3(nb), dim3(256), 0, ctx->stream, ll->d_x_rows.p, K, (int64_t)n,
-                       ll->d_x_aos.p);
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(ll->d_g_aos.p, 0, tot * sizeof(float), ctx->stream));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(ll->d_lp.p, 0, PSELL_MAX_K * sizeof(double), ctx->stream));
-    POLEE_TRY(loglik_eval_device(ll, ll->d_x_aos.p, K, ll->d_g_aos.p, lp ? ll->d_lp.p : nullptr));
-    hipLaunchKernelGGL(aos_to_rows_f64_kernel, dim3(nb), dim3(256), 0, ctx->stream, ll->d_g_aos.p, K, (int64_t)n,
-                       ll->d_g_rows.p);
-    POLEE_KERNEL_CHECK(ctx);
-    POLEE_TRY(ll->d_g_rows.download(ctx, x_grad, tot));
-    if (lp) {
-        POLEE_TRY(ll->d_lp.download(ctx, lp, K));
-        for (int k = 0; k < K; ++k)
-            if (!std::isfinite(lp[k]))
-                return fail(ctx, POLEE_ERR_NONFINITE, "log-likelihood is not finite (likelihood.jl:50)");
-    }
-    return POLEE_OK;
+    return entry(ll, "polee_loglik_eval", [&](polee_ctx *ctx) -> polee_status {
+        if (!xs || !x_grad || K < 1 || K > PSELL_MAX_K)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_loglik_eval: bad argument (K must be 1..8)");
+        const size_t n = ll->n, tot = n * K;
+        POLEE_TRY(ll->d_x_rows.upload(ctx, xs, tot));
+        POLEE_TRY(ll->d_x_aos.alloc(ctx, tot));
+        POLEE_TRY(ll->d_g_aos.alloc(ctx, tot));
+        POLEE_TRY(ll->d_g_rows.alloc(ctx, tot));
+        POLEE_TRY(ll->d_lp.alloc(ctx, PSELL_MAX_K));
+        const unsigned nb = (unsigned)ceil_div(tot, 256);
+        hipLaunchKernelGGL(rows_to_aos_kernel, dim3(nb), dim3(256), 0, ctx->stream, ll->d_x_rows.p, K, (int64_t)n,
+                           ll->d_x_aos.p);
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(ll->d_g_aos.p, 0, tot * sizeof(float), ctx->stream));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(ll->d_lp.p, 0, PSELL_MAX_K * sizeof(double), ctx->stream));
+        POLEE_TRY(loglik_eval_device(ll, ll->d_x_aos.p, K, ll->d_g_aos.p, lp ? ll->d_lp.p : nullptr));
+        hipLaunchKernelGGL(aos_to_rows_f64_kernel, dim3(nb), dim3(256), 0, ctx->stream, ll->d_g_aos.p, K, (int64_t)n,
+                           ll->d_g_rows.p);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(ll->d_g_rows.download(ctx, x_grad, tot));
+        if (lp) {
+            POLEE_TRY(ll->d_lp.download(ctx, lp, K));
+            for (int k = 0; k < K; ++k)
+                if (!std::isfinite(lp[k]))
+                    return fail(ctx, POLEE_ERR_NONFINITE, "log-likelihood is not finite (likelihood.jl:50)");
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_efflen_jacobian_adjustment(polee_ctx *ctx, const float *efflens, const float *xs, int32_t K,
                                               int64_t n, double *x_grad, float *xls)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!efflens || !xs || !x_grad || K < 1 || n < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    DevBuf<float> d_l, d_x, d_xls;
-    DevBuf<double> d_g, d_s;
-    const size_t tot = (size_t)n * K;
-    POLEE_TRY(d_l.upload(ctx, efflens, n));
-    POLEE_TRY(d_x.upload(ctx, xs, tot));
-    POLEE_TRY(d_g.upload(ctx, x_grad, tot));
-    POLEE_TRY(d_s.alloc(ctx, K));
-    if (xls) POLEE_TRY(d_xls.alloc(ctx, tot));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(d_s.p, 0, K * sizeof(double), ctx->stream));
-    const unsigned nb = (unsigned)std::min<int64_t>(ceil_div(n, 256), 1024);
-    hipLaunchKernelGGL(efflen_sum_kernel, dim3(nb, K), dim3(256), 0, ctx->stream, d_l.p, d_x.p, n, d_s.p);
-    hipLaunchKernelGGL(efflen_adjust_kernel, dim3((unsigned)ceil_div(n, 256), K), dim3(256), 0, ctx->stream, d_l.p,
-                       d_x.p, d_s.p, n, d_g.p, xls ? d_xls.p : nullptr);
-    POLEE_KERNEL_CHECK(ctx);
-    POLEE_TRY(d_g.download(ctx, x_grad, tot));
-    if (xls) POLEE_TRY(d_xls.download(ctx, xls, tot));
-    return POLEE_OK;
+    return ctx_entry(ctx, "polee_efflen_jacobian_adjustment", [&]() -> polee_status {
+        if (!efflens || !xs || !x_grad || K < 1 || n < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_efflen_jacobian_adjustment: bad argument");
+        DevBuf<float> d_l, d_x, d_xls;
+        DevBuf<double> d_g, d_s;
+        const size_t tot = (size_t)n * K;
+        POLEE_TRY(d_l.upload(ctx, efflens, n));
+        POLEE_TRY(d_x.upload(ctx, xs, tot));
+        POLEE_TRY(d_g.upload(ctx, x_grad, tot));
+        POLEE_TRY(d_s.alloc(ctx, K));
+        if (xls) POLEE_TRY(d_xls.alloc(ctx, tot));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(d_s.p, 0, K * sizeof(double), ctx->stream));
+        const unsigned nb = (unsigned)std::min<int64_t>(ceil_div(n, 256), 1024);
+        hipLaunchKernelGGL(efflen_sum_kernel, dim3(nb, K), dim3(256), 0, ctx->stream, d_l.p, d_x.p, n, d_s.p);
+        hipLaunchKernelGGL(efflen_adjust_kernel, dim3((unsigned)ceil_div(n, 256), K), dim3(256), 0, ctx->stream, d_l.p,
+                           d_x.p, d_s.p, n, d_g.p, xls ? d_xls.p : nullptr);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(d_g.download(ctx, x_grad, tot));
+        if (xls) POLEE_TRY(d_xls.download(ctx, xls, tot));
+        return POLEE_OK;
+    });
 }
 
 }  // extern "C"

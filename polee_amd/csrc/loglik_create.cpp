@@ -356,14 +356,18 @@ static polee_status polee_loglik_create_from_xbuild_impl(polee_ctx *ctx, const p
 
 polee_status polee_loglik_create_from_xbuild(polee_ctx *ctx, const polee_xbuild *xb, const int64_t *ks, polee_loglik **out)
 {
-    return guarded(ctx, "polee_loglik_create_from_xbuild", [&] { return polee_loglik_create_from_xbuild_impl(ctx, xb, ks, out); });
+    return ctx_entry(ctx, "polee_loglik_create_from_xbuild", [&]() -> polee_status {
+        return polee_loglik_create_from_xbuild_impl(ctx, xb, ks, out);
+    });
 }
 
 polee_status polee_loglik_create_from_xt(polee_ctx *ctx, int64_t m, int64_t n, const uint64_t *tcolptr,
                                          const uint32_t *trowval, const float *tnzval, const int64_t *ks,
                                          polee_loglik **out)
 {
-    return guarded(ctx, "polee_loglik_create_from_xt", [&] { return polee_loglik_create_from_xt_impl(ctx, m, n, tcolptr, trowval, tnzval, ks, out); });
+    return ctx_entry(ctx, "polee_loglik_create_from_xt", [&]() -> polee_status {
+        return polee_loglik_create_from_xt_impl(ctx, m, n, tcolptr, trowval, tnzval, ks, out);
+    });
 }
 
 static polee_status polee_loglik_create_impl(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes,
@@ -402,15 +406,16 @@ static polee_status polee_loglik_create_impl(polee_ctx *ctx, int64_t m, int64_t 
 polee_status polee_loglik_create(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes,
                                  const uint32_t *rowval, const float *nzval, const int64_t *ks, polee_loglik **out)
 {
-    return guarded(ctx, "polee_loglik_create", [&] { return polee_loglik_create_impl(ctx, m, n, colptr, colptr_bytes, rowval, nzval, ks, out); });
+    return ctx_entry(ctx, "polee_loglik_create", [&]() -> polee_status {
+        return polee_loglik_create_impl(ctx, m, n, colptr, colptr_bytes, rowval, nzval, ks, out);
+    });
 }
 
 // ---- X on the device, once, for the tree and the layout ------------------------------------------------------
 polee_status polee_devx_upload(polee_ctx *ctx, int64_t m, int64_t n, const void *colptr, int colptr_bytes, const uint32_t *rowval,
                                const float *nzval, polee_devx **out)
 {
-    return guarded(ctx, "polee_devx_upload", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_devx_upload", [&]() -> polee_status {
         if (!colptr || !out || m < 0 || n < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_devx_upload: bad argument");
         std::vector<uint64_t> cp;
         uint64_t nnz = 0;
@@ -439,10 +444,7 @@ polee_status polee_devx_upload(polee_ctx *ctx, int64_t m, int64_t n, const void 
 
 polee_status polee_devx_upload_values(polee_devx *dx, const float *nzval)
 {
-    if (!dx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_devx_upload_values: null argument");
-    polee_ctx *ctx = dx->ctx;
-    return guarded(ctx, "polee_devx_upload_values", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(dx, "polee_devx_upload_values", [&](polee_ctx *ctx) -> polee_status {
         if (dx->nnz && !nzval) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_devx_upload_values: null argument");
         if (dx->nnz) POLEE_TRY(dx->nzval.upload(ctx, nzval, (size_t)dx->nnz));
         return POLEE_OK;
@@ -463,8 +465,7 @@ void polee_devx_destroy(polee_devx *dx)
 
 polee_status polee_loglik_create_from_devx(polee_ctx *ctx, polee_devx *dx, const float *nzval, const int64_t *ks, polee_loglik **out)
 {
-    return guarded(ctx, "polee_loglik_create_from_devx", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_loglik_create_from_devx", [&]() -> polee_status {
         if (!dx || !out) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_loglik_create_from_devx: null argument");
         if (dx->ctx->device != ctx->device) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_loglik_create_from_devx: X lives on another device");
         if (dx->nnz && !dx->nzval.p && !nzval)
@@ -504,32 +505,34 @@ polee_status polee_loglik_create_from_devx(polee_ctx *ctx, polee_devx *dx, const
 
 polee_status polee_loglik_get_info(const polee_loglik *ll, polee_loglik_info *info)
 {
-    if (!ll || !info) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    const PsellHost &h = ll->host;
-    info->m = ll->m;
-    info->n = ll->n;
-    info->nnz = ll->nnz;
-    info->num_slices = h.num_slices;
-    info->num_tiles = h.num_tiles;
-    info->padded_nnz = h.padded_nnz;
-    info->stream_bytes = (int64_t)(ll->d_data.n + 4 * (ll->d_slice_off.n + ll->d_tile_slice.n + ll->d_tile_dict.n +
-                                                        ll->d_dict.n + ll->d_slice_ks.n + ll->d_csr_rowptr.n + ll->d_csr_col.n +
-                                                        ll->d_csr_val.n + ll->d_csr_ks.n));
-    info->device_bytes = info->stream_bytes;
-    info->num_empty_rows = h.empty_rows;
-    info->max_row_nnz = h.max_row;
-    info->max_tile_cols = h.max_tile_cols;
-    const int64_t tiles[PSELL_NSTREAMS] = {h.num_tiles_a1, h.num_tiles_a1m - h.num_tiles_a1, h.num_tiles_a2 - h.num_tiles_a1m,
-                                           h.num_tiles_a - h.num_tiles_a2, h.num_tiles_s - h.num_tiles_a, h.num_tiles - h.num_tiles_s, 0};
-    for (int i = 0; i < 8; ++i) info->stream_rows[i] = info->stream_nnz[i] = info->stream_tiles[i] = info->stream_bytes_hbm[i] = 0;
-    for (int i = 0; i < PSELL_NSTREAMS; ++i) {
-        info->stream_rows[i] = h.stream_rows[i];
-        info->stream_nnz[i] = h.stream_nnz[i];
-        info->stream_tiles[i] = tiles[i];
-        info->stream_bytes_hbm[i] = h.stream_bytes[i];
-    }
-    info->dict_entries = ll->dict_len;
-    return POLEE_OK;
+    return entry(ll, "polee_loglik_get_info", [&](polee_ctx *ctx) -> polee_status {
+        if (!info) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_loglik_get_info: null argument");
+        const PsellHost &h = ll->host;
+        info->m = ll->m;
+        info->n = ll->n;
+        info->nnz = ll->nnz;
+        info->num_slices = h.num_slices;
+        info->num_tiles = h.num_tiles;
+        info->padded_nnz = h.padded_nnz;
+        info->stream_bytes = (int64_t)(ll->d_data.n + 4 * (ll->d_slice_off.n + ll->d_tile_slice.n + ll->d_tile_dict.n +
+                                                            ll->d_dict.n + ll->d_slice_ks.n + ll->d_csr_rowptr.n + ll->d_csr_col.n +
+                                                            ll->d_csr_val.n + ll->d_csr_ks.n));
+        info->device_bytes = info->stream_bytes;
+        info->num_empty_rows = h.empty_rows;
+        info->max_row_nnz = h.max_row;
+        info->max_tile_cols = h.max_tile_cols;
+        const int64_t tiles[PSELL_NSTREAMS] = {h.num_tiles_a1, h.num_tiles_a1m - h.num_tiles_a1, h.num_tiles_a2 - h.num_tiles_a1m,
+                                               h.num_tiles_a - h.num_tiles_a2, h.num_tiles_s - h.num_tiles_a, h.num_tiles - h.num_tiles_s, 0};
+        for (int i = 0; i < 8; ++i) info->stream_rows[i] = info->stream_nnz[i] = info->stream_tiles[i] = info->stream_bytes_hbm[i] = 0;
+        for (int i = 0; i < PSELL_NSTREAMS; ++i) {
+            info->stream_rows[i] = h.stream_rows[i];
+            info->stream_nnz[i] = h.stream_nnz[i];
+            info->stream_tiles[i] = tiles[i];
+            info->stream_bytes_hbm[i] = h.stream_bytes[i];
+        }
+        info->dict_entries = ll->dict_len;
+        return POLEE_OK;
+    });
 }
 
 }  // extern "C"

@@ -382,37 +382,41 @@ extern "C" {
 polee_status polee_make_inverse_ptt_params(const int32_t *node_parent_idxs, const int32_t *node_js, int32_t N,
                                            int32_t *left_index, int32_t *right_index, int32_t *leaf_index)
 {
-    if (!node_parent_idxs || !node_js || !left_index || !right_index || !leaf_index || N < 1)
-        return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_make_inverse_ptt_params: bad argument");
-    std::vector<int32_t> l, r, f;
-    std::string err = children_from_parents(node_parent_idxs, node_js, N, l, r, f);
-    if (!err.empty()) return fail(nullptr, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
-    std::copy(l.begin(), l.end(), left_index);
-    std::copy(r.begin(), r.end(), right_index);
-    std::copy(f.begin(), f.end(), leaf_index);
-    return POLEE_OK;
+    return host_entry("polee_make_inverse_ptt_params", [&]() -> polee_status {
+        if (!node_parent_idxs || !node_js || !left_index || !right_index || !leaf_index || N < 1)
+            return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_make_inverse_ptt_params: bad argument");
+        std::vector<int32_t> l, r, f;
+        std::string err = children_from_parents(node_parent_idxs, node_js, N, l, r, f);
+        if (!err.empty()) return fail(nullptr, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
+        std::copy(l.begin(), l.end(), left_index);
+        std::copy(r.begin(), r.end(), right_index);
+        std::copy(f.begin(), f.end(), leaf_index);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_ptt_create_from_index(polee_ctx *ctx, const int32_t *left_index, const int32_t *right_index,
                                          const int32_t *leaf_index, int32_t N, polee_ptt **out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!left_index || !right_index || !leaf_index || !out) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
-    std::vector<PttPlan> plans(1);
-    std::string err = build_ptt_plan(left_index, right_index, leaf_index, N, plans[0]);
-    if (!err.empty()) return fail(ctx, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
-    return ptt_create_from_plans(ctx, std::move(plans), out);
+    return ctx_entry(ctx, "polee_ptt_create_from_index", [&]() -> polee_status {
+        if (!left_index || !right_index || !leaf_index || !out) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_ptt_create_from_index: null argument");
+        std::vector<PttPlan> plans(1);
+        std::string err = build_ptt_plan(left_index, right_index, leaf_index, N, plans[0]);
+        if (!err.empty()) return fail(ctx, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
+        return ptt_create_from_plans(ctx, std::move(plans), out);
+    });
 }
 
 polee_status polee_ptt_create(polee_ctx *ctx, const int32_t *node_parent_idxs, const int32_t *node_js, int32_t N,
                               polee_ptt **out)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!node_parent_idxs || !node_js || !out || N < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
-    std::vector<int32_t> l, r, f;
-    std::string err = children_from_parents(node_parent_idxs, node_js, N, l, r, f);
-    if (!err.empty()) return fail(ctx, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
-    return polee_ptt_create_from_index(ctx, l.data(), r.data(), f.data(), N, out);
+    return ctx_entry(ctx, "polee_ptt_create", [&]() -> polee_status {
+        if (!node_parent_idxs || !node_js || !out || N < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_ptt_create: null argument");
+        std::vector<int32_t> l, r, f;
+        std::string err = children_from_parents(node_parent_idxs, node_js, N, l, r, f);
+        if (!err.empty()) return fail(ctx, POLEE_ERR_BAD_ARG, "malformed tree: %s", err.c_str());
+        return polee_ptt_create_from_index(ctx, l.data(), r.data(), f.data(), N, out);
+    });
 }
 
 void polee_ptt_destroy(polee_ptt *t) { ptt_release(t); }
@@ -421,60 +425,58 @@ int32_t polee_ptt_n(const polee_ptt *t) { return t ? t->n : 0; }
 
 polee_status polee_ptt_transform(polee_ptt *t, const double *ys, int32_t B, float *xs, double *ladj)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!ys || !xs || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_ptt_transform: bad argument");
-    POLEE_TRY(t->reserve(B));
-    const size_t nm1 = t->n - 1;
-    POLEE_TRY(t->d_ys.upload(ctx, ys, (size_t)B * nm1));
-    POLEE_TRY(t->d_f32a.alloc(ctx, (size_t)B * t->n));
-    FwdOut o;
-    o.uleaf = t->d_uleaf.p;
-    o.logu = t->d_logu.p;
-    o.xs = t->d_f32a.p;
-    o.xs_rs = t->n;
-    o.row_sums = ladj ? t->d_row.p : nullptr;
-    POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
-    POLEE_TRY(t->d_f32a.download(ctx, xs, (size_t)B * t->n));
-    if (ladj) {
-        std::vector<double> rs((size_t)B * 2);
-        POLEE_TRY(t->d_row.download(ctx, rs.data(), rs.size()));
-        for (int b = 0; b < B; ++b) {
-            ladj[b] = rs[(size_t)b * 2 + 1];
-            if (!std::isfinite(ladj[b]))
-                return fail(ctx, POLEE_ERR_NONFINITE, "transform!: non-finite ladj (ptt.jl:157)");
+    return entry(t, "polee_ptt_transform", [&](polee_ctx *ctx) -> polee_status {
+        if (!ys || !xs || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_ptt_transform: bad argument");
+        POLEE_TRY(t->reserve(B));
+        const size_t nm1 = t->n - 1;
+        POLEE_TRY(t->d_ys.upload(ctx, ys, (size_t)B * nm1));
+        POLEE_TRY(t->d_f32a.alloc(ctx, (size_t)B * t->n));
+        FwdOut o;
+        o.uleaf = t->d_uleaf.p;
+        o.logu = t->d_logu.p;
+        o.xs = t->d_f32a.p;
+        o.xs_rs = t->n;
+        o.row_sums = ladj ? t->d_row.p : nullptr;
+        POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
+        POLEE_TRY(t->d_f32a.download(ctx, xs, (size_t)B * t->n));
+        if (ladj) {
+            std::vector<double> rs((size_t)B * 2);
+            POLEE_TRY(t->d_row.download(ctx, rs.data(), rs.size()));
+            for (int b = 0; b < B; ++b) {
+                ladj[b] = rs[(size_t)b * 2 + 1];
+                if (!std::isfinite(ladj[b]))
+                    return fail(ctx, POLEE_ERR_NONFINITE, "transform!: non-finite ladj (ptt.jl:157)");
+            }
         }
-    }
-    return POLEE_OK;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_ptt_transform_gradients(polee_ptt *t, const double *ys, const double *x_grad, int32_t B,
                                            int with_ladj, double *y_grad)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!ys || !x_grad || !y_grad || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    if (t->n < 2) return POLEE_OK;
-    POLEE_TRY(t->reserve(B));
-    const size_t nm1 = t->n - 1, n = t->n;
-    POLEE_TRY(t->d_ys.upload(ctx, ys, (size_t)B * nm1));
-    POLEE_TRY(t->d_f64a.upload(ctx, x_grad, (size_t)B * n));
-    POLEE_TRY(t->d_f64b.alloc(ctx, (size_t)B * nm1));
-    // u of the leaves (the reference reuses t.us of the preceding transform!; recomputed here)
-    FwdOut o;
-    o.uleaf = t->d_uleaf.p;
-    POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
-    LeafLoadGradF64 load{t->view(), t->d_uleaf.p, t->d_f64a.p};
-    LeafPrefixEmit emit{t->n, t->d_C.p};
-    hipError_t e = run_scan_partial<dd>(ctx->stream, B, t->n, t->d_chunk.p, nullptr, load, emit);
-    if (e != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
-    dim3 grid((unsigned)ceil_div(nm1, 256), B);
-    hipLaunchKernelGGL(ptt_grad_nodes_kernel, grid, dim3(256), 0, ctx->stream, t->view(), t->d_ys.p, t->d_C.p,
-                       with_ladj, t->d_f64b.p);
-    POLEE_KERNEL_CHECK(ctx);
-    return t->d_f64b.download(ctx, y_grad, (size_t)B * nm1);
+    return entry(t, "polee_ptt_transform_gradients", [&](polee_ctx *ctx) -> polee_status {
+        if (!ys || !x_grad || !y_grad || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_ptt_transform_gradients: bad argument");
+        if (t->n < 2) return POLEE_OK;
+        POLEE_TRY(t->reserve(B));
+        const size_t nm1 = t->n - 1, n = t->n;
+        POLEE_TRY(t->d_ys.upload(ctx, ys, (size_t)B * nm1));
+        POLEE_TRY(t->d_f64a.upload(ctx, x_grad, (size_t)B * n));
+        POLEE_TRY(t->d_f64b.alloc(ctx, (size_t)B * nm1));
+        // u of the leaves (the reference reuses t.us of the preceding transform!; recomputed here)
+        FwdOut o;
+        o.uleaf = t->d_uleaf.p;
+        POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
+        LeafLoadGradF64 load{t->view(), t->d_uleaf.p, t->d_f64a.p};
+        LeafPrefixEmit emit{t->n, t->d_C.p};
+        hipError_t e = run_scan_partial<dd>(ctx->stream, B, t->n, t->d_chunk.p, nullptr, load, emit);
+        if (e != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
+        dim3 grid((unsigned)ceil_div(nm1, 256), B);
+        hipLaunchKernelGGL(ptt_grad_nodes_kernel, grid, dim3(256), 0, ctx->stream, t->view(), t->d_ys.p, t->d_C.p,
+                           with_ladj, t->d_f64b.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return t->d_f64b.download(ctx, y_grad, (size_t)B * nm1);
+    });
 }
 
 static polee_status inverse_impl(polee_ptt *t, const float *xs, int32_t B, int julia_log, double *ys,
@@ -509,60 +511,60 @@ static polee_status inverse_impl(polee_ptt *t, const float *xs, int32_t B, int j
 
 polee_status polee_ptt_inverse_transform(polee_ptt *t, const float *xs, int32_t B, double *ys, double *ladj)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    return inverse_impl(t, xs, B, 1, ys, ladj, nullptr);
+    return entry(t, "polee_ptt_inverse_transform", [&](polee_ctx *ctx) -> polee_status {
+        return inverse_impl(t, xs, B, 1, ys, ladj, nullptr);
+    });
 }
 
 polee_status polee_inv_hsb(polee_ptt *t, const float *x, int32_t B, double *y, float *ladj)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    return inverse_impl(t, x, B, 0, y, nullptr, ladj);
+    return entry(t, "polee_inv_hsb", [&](polee_ctx *ctx) -> polee_status {
+        return inverse_impl(t, x, B, 0, y, nullptr, ladj);
+    });
 }
 
 polee_status polee_hsb(polee_ptt *t, const float *y_logit, int32_t B, float *x)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!y_logit || !x || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    POLEE_TRY(t->reserve(B));
-    const size_t nm1 = t->n - 1, n = t->n;
-    POLEE_TRY(t->d_f32b.upload(ctx, y_logit, (size_t)B * nm1));
-    POLEE_TRY(t->d_f32a.alloc(ctx, (size_t)B * n));
-    if (nm1 > 0) {
-        hipLaunchKernelGGL(logistic_f32_to_f64_kernel, dim3((unsigned)ceil_div(B * nm1, 256)), dim3(256), 0,
-                           ctx->stream, t->d_f32b.p, (int64_t)B * nm1, t->d_ys.p);
-        POLEE_KERNEL_CHECK(ctx);
-    }
-    FwdOut o;
-    o.xs = t->d_f32a.p;
-    o.xs_rs = t->n;
-    o.leaf_floor = 0.0;  // the TF op does not floor (hsb_ops.cpp:99-101)
-    POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
-    return t->d_f32a.download(ctx, x, (size_t)B * n);
+    return entry(t, "polee_hsb", [&](polee_ctx *ctx) -> polee_status {
+        if (!y_logit || !x || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_hsb: bad argument");
+        POLEE_TRY(t->reserve(B));
+        const size_t nm1 = t->n - 1, n = t->n;
+        POLEE_TRY(t->d_f32b.upload(ctx, y_logit, (size_t)B * nm1));
+        POLEE_TRY(t->d_f32a.alloc(ctx, (size_t)B * n));
+        if (nm1 > 0) {
+            hipLaunchKernelGGL(logistic_f32_to_f64_kernel, dim3((unsigned)ceil_div(B * nm1, 256)), dim3(256), 0,
+                               ctx->stream, t->d_f32b.p, (int64_t)B * nm1, t->d_ys.p);
+            POLEE_KERNEL_CHECK(ctx);
+        }
+        FwdOut o;
+        o.xs = t->d_f32a.p;
+        o.xs_rs = t->n;
+        o.leaf_floor = 0.0;  // the TF op does not floor (hsb_ops.cpp:99-101)
+        POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
+        return t->d_f32a.download(ctx, x, (size_t)B * n);
+    });
 }
 
 polee_status polee_inv_hsb_grad(polee_ptt *t, const double *y_grad, const float *ladj_grad, const double *y,
                                 int32_t B, float *backprops)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!y_grad || !ladj_grad || !y || !backprops || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    POLEE_TRY(t->reserve(B));
-    const size_t nm1 = t->n - 1, n = t->n;
-    POLEE_TRY(t->d_ys.upload(ctx, y, (size_t)B * nm1));
-    POLEE_TRY(t->d_f64a.upload(ctx, y_grad, (size_t)B * nm1));
-    POLEE_TRY(t->d_f32b.upload(ctx, ladj_grad, (size_t)B));
-    POLEE_TRY(t->d_f32a.alloc(ctx, (size_t)B * n));
-    FwdOut o;
-    o.logu = t->d_logu.p;
-    POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
-    InvGradLoad load{t->view(), t->d_ys.p, t->d_f64a.p, t->d_logu.p, t->d_f32b.p};
-    InvGradEmit emit{load, t->d_f32a.p};
-    hipError_t e = run_scan_partial<dd>(ctx->stream, B, t->TL, t->d_chunk.p, nullptr, load, emit);
-    if (e != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
-    return t->d_f32a.download(ctx, backprops, (size_t)B * n);
+    return entry(t, "polee_inv_hsb_grad", [&](polee_ctx *ctx) -> polee_status {
+        if (!y_grad || !ladj_grad || !y || !backprops || B < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_inv_hsb_grad: bad argument");
+        POLEE_TRY(t->reserve(B));
+        const size_t nm1 = t->n - 1, n = t->n;
+        POLEE_TRY(t->d_ys.upload(ctx, y, (size_t)B * nm1));
+        POLEE_TRY(t->d_f64a.upload(ctx, y_grad, (size_t)B * nm1));
+        POLEE_TRY(t->d_f32b.upload(ctx, ladj_grad, (size_t)B));
+        POLEE_TRY(t->d_f32a.alloc(ctx, (size_t)B * n));
+        FwdOut o;
+        o.logu = t->d_logu.p;
+        POLEE_TRY(ptt_forward_device(t, t->d_ys.p, B, o));
+        InvGradLoad load{t->view(), t->d_ys.p, t->d_f64a.p, t->d_logu.p, t->d_f32b.p};
+        InvGradEmit emit{load, t->d_f32a.p};
+        hipError_t e = run_scan_partial<dd>(ctx->stream, B, t->TL, t->d_chunk.p, nullptr, load, emit);
+        if (e != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "scan launch failed: %s", hipGetErrorString(e));
+        return t->d_f32a.download(ctx, backprops, (size_t)B * n);
+    });
 }
 
 }  // extern "C"

@@ -1002,18 +1002,6 @@ polee_status reg_enqueue_step(polee_regression *r, const float *noise, bool want
     return POLEE_OK;
 }
 
-// Every entry point that works on a handle: the arguments are there, the calling thread is on the handle's device, and nothing
-// unwinds through the C ABI.
-template <class F>
-polee_status reg_entry(polee_regression *r, bool args_ok, const char *what, F &&f)
-{
-    if (!r || !args_ok) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "%s: null argument", what);
-    return guarded(r->ctx, what, [&]() -> polee_status {
-        POLEE_TRY(use_device(r->ctx));
-        return f();
-    });
-}
-
 // column means over the S rows of x [S][n]
 std::vector<double> column_means(const float *x, int S, int n)
 {
@@ -1083,8 +1071,7 @@ polee_status polee_regression_create(polee_ctx *ctx, polee_approx *ap, int32_t S
                                      float x_bias_scale0, int use_distortion, float scale_penalty,
                                      int use_point_estimates, polee_regression **out)
 {
-    return guarded(ctx, "polee_regression_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_regression_create", [&]() -> polee_status {
         if (!out || !design || !x_init || !sample_scales || S < 1 || F < 1 || n < 1 || degree < 1)
             return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_create: bad argument");
         if (F > REG_MAXF || degree > REG_MAXDEG)
@@ -1169,28 +1156,33 @@ int64_t polee_debug_regression_num_stats(const polee_regression *r) { return r ?
 
 polee_status polee_regression_get_params(polee_regression *r, float *params)
 {
-    return reg_entry(r, params, "polee_regression_get_params",
-                     [&] { return r->main.p.download(r->ctx, params, (size_t)r->main.num_params()); });
+    return entry(r, "polee_regression_get_params", [&](polee_ctx *ctx) -> polee_status {
+        if (!params) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_get_params: null argument");
+        return r->main.p.download(ctx, params, (size_t)r->main.num_params());
+    });
 }
 
 polee_status polee_regression_set_params(polee_regression *r, const float *params)
 {
-    return reg_entry(r, params, "polee_regression_set_params", [&] {
+    return entry(r, "polee_regression_set_params", [&](polee_ctx *ctx) -> polee_status {
+        if (!params) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_params: null argument");
         r->lse_valid = false;
-        return r->main.p.upload(r->ctx, params, (size_t)r->main.num_params());
+        return r->main.p.upload(ctx, params, (size_t)r->main.num_params());
     });
 }
 
 polee_status polee_regression_weights(polee_regression *r, float *weights)
 {
-    return reg_entry(r, weights, "polee_regression_weights",
-                     [&] { return r->d_W.download(r->ctx, weights, (size_t)r->main.v.deg * r->main.v.n); });
+    return entry(r, "polee_regression_weights", [&](polee_ctx *ctx) -> polee_status {
+        if (!weights) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_weights: null argument");
+        return r->d_W.download(ctx, weights, (size_t)r->main.v.deg * r->main.v.n);
+    });
 }
 
 polee_status polee_regression_set_normal_likelihood(polee_regression *r, const float *loc, const float *scale)
 {
-    return reg_entry(r, loc && scale, "polee_regression_set_normal_likelihood", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_regression_set_normal_likelihood", [&](polee_ctx *ctx) -> polee_status {
+        if (!loc || !scale) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_normal_likelihood: null argument");
         if (r->main.v.point) return fail(ctx, POLEE_ERR_BAD_ARG, "a model with point estimates has no likelihood term");
         const size_t sn = (size_t)r->main.v.S * r->main.v.n;
         for (size_t i = 0; i < sn; ++i)
@@ -1204,7 +1196,8 @@ polee_status polee_regression_set_normal_likelihood(polee_regression *r, const f
 polee_status polee_regression_set_gene_likelihood(polee_regression *r, polee_approx *ap, const int32_t *gene_of,
                                                   const float *x_isoform_init)
 {
-    return reg_entry(r, ap && gene_of && x_isoform_init, "polee_regression_set_gene_likelihood", [&]() -> polee_status {
+    return entry(r, "polee_regression_set_gene_likelihood", [&](polee_ctx *ctx) -> polee_status {
+        if (!ap || !gene_of || !x_isoform_init) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_gene_likelihood: null argument");
         int32_t nt;
         POLEE_TRY(gene_likelihood_check(r, ap, &nt));
         const int S = r->main.v.S;
@@ -1216,7 +1209,7 @@ polee_status polee_regression_set_gene_likelihood(polee_regression *r, polee_app
         std::copy_n(x_isoform_init, snt, ip.begin() + 2 * (size_t)nt);
         RegBlock blk;
         DevBuf<float> xi;
-        POLEE_TRY(blk.init(r->ctx, RegView{}, (int64_t)ip.size(), (int64_t)(nt + snt), ip));
+        POLEE_TRY(blk.init(ctx, RegView{}, (int64_t)ip.size(), (int64_t)(nt + snt), ip));
         POLEE_TRY(gene_likelihood_prepare(r, ap, gene_of, nt, xi));
         gene_likelihood_attach(r, ap, nt, IsoKind::gene, blk, xi);
         return POLEE_OK;
@@ -1227,8 +1220,8 @@ polee_status polee_regression_set_gene_isoform_likelihood(polee_regression *r, p
                                                           const float *x_isoform_init, const float *design_isoform,
                                                           int32_t num_isoform_factors)
 {
-    return reg_entry(r, ap && gene_of && x_isoform_init && design_isoform, "polee_regression_set_gene_isoform_likelihood", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_regression_set_gene_isoform_likelihood", [&](polee_ctx *ctx) -> polee_status {
+        if (!ap || !gene_of || !x_isoform_init || !design_isoform) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_gene_isoform_likelihood: null argument");
         const int S = r->main.v.S, Fi = num_isoform_factors;
         int32_t nt;
         if (Fi < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "at least one isoform factor (got %d)", Fi);
@@ -1258,8 +1251,8 @@ polee_status polee_regression_set_joint_likelihood(polee_regression *r, polee_ap
                                                    const float *x_isoform_init, int32_t num_splice_features,
                                                    const int32_t *pair_transcript, const int32_t *pair_feature, int64_t num_pairs)
 {
-    return reg_entry(r, ap && gene_of && x_isoform_init && pair_transcript && pair_feature, "polee_regression_set_joint_likelihood", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_regression_set_joint_likelihood", [&](polee_ctx *ctx) -> polee_status {
+        if (!ap || !gene_of || !x_isoform_init || !pair_transcript || !pair_feature) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_joint_likelihood: null argument");
         RegView &v = r->main.v;
         const int S = v.S, P = num_splice_features;
         int32_t nt;
@@ -1329,55 +1322,61 @@ polee_status polee_regression_set_joint_likelihood(polee_regression *r, polee_ap
 
 polee_status polee_regression_set_learning_rate(polee_regression *r, float lr)
 {
-    if (!r || !(lr > 0.0f)) return fail(r ? r->ctx : nullptr, POLEE_ERR_BAD_ARG, "bad learning rate");
-    r->lr = lr;
-    r->drop_graph();  // (the step size is an argument of the captured tick kernel)
-    return POLEE_OK;
+    return entry(r, "polee_regression_set_learning_rate", [&](polee_ctx *ctx) -> polee_status {
+        if (!(lr > 0.0f)) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_learning_rate: bad learning rate");
+        r->lr = lr;
+        r->drop_graph();  // (the step size is an argument of the captured tick kernel)
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_regression_get_isoform_params(polee_regression *r, float *params)
 {
-    return reg_entry(r, params, "polee_regression_get_isoform_params", [&] {
-        return r->gene_ap ? r->iso.p.download(r->ctx, params, (size_t)r->iso.num_params()) : fail(r->ctx, POLEE_ERR_BAD_ARG, "no isoform block");
+    return entry(r, "polee_regression_get_isoform_params", [&](polee_ctx *ctx) -> polee_status {
+        if (!params) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_get_isoform_params: null argument");
+        return r->gene_ap ? r->iso.p.download(ctx, params, (size_t)r->iso.num_params()) : fail(ctx, POLEE_ERR_BAD_ARG, "no isoform block");
     });
 }
 
 polee_status polee_regression_set_isoform_params(polee_regression *r, const float *params)
 {
-    return reg_entry(r, params, "polee_regression_set_isoform_params", [&] {
-        return r->gene_ap ? r->iso.p.upload(r->ctx, params, (size_t)r->iso.num_params()) : fail(r->ctx, POLEE_ERR_BAD_ARG, "no isoform block");
+    return entry(r, "polee_regression_set_isoform_params", [&](polee_ctx *ctx) -> polee_status {
+        if (!params) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_isoform_params: null argument");
+        return r->gene_ap ? r->iso.p.upload(ctx, params, (size_t)r->iso.num_params()) : fail(ctx, POLEE_ERR_BAD_ARG, "no isoform block");
     });
 }
 
 // gradient of the isoform block left by the last polee_regression_eval
 polee_status polee_regression_get_isoform_grad(polee_regression *r, float *grad)
 {
-    return reg_entry(r, grad, "polee_regression_get_isoform_grad", [&] {
-        return r->gene_ap ? r->iso.g.download(r->ctx, grad, (size_t)r->iso.num_params()) : fail(r->ctx, POLEE_ERR_BAD_ARG, "no isoform block");
+    return entry(r, "polee_regression_get_isoform_grad", [&](polee_ctx *ctx) -> polee_status {
+        if (!grad) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_get_isoform_grad: null argument");
+        return r->gene_ap ? r->iso.g.download(ctx, grad, (size_t)r->iso.num_params()) : fail(ctx, POLEE_ERR_BAD_ARG, "no isoform block");
     });
 }
 
 polee_status polee_regression_set_comm(polee_regression *r, polee_comm *comm)
 {
-    if (!r) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    if (comm && comm->nranks > 1 && r->gene_ap)
-        return fail(r->ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is not sharded over ranks");
-    if (comm && comm->nranks > 1 && r->latent)
-        return fail(r->ctx, POLEE_ERR_UNSUPPORTED, "a model with a latent design is not sharded over ranks");
-    if (comm && comm->ctx != r->ctx)
-        return fail(r->ctx, POLEE_ERR_BAD_ARG, "communicator and model belong to different contexts");
-    if (comm) ++comm->refs;
-    polee_comm_destroy(r->comm);
-    r->comm = comm;
-    r->drop_graph();
-    return POLEE_OK;
+    return entry(r, "polee_regression_set_comm", [&](polee_ctx *ctx) -> polee_status {
+        if (comm && comm->nranks > 1 && r->gene_ap)
+            return fail(ctx, POLEE_ERR_UNSUPPORTED, "the gene-level model is not sharded over ranks");
+        if (comm && comm->nranks > 1 && r->latent)
+            return fail(ctx, POLEE_ERR_UNSUPPORTED, "a model with a latent design is not sharded over ranks");
+        if (comm && comm->ctx != ctx)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "communicator and model belong to different contexts");
+        if (comm) ++comm->refs;
+        polee_comm_destroy(r->comm);
+        r->comm = comm;
+        r->drop_graph();
+        return POLEE_OK;
+    });
 }
 
 // test hooks (include/polee_hip_debug.h): the two halves of a step, with the exchange left to the caller
 polee_status polee_debug_regression_data_pass(polee_regression *r, const float *noise, float *stats)
 {
-    return reg_entry(r, noise && stats, "polee_debug_regression_data_pass", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_debug_regression_data_pass", [&](polee_ctx *ctx) -> polee_status {
+        if (!noise || !stats) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_regression_data_pass: null argument");
         const RegBlock &mb = r->main;
         POLEE_TRY(reg_fill_noise(r, noise, 0, 0, false));
         POLEE_HIP_TRY(ctx, hipMemsetAsync(mb.loss_slots(), 0, sizeof(float) * REG_SLOTS, ctx->stream));
@@ -1391,11 +1390,12 @@ polee_status polee_debug_regression_data_pass(polee_regression *r, const float *
 
 polee_status polee_debug_regression_prior_pass(polee_regression *r, const float *stats, float *loss, float *grad)
 {
-    return reg_entry(r, stats && loss, "polee_debug_regression_prior_pass", [&]() -> polee_status {
-        POLEE_TRY(r->main.stats.upload(r->ctx, stats, (size_t)r->main.num_stats()));
+    return entry(r, "polee_debug_regression_prior_pass", [&](polee_ctx *ctx) -> polee_status {
+        if (!stats || !loss) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_regression_prior_pass: null argument");
+        POLEE_TRY(r->main.stats.upload(ctx, stats, (size_t)r->main.num_stats()));
         POLEE_TRY(reg_prior_pass(r, RegStep{}));
-        POLEE_TRY(r->main.loss.download(r->ctx, loss, 1));
-        if (grad) POLEE_TRY(r->main.g.download(r->ctx, grad, (size_t)r->main.num_params()));
+        POLEE_TRY(r->main.loss.download(ctx, loss, 1));
+        if (grad) POLEE_TRY(r->main.g.download(ctx, grad, (size_t)r->main.num_params()));
         return POLEE_OK;
     });
 }
@@ -1403,8 +1403,8 @@ polee_status polee_debug_regression_prior_pass(polee_regression *r, const float 
 // ---- classify (models/polee_regression.py:342-413) ---------------------------------------------------------------------------------
 polee_status polee_regression_set_design(polee_regression *r, const float *design)
 {
-    return reg_entry(r, design, "polee_regression_set_design", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_regression_set_design", [&](polee_ctx *ctx) -> polee_status {
+        if (!design) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_design: null argument");
         const RegView &v = r->main.v;
         if (r->gene_ap || v.fixed_ab > 0.0f || (r->comm && r->comm->nranks > 1))
             return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_regression_set_design: the transcript-level model on one GPU only");
@@ -1420,8 +1420,8 @@ polee_status polee_regression_set_design(polee_regression *r, const float *desig
 // ---- latent design (RNASeqPCA, models/polee_pca.py:14-92) --------------------------------------------------------------------------
 polee_status polee_regression_set_latent_design(polee_regression *r, const float *z0, float prior_scale)
 {
-    return reg_entry(r, z0, "polee_regression_set_latent_design", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_regression_set_latent_design", [&](polee_ctx *ctx) -> polee_status {
+        if (!z0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_latent_design: null argument");
         const RegView &v = r->main.v;
         if (r->gene_ap || v.fixed_ab > 0.0f || (r->comm && r->comm->nranks > 1))
             return fail(ctx, POLEE_ERR_UNSUPPORTED, "polee_regression_set_latent_design: the transcript-level model on one GPU only");
@@ -1443,27 +1443,30 @@ polee_status polee_regression_set_latent_design(polee_regression *r, const float
 
 polee_status polee_regression_get_design(polee_regression *r, float *design)
 {
-    return reg_entry(r, design, "polee_regression_get_design",
-                     [&] { return r->d_design.download(r->ctx, design, (size_t)r->main.v.S * r->main.v.F); });
+    return entry(r, "polee_regression_get_design", [&](polee_ctx *ctx) -> polee_status {
+        if (!design) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_get_design: null argument");
+        return r->d_design.download(ctx, design, (size_t)r->main.v.S * r->main.v.F);
+    });
 }
 
 polee_status polee_regression_set_trainable(polee_regression *r, int64_t begin, int64_t end)
 {
-    if (!r) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    const int64_t P = r->main.num_params();
-    if (begin < 0 || end < begin || end > P)
-        return fail(r->ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_trainable: [%lld, %lld) of %lld parameters", (long long)begin,
-                    (long long)end, (long long)P);
-    r->train_lo = begin;
-    r->train_hi = end;
-    r->drop_graph();
-    return POLEE_OK;
+    return entry(r, "polee_regression_set_trainable", [&](polee_ctx *ctx) -> polee_status {
+        const int64_t P = r->main.num_params();
+        if (begin < 0 || end < begin || end > P)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_set_trainable: [%lld, %lld) of %lld parameters", (long long)begin,
+                        (long long)end, (long long)P);
+        r->train_lo = begin;
+        r->train_hi = end;
+        r->drop_graph();
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_regression_design_grad(polee_regression *r, float *grad)
 {
-    return reg_entry(r, grad, "polee_regression_design_grad", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_regression_design_grad", [&](polee_ctx *ctx) -> polee_status {
+        if (!grad) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_design_grad: null argument");
         if (!r->want_dgrad) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_design_grad: call polee_regression_set_design first");
         const size_t SF = (size_t)r->main.v.S * r->main.v.F;
         if (r->latent) return r->d_gz.download(ctx, grad, SF);  // (the total, prior term included: reg_latent_kernel)
@@ -1480,19 +1483,20 @@ polee_status polee_regression_design_grad(polee_regression *r, float *grad)
 
 polee_status polee_regression_eval(polee_regression *r, const float *noise, uint64_t seed, float *loss, float *grad)
 {
-    return reg_entry(r, loss, "polee_regression_eval", [&]() -> polee_status {
+    return entry(r, "polee_regression_eval", [&](polee_ctx *ctx) -> polee_status {
+        if (!loss) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_eval: null argument");
         POLEE_TRY(reg_fill_noise(r, noise, seed, (uint32_t)(r->step + 1), false));
         POLEE_TRY(reg_eval_device(r));
-        POLEE_TRY(r->main.loss.download(r->ctx, loss, 1));
-        if (grad) POLEE_TRY(r->main.g.download(r->ctx, grad, (size_t)r->main.num_params()));
+        POLEE_TRY(r->main.loss.download(ctx, loss, 1));
+        if (grad) POLEE_TRY(r->main.g.download(ctx, grad, (size_t)r->main.num_params()));
         return POLEE_OK;
     });
 }
 
 polee_status polee_regression_fit(polee_regression *r, int32_t niter, uint64_t seed, const float *noise, float *loss_trace)
 {
-    return reg_entry(r, niter >= 0, "polee_regression_fit", [&]() -> polee_status {
-        polee_ctx *ctx = r->ctx;
+    return entry(r, "polee_regression_fit", [&](polee_ctx *ctx) -> polee_status {
+        if (niter < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_regression_fit: null argument");
         if (niter == 0) return POLEE_OK;
         hipStream_t st = ctx->stream;
         const int64_t ne = r->main.num_noise() + r->iso.num_noise();

@@ -324,10 +324,7 @@ extern "C" {
 polee_status polee_sampler_create(polee_ptt *t, const float *mu, const float *sigma, const float *alpha, const float *efflens,
                                   int64_t m, uint64_t seed, polee_sampler **out)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_sampler_create: null tree");
-    polee_ctx *ctx = t->ctx;
-    return guarded(ctx, "polee_sampler_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(t, "polee_sampler_create", [&](polee_ctx *ctx) -> polee_status {
         if (!out || !mu || !sigma || !alpha || !efflens) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_create: null argument");
         if (t->T != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_create: the sampler needs a single tree");
         if (m < 0 || m >= ((int64_t)1 << 31))
@@ -381,18 +378,17 @@ void polee_sampler_destroy(polee_sampler *s)
 
 polee_status polee_sampler_num_draws(polee_sampler *s, int64_t *ndraws)
 {
-    if (!s || !ndraws) return fail(s ? s->ctx : nullptr, POLEE_ERR_BAD_ARG, "polee_sampler_num_draws: null argument");
-    *ndraws = (int64_t)s->next_draw;
-    return POLEE_OK;
+    return entry(s, "polee_sampler_num_draws", [&](polee_ctx *ctx) -> polee_status {
+        if (!ndraws) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_num_draws: null argument");
+        *ndraws = (int64_t)s->next_draw;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_sampler_next(polee_sampler *s, int32_t count, int32_t count_mode, const float *z0_or_null, float *raw_or_null,
                                 float *props_or_null, double *counts_or_null)
 {
-    if (!s) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_sampler_next: null handle");
-    polee_ctx *ctx = s->ctx;
-    return guarded(ctx, "polee_sampler_next", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(s, "polee_sampler_next", [&](polee_ctx *ctx) -> polee_status {
         if (count < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_next: count < 1");
         if (count_mode != 0 && count_mode != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_next: count_mode must be 0 or 1");
         const int64_t n = s->n;
@@ -443,10 +439,7 @@ polee_status polee_sampler_next(polee_sampler *s, int32_t count, int32_t count_m
 
 polee_status polee_sampler_mean(polee_sampler *s, float *post_mean, double *est_counts_or_null, int32_t count_mode)
 {
-    if (!s) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_sampler_mean: null handle");
-    polee_ctx *ctx = s->ctx;
-    return guarded(ctx, "polee_sampler_mean", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return entry(s, "polee_sampler_mean", [&](polee_ctx *ctx) -> polee_status {
         if (!post_mean) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_mean: null output");
         if (count_mode != 0 && count_mode != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_mean: count_mode must be 0 or 1");
         if (s->next_draw == 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_mean: no draws yet");
@@ -479,9 +472,7 @@ polee_status polee_sampler_mean(polee_sampler *s, float *post_mean, double *est_
 polee_status polee_multinomial_counts(polee_ctx *ctx, const double *p, int32_t D, int64_t n, int64_t m, uint64_t seed,
                                       uint64_t first_draw, uint32_t *counts)
 {
-    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_multinomial_counts: null context");
-    return guarded(ctx, "polee_multinomial_counts", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_multinomial_counts", [&]() -> polee_status {
         if (!p || !counts) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_multinomial_counts: null argument");
         if (D < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_multinomial_counts: D < 1");
         if (n < 1 || n > MN_MAX_N) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_multinomial_counts: n = %lld outside [1, 2^30]", (long long)n);
@@ -533,9 +524,7 @@ polee_status polee_multinomial_counts(polee_ctx *ctx, const double *p, int32_t D
 
 polee_status polee_debug_binomial(polee_ctx *ctx, const int64_t *N, const double *p, int64_t count, uint64_t seed, int64_t *out)
 {
-    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_debug_binomial: null context");
-    return guarded(ctx, "polee_debug_binomial", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_debug_binomial", [&]() -> polee_status {
         if (!N || !p || !out || count < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_binomial: bad argument");
         for (int64_t i = 0; i < count; ++i)
             if (N[i] < 0 || N[i] >= ((int64_t)1 << 31) || !(p[i] >= 0.0 && p[i] <= 1.0))

@@ -577,9 +577,7 @@ void polee_tsne_default_opts(polee_tsne_opts *o)
 
 polee_status polee_tsne_create(polee_ctx *ctx, int32_t n, int32_t S, const polee_tsne_opts *opts, polee_tsne **out)
 {
-    if (!ctx) return fail(nullptr, POLEE_ERR_BAD_ARG, "polee_tsne_create: null context");
-    return guarded(ctx, "polee_tsne_create", [&]() -> polee_status {
-        POLEE_TRY(use_device(ctx));
+    return ctx_entry(ctx, "polee_tsne_create", [&]() -> polee_status {
         if (!out || n < 2 || S < 2) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_tsne_create: bad argument");
         polee_tsne_opts o;
         polee_tsne_default_opts(&o);

@@ -341,21 +341,10 @@ static polee_status vi_step_k(polee_vi *vi, bool apply, bool want_values, bool h
                            vi->d_efflens.p, vi->d_part_c.p, nch_f, (int64_t)n, gp, vi->d_gene_c.p);
     }
     // backward + update: the chunk-local double-double prefix of u * (g - efflen term), the chunks' offsets, the update
-    AdamConsts a;
-    // adam_learning_rate(step_num - 1) (likelihood-approximation.jl:107-110, 497)
-    a.lr = std::max(o.adam_min_learning_rate,
-                    o.adam_initial_learning_rate * std::exp(-o.adam_learning_rate_decay * (double)(step_num - 1)));
-    a.rm = o.adam_rm;
-    a.rv = o.adam_rv;
-    a.eps = o.adam_eps;
-    a.m_denom = 1 - std::pow(o.adam_rm, (double)step_num);
-    a.v_denom = 1 - std::pow(o.adam_rv, (double)step_num);
-    a.inv_m_denom = 1.0 / a.m_denom;
-    a.inv_v_denom = 1.0 / a.v_denom;
+    AdamConsts a = adam_schedule(o, step_num);
     a.max_mu = o.max_mu_step;
     a.max_omega = o.max_omega_step;
     a.max_alpha = o.max_alpha_step;
-    a.first = step_num == 1;
     // the update also draws the next iteration's samples (one launch and one pass over the parameters less),
     // unless the caller's noise table ends here
     const bool sample_next = apply && !(o.z0 && step_num + 1 > o.num_steps);
@@ -569,222 +558,222 @@ static thread_local bool g_vi_plain_order = false;
 polee_status polee_vi_create(polee_loglik *ll, polee_ptt *t, const float *efflens, const polee_vi_opts *opts,
                              polee_vi **out)
 {
-    if (!ll || !t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = ll->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (t->ctx != ctx) return fail(ctx, POLEE_ERR_BAD_ARG, "likelihood and tree belong to different contexts");
-    if (!out || !efflens) return fail(ctx, POLEE_ERR_BAD_ARG, "null argument");
-    if (t->T != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "the VI loop needs a single tree");
-    if ((int64_t)t->n != ll->n)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "tree has %d leaves but X has %lld transcripts", t->n, (long long)ll->n);
-    polee_vi_opts o;
-    if (opts)
-        o = *opts;
-    else
-        polee_vi_default_opts(&o);
-    if (o.num_mc_samples < 1 || o.num_mc_samples > PSELL_MAX_K)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "num_mc_samples must be in 1..8");
-    if (o.num_steps < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "num_steps must be >= 0");
-    // (the forward kernel takes log y and log(1 - y) of the clamped y without the special cases of a general log)
-    if (!(o.y_eps > 0.0 && o.y_eps < 0.5)) return fail(ctx, POLEE_ERR_BAD_ARG, "y_eps must lie in (0, 0.5) (LIKAP_Y_EPS = 1e-10)");
-    // gene_noninformative: members per gene and M = sum over genes of (members - 1)
-    std::vector<int> gene_k;
-    double gene_M = 0.0;
-    if (o.gene_of) {
-        if (!o.use_efflen_jacobian)
-            return fail(ctx, POLEE_ERR_BAD_ARG, "gene_of needs use_efflen_jacobian (gene_noninformative_prior! works on the "
-                                                "xls of the effective-length adjustment, likelihood.jl:114-159)");
-        int32_t ng = 0;
-        for (int64_t i = 0; i < ll->n; ++i) {
-            if (o.gene_of[i] < -1) return fail(ctx, POLEE_ERR_BAD_ARG, "gene_of[%lld] = %d", (long long)i, o.gene_of[i]);
-            ng = std::max(ng, o.gene_of[i] + 1);
+    return entry(ll, "polee_vi_create", [&](polee_ctx *ctx) -> polee_status {
+        if (!t) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_vi_create: null handle");
+        if (t->ctx != ctx) return fail(ctx, POLEE_ERR_BAD_ARG, "likelihood and tree belong to different contexts");
+        if (!out || !efflens) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_vi_create: null argument");
+        if (t->T != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "the VI loop needs a single tree");
+        if ((int64_t)t->n != ll->n)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "tree has %d leaves but X has %lld transcripts", t->n, (long long)ll->n);
+        polee_vi_opts o;
+        if (opts)
+            o = *opts;
+        else
+            polee_vi_default_opts(&o);
+        if (o.num_mc_samples < 1 || o.num_mc_samples > PSELL_MAX_K)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "num_mc_samples must be in 1..8");
+        if (o.num_steps < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "num_steps must be >= 0");
+        // (the forward kernel takes log y and log(1 - y) of the clamped y without the special cases of a general log)
+        if (!(o.y_eps > 0.0 && o.y_eps < 0.5)) return fail(ctx, POLEE_ERR_BAD_ARG, "y_eps must lie in (0, 0.5) (LIKAP_Y_EPS = 1e-10)");
+        // gene_noninformative: members per gene and M = sum over genes of (members - 1)
+        std::vector<int> gene_k;
+        double gene_M = 0.0;
+        if (o.gene_of) {
+            if (!o.use_efflen_jacobian)
+                return fail(ctx, POLEE_ERR_BAD_ARG, "gene_of needs use_efflen_jacobian (gene_noninformative_prior! works on the "
+                                                    "xls of the effective-length adjustment, likelihood.jl:114-159)");
+            int32_t ng = 0;
+            for (int64_t i = 0; i < ll->n; ++i) {
+                if (o.gene_of[i] < -1) return fail(ctx, POLEE_ERR_BAD_ARG, "gene_of[%lld] = %d", (long long)i, o.gene_of[i]);
+                ng = std::max(ng, o.gene_of[i] + 1);
+            }
+            gene_k.assign((size_t)ng, 0);
+            for (int64_t i = 0; i < ll->n; ++i)
+                if (o.gene_of[i] >= 0) ++gene_k[o.gene_of[i]];
+            for (int k : gene_k)
+                if (k > 1) gene_M += (double)(k - 1);
+            // (no gene information at all: the reference warns and switches the option off, :487-490)
         }
-        gene_k.assign((size_t)ng, 0);
-        for (int64_t i = 0; i < ll->n; ++i)
-            if (o.gene_of[i] >= 0) ++gene_k[o.gene_of[i]];
-        for (int k : gene_k)
-            if (k > 1) gene_M += (double)(k - 1);
-        // (no gene information at all: the reference warns and switches the option off, :487-490)
-    }
-    polee_vi *vi = new (std::nothrow) polee_vi();
-    if (!vi) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
-    vi->ctx = ctx;
-    vi->ll = ll;
-    vi->t = t;
-    ctx_retain(ctx);
-    loglik_retain(ll);
-    ptt_retain(t);
-    vi->o = o;
-    vi->n = t->n;
-    vi->K = o.num_mc_samples;
-    if (const char *e = getenv("POLEE_VI_DRAW_SPLIT")) {  // (A/B: "fwd,bwd" draws per workgroup; a value not offered = the default)
-        int f = 0, b = 0;
-        if (sscanf(e, "%d,%d", &f, &b) == 2) {
-            vi->dpw_fwd = draw_split_offered(vi->K, f) ? f : 0;
-            vi->dpw_bwd = draw_split_offered(vi->K, b) ? b : 0;
+        polee_vi *vi = new (std::nothrow) polee_vi();
+        if (!vi) return fail(ctx, POLEE_ERR_OOM, "out of host memory");
+        vi->ctx = ctx;
+        vi->ll = ll;
+        vi->t = t;
+        ctx_retain(ctx);
+        loglik_retain(ll);
+        ptt_retain(t);
+        vi->o = o;
+        vi->n = t->n;
+        vi->K = o.num_mc_samples;
+        if (const char *e = getenv("POLEE_VI_DRAW_SPLIT")) {  // (A/B: "fwd,bwd" draws per workgroup; a value not offered = the default)
+            int f = 0, b = 0;
+            if (sscanf(e, "%d,%d", &f, &b) == 2) {
+                vi->dpw_fwd = draw_split_offered(vi->K, f) ? f : 0;
+                vi->dpw_bwd = draw_split_offered(vi->K, b) ? b : 0;
+            }
         }
-    }
-    ll->profile = o.profile != 0;
-    ll->prof_every = o.profile > 1 ? o.profile : 1;
-    // (opts.deterministic belongs to THIS fit: applied around its likelihood passes, the handle's own setting restored)
-    const size_t n = vi->n, nm1 = std::max<size_t>(n - 1, 1), K = vi->K;
-    polee_status s = POLEE_OK;
-    auto A = [&](polee_status r) {
-        if (s == POLEE_OK) s = r;
-    };
-    A(vi->d_efflens.upload(ctx, efflens, n));
-    for (DevBuf<float> *b : {&vi->d_mu, &vi->d_omega, &vi->d_alpha, &vi->d_mm, &vi->d_vm, &vi->d_mo, &vi->d_vo,
-                             &vi->d_ma, &vi->d_va, &vi->d_mug, &vi->d_omg, &vi->d_alg})
-        A(b->alloc(ctx, nm1));
-    A(vi->d_x.alloc(ctx, n * K));
-    A(vi->d_zcur.alloc(ctx, nm1 * K));
-    A(vi->d_y32.alloc(ctx, nm1 * K));
-    A(vi->d_g.alloc(ctx, n * K));
-    A(vi->d_x_rows.alloc(ctx, n * K));
-    A(vi->d_ys.alloc(ctx, nm1));  // (initial values; the point optimisation's y)
-    if (g_vi_plain_order) A(vi->d_lyy.alloc(ctx, nm1 * 2));  // (the point optimisation's edge logs)
-    A(vi->d_u32.alloc(ctx, n * K));
-    if (g_vi_plain_order) A(vi->d_uleaf.alloc(ctx, n));  // (the point optimisation's f64 leaf u)
-    A(vi->d_C.alloc(ctx, (n + 1) * K));
-    {
-        const size_t nch = (size_t)std::max(scan_num_chunks(3 * (int64_t)n - 2), 1);
-        A(vi->d_part_c.alloc(ctx, nch * K));
-        A(vi->d_part_ladj.alloc(ctx, nch * K));
-        A(vi->d_csum.alloc(ctx, 2 * PSELL_MAX_K));
-    }
-    {   // backward tables (vi_bwd_local_kernel): internal nodes in DFS pre-order have non-decreasing lo
-        const PttPlan &pl = t->plans[0];
-        const int CH = K <= 6 ? bu_ch<6>() : bu_ch<8>();
-        vi->bu_ch = CH;
-        const int nch_bu = (int)ceil_div((int64_t)n, CH);
-        std::vector<int32_t> node_start((size_t)nch_bu + 1, (int32_t)(n - 1));
-        std::vector<uint32_t> need((n + 1 + 31) / 32 + 1, 0u);
-        bool monotone = true;
-        int c = 0;
-        for (size_t k = 0; k + 1 < n; ++k) {
-            if (k > 0 && pl.lo[k] < pl.lo[k - 1]) monotone = false;
-            for (; c <= pl.lo[k] / CH; ++c) node_start[(size_t)c] = (int32_t)k;
-            const int64_t end = std::min<int64_t>(((int64_t)pl.lo[k] / CH + 1) * CH, (int64_t)n);
-            if (pl.hi1[k] > end)
-                for (int32_t b : {pl.lo[k], pl.mid[k], pl.hi1[k]}) need[(size_t)b >> 5] |= 1u << (b & 31);
+        ll->profile = o.profile != 0;
+        ll->prof_every = o.profile > 1 ? o.profile : 1;
+        // (opts.deterministic belongs to THIS fit: applied around its likelihood passes, the handle's own setting restored)
+        const size_t n = vi->n, nm1 = std::max<size_t>(n - 1, 1), K = vi->K;
+        polee_status s = POLEE_OK;
+        auto A = [&](polee_status r) {
+            if (s == POLEE_OK) s = r;
+        };
+        A(vi->d_efflens.upload(ctx, efflens, n));
+        for (DevBuf<float> *b : {&vi->d_mu, &vi->d_omega, &vi->d_alpha, &vi->d_mm, &vi->d_vm, &vi->d_mo, &vi->d_vo,
+                                 &vi->d_ma, &vi->d_va, &vi->d_mug, &vi->d_omg, &vi->d_alg})
+            A(b->alloc(ctx, nm1));
+        A(vi->d_x.alloc(ctx, n * K));
+        A(vi->d_zcur.alloc(ctx, nm1 * K));
+        A(vi->d_y32.alloc(ctx, nm1 * K));
+        A(vi->d_g.alloc(ctx, n * K));
+        A(vi->d_x_rows.alloc(ctx, n * K));
+        A(vi->d_ys.alloc(ctx, nm1));  // (initial values; the point optimisation's y)
+        if (g_vi_plain_order) A(vi->d_lyy.alloc(ctx, nm1 * 2));  // (the point optimisation's edge logs)
+        A(vi->d_u32.alloc(ctx, n * K));
+        if (g_vi_plain_order) A(vi->d_uleaf.alloc(ctx, n));  // (the point optimisation's f64 leaf u)
+        A(vi->d_C.alloc(ctx, (n + 1) * K));
+        {
+            const size_t nch = (size_t)std::max(scan_num_chunks(3 * (int64_t)n - 2), 1);
+            A(vi->d_part_c.alloc(ctx, nch * K));
+            A(vi->d_part_ladj.alloc(ctx, nch * K));
+            A(vi->d_csum.alloc(ctx, 2 * PSELL_MAX_K));
         }
-        if (!monotone) A(fail(ctx, POLEE_ERR_BAD_ARG, "tree plan: internal nodes are not in DFS pre-order"));
-        A(vi->d_node_start.upload(ctx, node_start));
-        A(vi->d_need.upload(ctx, need));
-        A(vi->d_chunk_bu.alloc(ctx, ((size_t)nch_bu + 1) * K));
-        A(vi->d_H.alloc(ctx, 2 * K * nm1));
-        // (row n of C is exported by the kernel when a node needs it, unless n is a multiple of the chunk size: then it is the
-        // zero first row of a chunk past the end)
-        if (s == POLEE_OK && hipMemsetAsync(vi->d_C.p, 0, sizeof(dd) * (n + 1) * K, ctx->stream) != hipSuccess)
-            A(fail(ctx, POLEE_ERR_HIP, "memset failed"));
-    }
-    {   // The forward scan's chunk offsets from the tree (vi_fwd_apply_kernel): for every chunk of the Euler tour the ENTER
-        // entries still open at its first entry = the path from the root to that point.  One walk over the tour with a
-        // stack; kept when the lists stay small (a caterpillar tree of 200 000 leaves would need n^2 / 1024 entries: the
-        // reduce launch stays for such trees).
-        static const bool no_open = getenv("POLEE_VI_NO_OPEN_LISTS") != nullptr;  // (A/B)
-        const std::vector<uint32_t> &code = t->plans[0].tour_code;
-        const int64_t TL = t->TL;
-        const size_t limit = (size_t)8 << 20;
-        std::vector<uint32_t> optr, ocode;
-        const bool ok = !no_open && t->T == 1 && (int64_t)code.size() == TL && build_open_lists(code.data(), TL, FWD_CHUNK, limit, optr, ocode);
-        if (ok) {
-            if (ocode.empty()) ocode.push_back(4u | TOUR_LEAF);  // (never read)
-            A(vi->d_open_ptr.upload(ctx, optr));
-            A(vi->d_open_code.upload(ctx, ocode));
+        {   // backward tables (vi_bwd_local_kernel): internal nodes in DFS pre-order have non-decreasing lo
+            const PttPlan &pl = t->plans[0];
+            const int CH = K <= 6 ? bu_ch<6>() : bu_ch<8>();
+            vi->bu_ch = CH;
+            const int nch_bu = (int)ceil_div((int64_t)n, CH);
+            std::vector<int32_t> node_start((size_t)nch_bu + 1, (int32_t)(n - 1));
+            std::vector<uint32_t> need((n + 1 + 31) / 32 + 1, 0u);
+            bool monotone = true;
+            int c = 0;
+            for (size_t k = 0; k + 1 < n; ++k) {
+                if (k > 0 && pl.lo[k] < pl.lo[k - 1]) monotone = false;
+                for (; c <= pl.lo[k] / CH; ++c) node_start[(size_t)c] = (int32_t)k;
+                const int64_t end = std::min<int64_t>(((int64_t)pl.lo[k] / CH + 1) * CH, (int64_t)n);
+                if (pl.hi1[k] > end)
+                    for (int32_t b : {pl.lo[k], pl.mid[k], pl.hi1[k]}) need[(size_t)b >> 5] |= 1u << (b & 31);
+            }
+            if (!monotone) A(fail(ctx, POLEE_ERR_BAD_ARG, "tree plan: internal nodes are not in DFS pre-order"));
+            A(vi->d_node_start.upload(ctx, node_start));
+            A(vi->d_need.upload(ctx, need));
+            A(vi->d_chunk_bu.alloc(ctx, ((size_t)nch_bu + 1) * K));
+            A(vi->d_H.alloc(ctx, 2 * K * nm1));
+            // (row n of C is exported by the kernel when a node needs it, unless n is a multiple of the chunk size: then it is the
+            // zero first row of a chunk past the end)
+            if (s == POLEE_OK && hipMemsetAsync(vi->d_C.p, 0, sizeof(dd) * (n + 1) * K, ctx->stream) != hipSuccess)
+                A(fail(ctx, POLEE_ERR_HIP, "memset failed"));
         }
-    }
-    A(vi->d_ygrad.alloc(ctx, nm1 * K));
-    A(vi->d_xgrad_rows.alloc(ctx, n * K));
-    A(vi->d_lp.alloc(ctx, PSELL_MAX_K));
-    A(vi->d_ladj_el.alloc(ctx, PSELL_MAX_K * 2));
-    A(vi->d_rows.alloc(ctx, PSELL_MAX_K * 2));
-    A(vi->d_flag.alloc(ctx, 1));
-    if (!gene_k.empty()) {
-        vi->num_genes = (int32_t)gene_k.size();
-        vi->gene_M = gene_M;
-        A(vi->d_gene_of.upload(ctx, o.gene_of, n));
-        A(vi->d_gene_k.upload(ctx, gene_k));
-        A(vi->d_gene_c.alloc(ctx, gene_k.size() * K));
-    }
-    // Leaf-order mode: the transcripts renumbered by leaf position for this fit (polee_vi::leaf_order)
-    static const bool no_leaf_env = getenv("POLEE_VI_NO_LEAF_ORDER") != nullptr;  // (A/B)
-    if (!no_leaf_env && !g_vi_plain_order && n > 1 && t->plans.size() == 1 && t->plans[0].tid_pos.size() == n) {
-        const PttPlan &pl = t->plans[0];
-        std::vector<uint32_t> index_of(n);
-        std::vector<float> eff_leaf(n);
-        for (size_t j = 0; j < n; ++j) index_of[j] = (uint32_t)pl.tid_pos[j];
-        for (size_t pos = 0; pos < n; ++pos) eff_leaf[pos] = efflens[pl.leaf_tid[pos]];
-        A(vi->d_index_of.upload(ctx, index_of));
-        A(vi->d_efflens.upload(ctx, eff_leaf));
+        {   // The forward scan's chunk offsets from the tree (vi_fwd_apply_kernel): for every chunk of the Euler tour the ENTER
+            // entries still open at its first entry = the path from the root to that point.  One walk over the tour with a
+            // stack; kept when the lists stay small (a caterpillar tree of 200 000 leaves would need n^2 / 1024 entries: the
+            // reduce launch stays for such trees).
+            static const bool no_open = getenv("POLEE_VI_NO_OPEN_LISTS") != nullptr;  // (A/B)
+            const std::vector<uint32_t> &code = t->plans[0].tour_code;
+            const int64_t TL = t->TL;
+            const size_t limit = (size_t)8 << 20;
+            std::vector<uint32_t> optr, ocode;
+            const bool ok = !no_open && t->T == 1 && (int64_t)code.size() == TL && build_open_lists(code.data(), TL, FWD_CHUNK, limit, optr, ocode);
+            if (ok) {
+                if (ocode.empty()) ocode.push_back(4u | TOUR_LEAF);  // (never read)
+                A(vi->d_open_ptr.upload(ctx, optr));
+                A(vi->d_open_code.upload(ctx, ocode));
+            }
+        }
+        A(vi->d_ygrad.alloc(ctx, nm1 * K));
+        A(vi->d_xgrad_rows.alloc(ctx, n * K));
+        A(vi->d_lp.alloc(ctx, PSELL_MAX_K));
+        A(vi->d_ladj_el.alloc(ctx, PSELL_MAX_K * 2));
+        A(vi->d_rows.alloc(ctx, PSELL_MAX_K * 2));
+        A(vi->d_flag.alloc(ctx, 1));
         if (!gene_k.empty()) {
-            std::vector<int32_t> gene_leaf(n);
-            for (size_t pos = 0; pos < n; ++pos) gene_leaf[pos] = o.gene_of[pl.leaf_tid[pos]];
-            A(vi->d_gene_of.upload(ctx, gene_leaf));
+            vi->num_genes = (int32_t)gene_k.size();
+            vi->gene_M = gene_M;
+            A(vi->d_gene_of.upload(ctx, o.gene_of, n));
+            A(vi->d_gene_k.upload(ctx, gene_k));
+            A(vi->d_gene_c.alloc(ctx, gene_k.size() * K));
         }
-        A(vi->d_dict_leaf.alloc(ctx, (size_t)std::max<int64_t>(ll->dict_len, 1)));
-        if (ll->csr_nnz > 0) A(vi->d_csr_col_leaf.alloc(ctx, (size_t)ll->csr_nnz));
-        if (ll->has_singles) A(vi->d_single_leaf.alloc(ctx, n));
-        if (s == POLEE_OK) {
-            hipStream_t st0 = ctx->stream;
-            if (ll->dict_len > 0)
-                hipLaunchKernelGGL(remap_u32_kernel, dim3((unsigned)ceil_div(ll->dict_len, 256)), dim3(256), 0, st0,
-                                   (const uint32_t *)ll->d_dict.p, (const uint32_t *)vi->d_index_of.p, ll->dict_len, vi->d_dict_leaf.p);
-            if (ll->csr_nnz > 0)
-                hipLaunchKernelGGL(remap_u32_kernel, dim3((unsigned)ceil_div(ll->csr_nnz, 256)), dim3(256), 0, st0,
-                                   (const uint32_t *)ll->d_csr_col.p, (const uint32_t *)vi->d_index_of.p, ll->csr_nnz, vi->d_csr_col_leaf.p);
-            if (ll->has_singles)
-                hipLaunchKernelGGL(gather_kernel<float>, dim3((unsigned)ceil_div((int64_t)n, 256)), dim3(256), 0, st0,
-                                   (const float *)ll->d_single_cnt.p, (const int32_t *)t->d_leaf_tid.p, (int64_t)n, vi->d_single_leaf.p);
-            if (hipGetLastError() != hipSuccess) A(fail(ctx, POLEE_ERR_HIP, "leaf-order tables: kernel launch failed"));
-            vi->leaf_order = true;
-            // (the singles' cnt / x goes into g in the forward kernel: one launch and one pass over g less per iteration)
-            vi->remap = LoglikRemap{vi->d_dict_leaf.p, ll->has_singles ? vi->d_single_leaf.p : nullptr,
-                                    ll->csr_nnz > 0 ? vi->d_csr_col_leaf.p : nullptr, vi->d_index_of.p, ll->has_singles};
+        // Leaf-order mode: the transcripts renumbered by leaf position for this fit (polee_vi::leaf_order)
+        static const bool no_leaf_env = getenv("POLEE_VI_NO_LEAF_ORDER") != nullptr;  // (A/B)
+        if (!no_leaf_env && !g_vi_plain_order && n > 1 && t->plans.size() == 1 && t->plans[0].tid_pos.size() == n) {
+            const PttPlan &pl = t->plans[0];
+            std::vector<uint32_t> index_of(n);
+            std::vector<float> eff_leaf(n);
+            for (size_t j = 0; j < n; ++j) index_of[j] = (uint32_t)pl.tid_pos[j];
+            for (size_t pos = 0; pos < n; ++pos) eff_leaf[pos] = efflens[pl.leaf_tid[pos]];
+            A(vi->d_index_of.upload(ctx, index_of));
+            A(vi->d_efflens.upload(ctx, eff_leaf));
+            if (!gene_k.empty()) {
+                std::vector<int32_t> gene_leaf(n);
+                for (size_t pos = 0; pos < n; ++pos) gene_leaf[pos] = o.gene_of[pl.leaf_tid[pos]];
+                A(vi->d_gene_of.upload(ctx, gene_leaf));
+            }
+            A(vi->d_dict_leaf.alloc(ctx, (size_t)std::max<int64_t>(ll->dict_len, 1)));
+            if (ll->csr_nnz > 0) A(vi->d_csr_col_leaf.alloc(ctx, (size_t)ll->csr_nnz));
+            if (ll->has_singles) A(vi->d_single_leaf.alloc(ctx, n));
+            if (s == POLEE_OK) {
+                hipStream_t st0 = ctx->stream;
+                if (ll->dict_len > 0)
+                    hipLaunchKernelGGL(remap_u32_kernel, dim3((unsigned)ceil_div(ll->dict_len, 256)), dim3(256), 0, st0,
+                                       (const uint32_t *)ll->d_dict.p, (const uint32_t *)vi->d_index_of.p, ll->dict_len, vi->d_dict_leaf.p);
+                if (ll->csr_nnz > 0)
+                    hipLaunchKernelGGL(remap_u32_kernel, dim3((unsigned)ceil_div(ll->csr_nnz, 256)), dim3(256), 0, st0,
+                                       (const uint32_t *)ll->d_csr_col.p, (const uint32_t *)vi->d_index_of.p, ll->csr_nnz, vi->d_csr_col_leaf.p);
+                if (ll->has_singles)
+                    hipLaunchKernelGGL(gather_kernel<float>, dim3((unsigned)ceil_div((int64_t)n, 256)), dim3(256), 0, st0,
+                                       (const float *)ll->d_single_cnt.p, (const int32_t *)t->d_leaf_tid.p, (int64_t)n, vi->d_single_leaf.p);
+                if (hipGetLastError() != hipSuccess) A(fail(ctx, POLEE_ERR_HIP, "leaf-order tables: kernel launch failed"));
+                vi->leaf_order = true;
+                // (the singles' cnt / x goes into g in the forward kernel: one launch and one pass over g less per iteration)
+                vi->remap = LoglikRemap{vi->d_dict_leaf.p, ll->has_singles ? vi->d_single_leaf.p : nullptr,
+                                        ll->csr_nnz > 0 ? vi->d_csr_col_leaf.p : nullptr, vi->d_index_of.p, ll->has_singles};
+            }
         }
-    }
-    vi->o.gene_of = nullptr;  // (host memory is borrowed for the call only)
-    vi->trace_cap = o.gradonly ? 0 : std::max(o.num_steps, 1);
-    if (!o.gradonly) {
-        A(vi->d_elbo.alloc(ctx, vi->trace_cap));
-        A(vi->d_lptrace.alloc(ctx, vi->trace_cap));
-    }
-    if (o.z0 && o.num_steps > 0) A(vi->d_z0.upload(ctx, o.z0, (size_t)o.num_steps * K * (n - 1)));
-    vi->o.z0 = o.z0;  // only its null-ness is used from here on
-    A(t->reserve((int32_t)K));
-    if (s != POLEE_OK) {
-        polee_vi_destroy(vi);
-        return s;
-    }
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMemsetAsync(vi->d_flag.p, 0, sizeof(int), st);
-    if (e == hipSuccess) e = hipMemsetAsync(vi->d_rows.p, 0, sizeof(double) * PSELL_MAX_K * 2, st);
-    for (DevBuf<float> *b : {&vi->d_mm, &vi->d_vm, &vi->d_mo, &vi->d_vo, &vi->d_ma, &vi->d_va})
-        if (e == hipSuccess) e = hipMemsetAsync(b->p, 0, sizeof(float) * nm1, st);
-    if (e != hipSuccess) {
-        polee_vi_destroy(vi);
-        return fail(ctx, POLEE_ERR_HIP, "memset failed: %s", hipGetErrorString(e));
-    }
-    // initial values (likelihood-approximation.jl:451-456): mu = logit(inverse_transform!(fill(1/n)))
-    if (n > 1) {
-        UniformLeafLoad load{(double)(1.0f / (float)n)};
-        LeafPrefixEmit emit{(int32_t)n, t->d_C.p};
-        e = run_scan_partial<dd>(st, 1, n, t->d_chunk.p, nullptr, load, emit);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(vi_inverse_nodes_kernel, dim3((unsigned)ceil_div(n - 1, 256)), dim3(256), 0, st,
-                               t->view(), t->d_C.p, vi->d_ys.p);
-            hipLaunchKernelGGL(vi_init_mu_kernel, dim3((unsigned)ceil_div(n - 1, 256)), dim3(256), 0, st, vi->d_ys.p,
-                               (int64_t)n - 1, vi->d_mu.p, vi->d_omega.p, vi->d_alpha.p);
-            e = hipGetLastError();
+        vi->o.gene_of = nullptr;  // (host memory is borrowed for the call only)
+        vi->trace_cap = o.gradonly ? 0 : std::max(o.num_steps, 1);
+        if (!o.gradonly) {
+            A(vi->d_elbo.alloc(ctx, vi->trace_cap));
+            A(vi->d_lptrace.alloc(ctx, vi->trace_cap));
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (o.z0 && o.num_steps > 0) A(vi->d_z0.upload(ctx, o.z0, (size_t)o.num_steps * K * (n - 1)));
+        vi->o.z0 = o.z0;  // only its null-ness is used from here on
+        A(t->reserve((int32_t)K));
+        if (s != POLEE_OK) {
+            polee_vi_destroy(vi);
+            return s;
+        }
+        hipStream_t st = ctx->stream;
+        hipError_t e = hipMemsetAsync(vi->d_flag.p, 0, sizeof(int), st);
+        if (e == hipSuccess) e = hipMemsetAsync(vi->d_rows.p, 0, sizeof(double) * PSELL_MAX_K * 2, st);
+        for (DevBuf<float> *b : {&vi->d_mm, &vi->d_vm, &vi->d_mo, &vi->d_vo, &vi->d_ma, &vi->d_va})
+            if (e == hipSuccess) e = hipMemsetAsync(b->p, 0, sizeof(float) * nm1, st);
         if (e != hipSuccess) {
             polee_vi_destroy(vi);
-            return fail(ctx, POLEE_ERR_HIP, "initialisation failed: %s", hipGetErrorString(e));
+            return fail(ctx, POLEE_ERR_HIP, "memset failed: %s", hipGetErrorString(e));
         }
-    }
-    *out = vi;
-    return POLEE_OK;
+        // initial values (likelihood-approximation.jl:451-456): mu = logit(inverse_transform!(fill(1/n)))
+        if (n > 1) {
+            UniformLeafLoad load{(double)(1.0f / (float)n)};
+            LeafPrefixEmit emit{(int32_t)n, t->d_C.p};
+            e = run_scan_partial<dd>(st, 1, n, t->d_chunk.p, nullptr, load, emit);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(vi_inverse_nodes_kernel, dim3((unsigned)ceil_div(n - 1, 256)), dim3(256), 0, st,
+                                   t->view(), t->d_C.p, vi->d_ys.p);
+                hipLaunchKernelGGL(vi_init_mu_kernel, dim3((unsigned)ceil_div(n - 1, 256)), dim3(256), 0, st, vi->d_ys.p,
+                                   (int64_t)n - 1, vi->d_mu.p, vi->d_omega.p, vi->d_alpha.p);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) {
+                polee_vi_destroy(vi);
+                return fail(ctx, POLEE_ERR_HIP, "initialisation failed: %s", hipGetErrorString(e));
+            }
+        }
+        *out = vi;
+        return POLEE_OK;
+    });
 }
 
 void polee_vi_destroy(polee_vi *vi)
@@ -807,334 +796,321 @@ void polee_vi_destroy(polee_vi *vi)
 
 polee_status polee_vi_set_comm(polee_vi *vi, polee_comm *comm)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    if (comm && comm->ctx != vi->ctx)
-        return fail(vi->ctx, POLEE_ERR_BAD_ARG, "communicator and fit belong to different contexts");
-    if (comm) ++comm->refs;
-    polee_comm_destroy(vi->comm);
-    vi->comm = comm;
-    return POLEE_OK;
+    return entry(vi, "polee_vi_set_comm", [&](polee_ctx *ctx) -> polee_status {
+        if (comm && comm->ctx != ctx)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "communicator and fit belong to different contexts");
+        if (comm) ++comm->refs;
+        polee_comm_destroy(vi->comm);
+        vi->comm = comm;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_run(polee_vi *vi, int32_t nsteps)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    POLEE_TRY(use_device(vi->ctx));
-    vi->ll->profile = vi->o.profile != 0;
-    vi->ll->prof_every = vi->o.profile > 1 ? vi->o.profile : 1;
-    for (int32_t i = 0; i < nsteps; ++i) POLEE_TRY(vi->one_step(true, !vi->o.gradonly, false));
-    return POLEE_OK;
+    return entry(vi, "polee_vi_run", [&](polee_ctx *ctx) -> polee_status {
+        vi->ll->profile = vi->o.profile != 0;
+        vi->ll->prof_every = vi->o.profile > 1 ? vi->o.profile : 1;
+        for (int32_t i = 0; i < nsteps; ++i) POLEE_TRY(vi->one_step(true, !vi->o.gradonly, false));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_sync(polee_vi *vi)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = vi->ctx;
-    POLEE_TRY(use_device(ctx));
-    int flag = 0;
-    POLEE_TRY(vi->d_flag.download(ctx, &flag, 1));
-    if (vi->ll->profile) POLEE_TRY(vi->ll->profile_collect());
-    if (flag != 0)
-        return fail(ctx, POLEE_ERR_NONFINITE, "non-finite gradient at VI step %d (likelihood-approximation.jl:559)",
-                    flag);
-    return POLEE_OK;
+    return entry(vi, "polee_vi_sync", [&](polee_ctx *ctx) -> polee_status {
+        int flag = 0;
+        POLEE_TRY(vi->d_flag.download(ctx, &flag, 1));
+        if (vi->ll->profile) POLEE_TRY(vi->ll->profile_collect());
+        if (flag != 0)
+            return fail(ctx, POLEE_ERR_NONFINITE, "non-finite gradient at VI step %d (likelihood-approximation.jl:559)",
+                        flag);
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_get_params(polee_vi *vi, float *mu, float *omega, float *alpha)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = vi->ctx;
-    POLEE_TRY(use_device(ctx));
-    const size_t nm1 = vi->n - 1;
-    if (mu) POLEE_TRY(vi->d_mu.download(ctx, mu, nm1));
-    if (omega) POLEE_TRY(vi->d_omega.download(ctx, omega, nm1));
-    if (alpha) POLEE_TRY(vi->d_alpha.download(ctx, alpha, nm1));
-    return POLEE_OK;
+    return entry(vi, "polee_vi_get_params", [&](polee_ctx *ctx) -> polee_status {
+        const size_t nm1 = vi->n - 1;
+        if (mu) POLEE_TRY(vi->d_mu.download(ctx, mu, nm1));
+        if (omega) POLEE_TRY(vi->d_omega.download(ctx, omega, nm1));
+        if (alpha) POLEE_TRY(vi->d_alpha.download(ctx, alpha, nm1));
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_set_params(polee_vi *vi, const float *mu, const float *omega, const float *alpha)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = vi->ctx;
-    POLEE_TRY(use_device(ctx));
-    const size_t nm1 = vi->n - 1;
-    if (mu) POLEE_TRY(vi->d_mu.upload(ctx, mu, nm1));
-    if (omega) POLEE_TRY(vi->d_omega.upload(ctx, omega, nm1));
-    if (alpha) POLEE_TRY(vi->d_alpha.upload(ctx, alpha, nm1));
-    vi->ahead_step = 0;  // draws made from the old parameters are stale
-    return POLEE_OK;
+    return entry(vi, "polee_vi_set_params", [&](polee_ctx *ctx) -> polee_status {
+        const size_t nm1 = vi->n - 1;
+        if (mu) POLEE_TRY(vi->d_mu.upload(ctx, mu, nm1));
+        if (omega) POLEE_TRY(vi->d_omega.upload(ctx, omega, nm1));
+        if (alpha) POLEE_TRY(vi->d_alpha.upload(ctx, alpha, nm1));
+        vi->ahead_step = 0;  // draws made from the old parameters are stale
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_get_stats(polee_vi *vi, polee_vi_stats *stats)
 {
-    if (!vi || !stats) return fail(nullptr, POLEE_ERR_BAD_ARG, "null argument");
-    polee_ctx *ctx = vi->ctx;
-    POLEE_TRY(use_device(ctx));
-    memset(stats, 0, sizeof(*stats));
-    stats->steps_done = vi->step;
-    int flag = 0;
-    POLEE_TRY(vi->d_flag.download(ctx, &flag, 1));
-    stats->nonfinite_step = flag;
-    if (vi->ll->profile) POLEE_TRY(vi->ll->profile_collect());
-    stats->loglik_kernel_launches = vi->ll->prof_launches;
-    stats->loglik_kernel_ms_avg = vi->ll->prof_launches ? vi->ll->prof_ms_total / vi->ll->prof_launches : 0.0;
-    stats->loglik_pass_ms_avg = vi->ll->prof_launches ? vi->ll->prof_pass_ms_total / vi->ll->prof_launches : 0.0;
-    if (!vi->o.gradonly && vi->step > 0 && vi->step <= vi->trace_cap) {
-        POLEE_HIP_TRY(ctx, hipMemcpyAsync(&stats->last_elbo, vi->d_elbo.p + (vi->step - 1), sizeof(double),
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        POLEE_HIP_TRY(ctx, hipMemcpyAsync(&stats->last_lp_mean, vi->d_lptrace.p + (vi->step - 1), sizeof(double),
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return POLEE_OK;
+    return entry(vi, "polee_vi_get_stats", [&](polee_ctx *ctx) -> polee_status {
+        if (!stats) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_vi_get_stats: null argument");
+        memset(stats, 0, sizeof(*stats));
+        stats->steps_done = vi->step;
+        int flag = 0;
+        POLEE_TRY(vi->d_flag.download(ctx, &flag, 1));
+        stats->nonfinite_step = flag;
+        if (vi->ll->profile) POLEE_TRY(vi->ll->profile_collect());
+        stats->loglik_kernel_launches = vi->ll->prof_launches;
+        stats->loglik_kernel_ms_avg = vi->ll->prof_launches ? vi->ll->prof_ms_total / vi->ll->prof_launches : 0.0;
+        stats->loglik_pass_ms_avg = vi->ll->prof_launches ? vi->ll->prof_pass_ms_total / vi->ll->prof_launches : 0.0;
+        if (!vi->o.gradonly && vi->step > 0 && vi->step <= vi->trace_cap) {
+            POLEE_HIP_TRY(ctx, hipMemcpyAsync(&stats->last_elbo, vi->d_elbo.p + (vi->step - 1), sizeof(double),
+                                              hipMemcpyDeviceToHost, ctx->stream));
+            POLEE_HIP_TRY(ctx, hipMemcpyAsync(&stats->last_lp_mean, vi->d_lptrace.p + (vi->step - 1), sizeof(double),
+                                              hipMemcpyDeviceToHost, ctx->stream));
+            POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_get_trace(polee_vi *vi, double *elbo, double *lp_mean)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = vi->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (vi->o.gradonly) return fail(ctx, POLEE_ERR_BAD_ARG, "no trace is recorded in gradonly mode");
-    const size_t cnt = std::min(vi->step, vi->trace_cap);
-    if (elbo) POLEE_TRY(vi->d_elbo.download(ctx, elbo, cnt));
-    if (lp_mean) POLEE_TRY(vi->d_lptrace.download(ctx, lp_mean, cnt));
-    return POLEE_OK;
+    return entry(vi, "polee_vi_get_trace", [&](polee_ctx *ctx) -> polee_status {
+        if (vi->o.gradonly) return fail(ctx, POLEE_ERR_BAD_ARG, "no trace is recorded in gradonly mode");
+        const size_t cnt = std::min(vi->step, vi->trace_cap);
+        if (elbo) POLEE_TRY(vi->d_elbo.download(ctx, elbo, cnt));
+        if (lp_mean) POLEE_TRY(vi->d_lptrace.download(ctx, lp_mean, cnt));
+        return POLEE_OK;
+    });
 }
 
 #ifdef POLEE_VI_STAMPS
 // diagnostic build only: the tree kernels' phase stamps of their last launches, [4][2048][8] (vi_fused.hpp)
 polee_status polee_debug_vi_stamps(unsigned long long *out)
 {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(polee::g_vi_stamps), sizeof(unsigned long long) * 4 * 2048 * 8) == hipSuccess ? POLEE_OK : POLEE_ERR_HIP;
+    return host_entry("polee_debug_vi_stamps", [&]() -> polee_status {
+        return hipMemcpyFromSymbol(out, HIP_SYMBOL(polee::g_vi_stamps), sizeof(unsigned long long) * 4 * 2048 * 8) == hipSuccess ? POLEE_OK : POLEE_ERR_HIP;
+    });
 }
 #endif
 
 polee_status polee_vi_debug_set_draw_split(polee_vi *vi, int32_t dpw_fwd, int32_t dpw_bwd, int32_t dpw_update)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    for (int32_t dpw : {dpw_fwd, dpw_bwd})
-        if (dpw != 0 && !draw_split_offered(vi->K, dpw))
-            return fail(vi->ctx, POLEE_ERR_BAD_ARG, "draw split %d of %d draws is not instantiated (0, %d, or 3, 2, 1 below it)", dpw, vi->K, vi->K);
-    // (the update kernel has no split: a lane per node and draw was slower at every DPW and is not kept, EXPERIMENTS.md)
-    if (dpw_update != 0 && dpw_update != vi->K)
-        return fail(vi->ctx, POLEE_ERR_BAD_ARG, "the update kernel runs all %d draws of a node on one lane: dpw_update must be 0 or %d", vi->K, vi->K);
-    vi->dpw_fwd = dpw_fwd;
-    vi->dpw_bwd = dpw_bwd;
-    return POLEE_OK;
+    return entry(vi, "polee_vi_debug_set_draw_split", [&](polee_ctx *ctx) -> polee_status {
+        for (int32_t dpw : {dpw_fwd, dpw_bwd})
+            if (dpw != 0 && !draw_split_offered(vi->K, dpw))
+                return fail(ctx, POLEE_ERR_BAD_ARG, "draw split %d of %d draws is not instantiated (0, %d, or 3, 2, 1 below it)", dpw, vi->K, vi->K);
+        // (the update kernel has no split: a lane per node and draw was slower at every DPW and is not kept, EXPERIMENTS.md)
+        if (dpw_update != 0 && dpw_update != vi->K)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "the update kernel runs all %d draws of a node on one lane: dpw_update must be 0 or %d", vi->K, vi->K);
+        vi->dpw_fwd = dpw_fwd;
+        vi->dpw_bwd = dpw_bwd;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_export_noise(polee_vi *vi, int32_t step, float *z0)
 {
-    if (!vi || !z0 || step < 1) return fail(nullptr, POLEE_ERR_BAD_ARG, "bad argument");
-    polee_ctx *ctx = vi->ctx;
-    POLEE_TRY(use_device(ctx));
-    const int64_t nm1 = vi->n - 1;
-    if (nm1 < 1) return POLEE_OK;
-    if (vi->o.z0 && step > vi->o.num_steps) return fail(ctx, POLEE_ERR_BAD_ARG, "step beyond the supplied noise");
-    DevBuf<float> tmp;
-    POLEE_TRY(tmp.alloc(ctx, (size_t)vi->K * nm1));
-    hipLaunchKernelGGL(export_noise_kernel, dim3((unsigned)ceil_div(nm1, 256), vi->K), dim3(256), 0, ctx->stream,
-                       vi->noise(), step, tmp.p);
-    POLEE_KERNEL_CHECK(ctx);
-    return tmp.download(ctx, z0, (size_t)vi->K * nm1);
+    return entry(vi, "polee_vi_export_noise", [&](polee_ctx *ctx) -> polee_status {
+        if (!z0 || step < 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_vi_export_noise: bad argument");
+        const int64_t nm1 = vi->n - 1;
+        if (nm1 < 1) return POLEE_OK;
+        if (vi->o.z0 && step > vi->o.num_steps) return fail(ctx, POLEE_ERR_BAD_ARG, "step beyond the supplied noise");
+        DevBuf<float> tmp;
+        POLEE_TRY(tmp.alloc(ctx, (size_t)vi->K * nm1));
+        hipLaunchKernelGGL(export_noise_kernel, dim3((unsigned)ceil_div(nm1, 256), vi->K), dim3(256), 0, ctx->stream,
+                           vi->noise(), step, tmp.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return tmp.download(ctx, z0, (size_t)vi->K * nm1);
+    });
 }
 
 polee_status polee_vi_eval_gradients(polee_vi *vi, float *xs, double *x_grad, double *y_grad, float *mu_grad,
                                      float *omega_grad, float *alpha_grad, double *lp, double *ladj)
 {
-    if (!vi) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = vi->ctx;
-    POLEE_TRY(use_device(ctx));
-    const size_t n = vi->n, nm1 = n - 1, K = vi->K;
-    POLEE_TRY(vi->one_step(false, true, true));
-    if (xs) {
-        hipLaunchKernelGGL(aos_to_rows_f32_kernel, dim3((unsigned)ceil_div(n * K, 256)), dim3(256), 0, ctx->stream,
-                           vi->d_x.p, (int)K, (int64_t)n, vi->d_x_rows.p, vi->leaf_order ? (const uint32_t *)vi->d_index_of.p : nullptr);
-        POLEE_KERNEL_CHECK(ctx);
-        POLEE_TRY(vi->d_x_rows.download(ctx, xs, n * K));
-    }
-    if (x_grad) POLEE_TRY(vi->d_xgrad_rows.download(ctx, x_grad, n * K));
-    if (y_grad) POLEE_TRY(vi->d_ygrad.download(ctx, y_grad, nm1 * K));
-    if (mu_grad) POLEE_TRY(vi->d_mug.download(ctx, mu_grad, nm1));
-    if (omega_grad) POLEE_TRY(vi->d_omg.download(ctx, omega_grad, nm1));
-    if (alpha_grad) POLEE_TRY(vi->d_alg.download(ctx, alpha_grad, nm1));
-    if (lp) POLEE_TRY(vi->d_lp.download(ctx, lp, K));
-    if (ladj) {
-        std::vector<double> el(K * 2), rs(K * 2);
-        POLEE_TRY(vi->d_ladj_el.download(ctx, el.data(), K * 2));
-        POLEE_TRY(vi->d_rows.download(ctx, rs.data(), K * 2));
-        for (size_t d = 0; d < K; ++d) ladj[d] = el[d * 2] + el[d * 2 + 1] + rs[d * 2 + 1];
-    }
-    return POLEE_OK;
+    return entry(vi, "polee_vi_eval_gradients", [&](polee_ctx *ctx) -> polee_status {
+        const size_t n = vi->n, nm1 = n - 1, K = vi->K;
+        POLEE_TRY(vi->one_step(false, true, true));
+        if (xs) {
+            hipLaunchKernelGGL(aos_to_rows_f32_kernel, dim3((unsigned)ceil_div(n * K, 256)), dim3(256), 0, ctx->stream,
+                               vi->d_x.p, (int)K, (int64_t)n, vi->d_x_rows.p, vi->leaf_order ? (const uint32_t *)vi->d_index_of.p : nullptr);
+            POLEE_KERNEL_CHECK(ctx);
+            POLEE_TRY(vi->d_x_rows.download(ctx, xs, n * K));
+        }
+        if (x_grad) POLEE_TRY(vi->d_xgrad_rows.download(ctx, x_grad, n * K));
+        if (y_grad) POLEE_TRY(vi->d_ygrad.download(ctx, y_grad, nm1 * K));
+        if (mu_grad) POLEE_TRY(vi->d_mug.download(ctx, mu_grad, nm1));
+        if (omega_grad) POLEE_TRY(vi->d_omg.download(ctx, omega_grad, nm1));
+        if (alpha_grad) POLEE_TRY(vi->d_alg.download(ctx, alpha_grad, nm1));
+        if (lp) POLEE_TRY(vi->d_lp.download(ctx, lp, K));
+        if (ladj) {
+            std::vector<double> el(K * 2), rs(K * 2);
+            POLEE_TRY(vi->d_ladj_el.download(ctx, el.data(), K * 2));
+            POLEE_TRY(vi->d_rows.download(ctx, rs.data(), K * 2));
+            for (size_t d = 0; d < K; ++d) ladj[d] = el[d * 2] + el[d * 2 + 1] + rs[d * 2 + 1];
+        }
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_vi_fit(polee_loglik *ll, polee_ptt *t, const float *efflens, const polee_vi_opts *opts, float *mu,
                           float *omega, float *alpha, polee_vi_stats *stats)
 {
-    polee_vi *vi = nullptr;
-    POLEE_TRY(polee_vi_create(ll, t, efflens, opts, &vi));
-    polee_status s = polee_vi_run(vi, vi->o.num_steps);
-    if (s == POLEE_OK) s = polee_vi_sync(vi);
-    if (s == POLEE_OK) s = polee_vi_get_params(vi, mu, omega, alpha);
-    if (s == POLEE_OK && stats) s = polee_vi_get_stats(vi, stats);
-    polee_vi_destroy(vi);
-    return s;
+    return entry(ll, "polee_vi_fit", [&](polee_ctx *ctx) -> polee_status {
+        polee_vi *vi = nullptr;
+        POLEE_TRY(polee_vi_create(ll, t, efflens, opts, &vi));
+        polee_status s = polee_vi_run(vi, vi->o.num_steps);
+        if (s == POLEE_OK) s = polee_vi_sync(vi);
+        if (s == POLEE_OK) s = polee_vi_get_params(vi, mu, omega, alpha);
+        if (s == POLEE_OK && stats) s = polee_vi_get_stats(vi, stats);
+        polee_vi_destroy(vi);
+        return s;
+    });
 }
 
 polee_status polee_optimize_ptt(polee_loglik *ll, polee_ptt *t, const float *efflens, int32_t num_steps, float *xs,
                                 float *zs_out)
 {
-    if (!ll || !t || !efflens || !xs || num_steps < 0) return fail(nullptr, POLEE_ERR_BAD_ARG, "bad argument");
-    polee_vi_opts o;
-    polee_vi_default_opts(&o);
-    o.num_steps = num_steps;
-    o.num_mc_samples = 1;
-    polee_vi *vi = nullptr;
-    g_vi_plain_order = true;
-    const polee_status cs = polee_vi_create(ll, t, efflens, &o, &vi);  // initial z = logit(inverse_transform(1/n)) lands in d_mu
-    g_vi_plain_order = false;
-    POLEE_TRY(cs);
-    polee_ctx *ctx = vi->ctx;
-    hipStream_t st = ctx->stream;
-    const int32_t n = vi->n;
-    const int64_t nm1 = n - 1;
-    const PttView view = t->view();
-    const int nch_f = fwd_num_chunks(t->TL), nch_b = scan_num_chunks(n);
-    VK<1> *chunk_f = reinterpret_cast<VK<1> *>(t->d_chunk.p);
-    VD<1> *chunk_b = reinterpret_cast<VD<1> *>(t->d_chunk.p);
-    polee_status rc = POLEE_OK;
-    auto forward = [&]() -> polee_status {
-        hipLaunchKernelGGL(point_sample_kernel, dim3((unsigned)ceil_div(nm1, 256)), dim3(256), 0, st, vi->d_mu.p, nm1,
-                           vi->d_ys.p, vi->d_lyy.p);
-        if (nch_f > 1) {
-            hipLaunchKernelGGL((vi_fwd_reduce_kernel<1, LogRows>), dim3(nch_f), dim3(SCAN_THREADS), 0, st, view, LogRows{vi->d_lyy.p}, chunk_f);
-            hipLaunchKernelGGL((scan_spine_kernel<VK<1>>), dim3(1), dim3(SCAN_THREADS), 0, st, chunk_f, nch_f);
-        } else {
-            POLEE_HIP_TRY(ctx, hipMemsetAsync(chunk_f, 0, sizeof(VK<1>), st));
+    return entry(ll, "polee_optimize_ptt", [&](polee_ctx *ctx) -> polee_status {
+        if (!t || !efflens || !xs || num_steps < 0) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_optimize_ptt: bad argument");
+        polee_vi_opts o;
+        polee_vi_default_opts(&o);
+        o.num_steps = num_steps;
+        o.num_mc_samples = 1;
+        polee_vi *vi = nullptr;
+        g_vi_plain_order = true;
+        const polee_status cs = polee_vi_create(ll, t, efflens, &o, &vi);  // initial z = logit(inverse_transform(1/n)) lands in d_mu
+        g_vi_plain_order = false;
+        POLEE_TRY(cs);
+        hipStream_t st = ctx->stream;
+        const int32_t n = vi->n;
+        const int64_t nm1 = n - 1;
+        const PttView view = t->view();
+        const int nch_f = fwd_num_chunks(t->TL), nch_b = scan_num_chunks(n);
+        VK<1> *chunk_f = reinterpret_cast<VK<1> *>(t->d_chunk.p);
+        VD<1> *chunk_b = reinterpret_cast<VD<1> *>(t->d_chunk.p);
+        polee_status rc = POLEE_OK;
+        auto forward = [&]() -> polee_status {
+            hipLaunchKernelGGL(point_sample_kernel, dim3((unsigned)ceil_div(nm1, 256)), dim3(256), 0, st, vi->d_mu.p, nm1,
+                               vi->d_ys.p, vi->d_lyy.p);
+            if (nch_f > 1) {
+                hipLaunchKernelGGL((vi_fwd_reduce_kernel<1, LogRows>), dim3(nch_f), dim3(SCAN_THREADS), 0, st, view, LogRows{vi->d_lyy.p}, chunk_f);
+                hipLaunchKernelGGL((scan_spine_kernel<VK<1>>), dim3(1), dim3(SCAN_THREADS), 0, st, chunk_f, nch_f);
+            } else {
+                POLEE_HIP_TRY(ctx, hipMemsetAsync(chunk_f, 0, sizeof(VK<1>), st));
+            }
+            hipLaunchKernelGGL((vi_fwd_apply_kernel<1, LogRows, double, false>), dim3(nch_f), dim3(SCAN_THREADS), 0, st, view, LogRows{vi->d_lyy.p}, chunk_f,
+                               vi->d_uleaf.p, vi->d_x.p, vi->d_g.p, vi->d_efflens.p, (float)o.y_eps, (float)(1.0 - o.y_eps),
+                               vi->d_part_c.p, (double *)nullptr, 0, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                               (const uint32_t *)nullptr, (const uint32_t *)nullptr, (float *)nullptr, (const float *)nullptr, nch_f, 0);
+            POLEE_KERNEL_CHECK(ctx);
+            return POLEE_OK;
+        };
+        for (int step_num = 1; step_num <= num_steps && rc == POLEE_OK && nm1 > 0; ++step_num) {
+            rc = forward();
+            if (rc != POLEE_OK) break;
+            rc = loglik_eval_device(ll, vi->d_x.p, 1, vi->d_g.p, nullptr);
+            if (rc != POLEE_OK) break;
+            const GenePrior no_gp{nullptr, nullptr, nullptr, 0.0};
+            hipLaunchKernelGGL((vi_bwd_reduce_kernel<1>), dim3(nch_b), dim3(SCAN_THREADS), 0, st, view, vi->d_uleaf.p,
+                               vi->d_g.p, vi->d_efflens.p, vi->d_part_c.p, nch_f, vi->d_csum.p, no_gp, chunk_b);
+            hipLaunchKernelGGL((scan_spine_kernel<VD<1>>), dim3(1), dim3(SCAN_THREADS), 0, st, chunk_b, nch_b);
+            hipLaunchKernelGGL((vi_bwd_apply_kernel<1>), dim3(nch_b), dim3(SCAN_THREADS), 0, st, view, vi->d_uleaf.p,
+                               vi->d_g.p, vi->d_efflens.p, vi->d_csum.p, no_gp, chunk_b, vi->d_C.p, 0);
+            AdamConsts a = adam_schedule(o, step_num);
+            a.max_mu = 1e-1;  // ss_max_z_step (likelihood-approximation.jl:166)
+            hipLaunchKernelGGL(point_update_kernel, dim3((unsigned)ceil_div(nm1, 256)), dim3(256), 0, st, view, vi->d_ys.p,
+                               vi->d_C.p, vi->d_mu.p, vi->d_mm.p, vi->d_vm.p, a, vi->d_flag.p, step_num);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) rc = fail(ctx, POLEE_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
         }
-        hipLaunchKernelGGL((vi_fwd_apply_kernel<1, LogRows, double, false>), dim3(nch_f), dim3(SCAN_THREADS), 0, st, view, LogRows{vi->d_lyy.p}, chunk_f,
-                           vi->d_uleaf.p, vi->d_x.p, vi->d_g.p, vi->d_efflens.p, (float)o.y_eps, (float)(1.0 - o.y_eps),
-                           vi->d_part_c.p, (double *)nullptr, 0, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, (float *)nullptr, (const float *)nullptr, nch_f, 0);
-        POLEE_KERNEL_CHECK(ctx);
-        return POLEE_OK;
-    };
-    for (int step_num = 1; step_num <= num_steps && rc == POLEE_OK && nm1 > 0; ++step_num) {
-        rc = forward();
-        if (rc != POLEE_OK) break;
-        rc = loglik_eval_device(ll, vi->d_x.p, 1, vi->d_g.p, nullptr);
-        if (rc != POLEE_OK) break;
-        const GenePrior no_gp{nullptr, nullptr, nullptr, 0.0};
-        hipLaunchKernelGGL((vi_bwd_reduce_kernel<1>), dim3(nch_b), dim3(SCAN_THREADS), 0, st, view, vi->d_uleaf.p,
-                           vi->d_g.p, vi->d_efflens.p, vi->d_part_c.p, nch_f, vi->d_csum.p, no_gp, chunk_b);
-        hipLaunchKernelGGL((scan_spine_kernel<VD<1>>), dim3(1), dim3(SCAN_THREADS), 0, st, chunk_b, nch_b);
-        hipLaunchKernelGGL((vi_bwd_apply_kernel<1>), dim3(nch_b), dim3(SCAN_THREADS), 0, st, view, vi->d_uleaf.p,
-                           vi->d_g.p, vi->d_efflens.p, vi->d_csum.p, no_gp, chunk_b, vi->d_C.p, 0);
-        AdamConsts a;
-        a.lr = std::max(o.adam_min_learning_rate,
-                        o.adam_initial_learning_rate * std::exp(-o.adam_learning_rate_decay * (double)(step_num - 1)));
-        a.rm = o.adam_rm;
-        a.rv = o.adam_rv;
-        a.eps = o.adam_eps;
-        a.m_denom = 1 - std::pow(o.adam_rm, (double)step_num);
-        a.v_denom = 1 - std::pow(o.adam_rv, (double)step_num);
-        a.inv_m_denom = 1.0 / a.m_denom;
-        a.inv_v_denom = 1.0 / a.v_denom;
-        a.max_mu = 1e-1;  // ss_max_z_step (likelihood-approximation.jl:166)
-        a.max_omega = a.max_alpha = 0.0;
-        a.first = step_num == 1;
-        hipLaunchKernelGGL(point_update_kernel, dim3((unsigned)ceil_div(nm1, 256)), dim3(256), 0, st, view, vi->d_ys.p,
-                           vi->d_C.p, vi->d_mu.p, vi->d_mm.p, vi->d_vm.p, a, vi->d_flag.p, step_num);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = fail(ctx, POLEE_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    }
-    if (rc == POLEE_OK) rc = forward();  // final xs = clamp(transform(logistic(zs))) (:235-241)
-    if (rc == POLEE_OK) rc = polee_vi_sync(vi);
-    if (rc == POLEE_OK) rc = vi->d_x.download(ctx, xs, n);  // K = 1: [n][1] is [n]
-    if (rc == POLEE_OK && zs_out) rc = vi->d_mu.download(ctx, zs_out, nm1);
-    polee_vi_destroy(vi);
-    return rc;
+        if (rc == POLEE_OK) rc = forward();  // final xs = clamp(transform(logistic(zs))) (:235-241)
+        if (rc == POLEE_OK) rc = polee_vi_sync(vi);
+        if (rc == POLEE_OK) rc = vi->d_x.download(ctx, xs, n);  // K = 1: [n][1] is [n]
+        if (rc == POLEE_OK && zs_out) rc = vi->d_mu.download(ctx, zs_out, nm1);
+        polee_vi_destroy(vi);
+        return rc;
+    });
 }
 
 polee_status polee_sampler_draw(polee_ptt *t, const float *mu, const float *sigma, const float *alpha,
                                 const float *z0, int32_t ndraws, uint64_t seed, float *xs)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!xs) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    DevBuf<float> d_all;
-    POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all));
-    return d_all.download(ctx, xs, (size_t)ndraws * t->n);
+    return entry(t, "polee_sampler_draw", [&](polee_ctx *ctx) -> polee_status {
+        if (!xs) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_draw: bad argument");
+        DevBuf<float> d_all;
+        POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all));
+        return d_all.download(ctx, xs, (size_t)ndraws * t->n);
+    });
 }
 
 polee_status polee_sampler_initial_values(polee_ptt *t, const float *mu, const float *sigma, const float *alpha,
                                           const float *efflens, const float *z0, int32_t ndraws, uint64_t seed, float *x0)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!x0 || !efflens) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    DevBuf<float> d_all, d_l, d_x0;
-    DevBuf<double> d_sums;
-    POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all, 1e-10 /* LIKAP_Y_EPS */));
-    const int64_t n = t->n;
-    POLEE_TRY(d_l.upload(ctx, efflens, (size_t)n));
-    POLEE_TRY(d_x0.alloc(ctx, (size_t)n));
-    POLEE_TRY(d_sums.alloc(ctx, (size_t)ndraws));
-    POLEE_HIP_TRY(ctx, hipMemsetAsync(d_sums.p, 0, sizeof(double) * ndraws, ctx->stream));
-    hipLaunchKernelGGL(x0_sums_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 256), (unsigned)ndraws), dim3(256), 0,
-                       ctx->stream, d_all.p, d_l.p, n, d_sums.p);
-    hipLaunchKernelGGL(x0_mean_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_all.p, d_l.p, d_sums.p,
-                       ndraws, n, d_x0.p);
-    POLEE_KERNEL_CHECK(ctx);
-    return d_x0.download(ctx, x0, (size_t)n);
+    return entry(t, "polee_sampler_initial_values", [&](polee_ctx *ctx) -> polee_status {
+        if (!x0 || !efflens) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_initial_values: bad argument");
+        DevBuf<float> d_all, d_l, d_x0;
+        DevBuf<double> d_sums;
+        POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all, 1e-10 /* LIKAP_Y_EPS */));
+        const int64_t n = t->n;
+        POLEE_TRY(d_l.upload(ctx, efflens, (size_t)n));
+        POLEE_TRY(d_x0.alloc(ctx, (size_t)n));
+        POLEE_TRY(d_sums.alloc(ctx, (size_t)ndraws));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(d_sums.p, 0, sizeof(double) * ndraws, ctx->stream));
+        hipLaunchKernelGGL(x0_sums_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 256), (unsigned)ndraws), dim3(256), 0,
+                           ctx->stream, d_all.p, d_l.p, n, d_sums.p);
+        hipLaunchKernelGGL(x0_mean_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_all.p, d_l.p, d_sums.p,
+                           ndraws, n, d_x0.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return d_x0.download(ctx, x0, (size_t)n);
+    });
 }
 
 polee_status polee_sampler_posterior_mean(polee_ptt *t, const float *mu, const float *sigma, const float *alpha,
                                           const float *z0, int32_t ndraws, uint64_t seed, float *pm)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!pm) return fail(ctx, POLEE_ERR_BAD_ARG, "bad argument");
-    DevBuf<float> d_all, d_pm;
-    POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all));
-    POLEE_TRY(d_pm.alloc(ctx, (size_t)t->n));
-    hipLaunchKernelGGL(sampler_mean_kernel, dim3((unsigned)ceil_div(t->n, 256)), dim3(256), 0, ctx->stream, d_all.p,
-                       ndraws, (int64_t)t->n, d_pm.p);
-    POLEE_KERNEL_CHECK(ctx);
-    return d_pm.download(ctx, pm, (size_t)t->n);
+    return entry(t, "polee_sampler_posterior_mean", [&](polee_ctx *ctx) -> polee_status {
+        if (!pm) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_sampler_posterior_mean: bad argument");
+        DevBuf<float> d_all, d_pm;
+        POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all));
+        POLEE_TRY(d_pm.alloc(ctx, (size_t)t->n));
+        hipLaunchKernelGGL(sampler_mean_kernel, dim3((unsigned)ceil_div(t->n, 256)), dim3(256), 0, ctx->stream, d_all.p,
+                           ndraws, (int64_t)t->n, d_pm.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return d_pm.download(ctx, pm, (size_t)t->n);
+    });
 }
 
 polee_status polee_sampler_quantiles(polee_ptt *t, const float *mu, const float *sigma, const float *alpha,
                                      const float *z0, int32_t ndraws, uint64_t seed, const double *qs, int32_t nq,
                                      float *quantiles)
 {
-    if (!t) return fail(nullptr, POLEE_ERR_BAD_ARG, "null tree");
-    polee_ctx *ctx = t->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!qs || !quantiles || nq < 1 || nq > SAMPLER_MAX_Q) return fail(ctx, POLEE_ERR_BAD_ARG, "1..%d quantiles", SAMPLER_MAX_Q);
-    QuantileSpec spec{};
-    spec.nq = nq;
-    for (int i = 0; i < nq; ++i) {
-        if (!(qs[i] >= 0.0 && qs[i] <= 1.0)) return fail(ctx, POLEE_ERR_BAD_ARG, "quantile %g outside [0, 1]", qs[i]);
-        // Statistics.quantile, default (type 7): aleph = (N-1) q + 1, j = clamp(trunc(aleph), 1, N-1), gamma = aleph - j
-        const double aleph = (double)(ndraws - 1) * qs[i] + 1.0;
-        const int j = ndraws == 1 ? 1 : std::min(std::max((int)aleph, 1), ndraws - 1);
-        spec.j[i] = j;
-        spec.gamma[i] = std::min(std::max(aleph - j, 0.0), 1.0);
-    }
-    DevBuf<float> d_all, d_q;
-    POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all));
-    const int64_t n = t->n;
-    POLEE_TRY(d_q.alloc(ctx, (size_t)nq * n));
-    const bool in_lds = (size_t)ndraws * 64 * sizeof(float) <= 48 * 1024;
-    hipLaunchKernelGGL(sampler_quantile_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64),
-                       in_lds ? (size_t)ndraws * 64 * sizeof(float) : 0, ctx->stream, d_all.p, ndraws, n, spec,
-                       in_lds ? 1 : 0, d_q.p);
-    POLEE_KERNEL_CHECK(ctx);
-    return d_q.download(ctx, quantiles, (size_t)nq * n);
+    return entry(t, "polee_sampler_quantiles", [&](polee_ctx *ctx) -> polee_status {
+        if (!qs || !quantiles || nq < 1 || nq > SAMPLER_MAX_Q) return fail(ctx, POLEE_ERR_BAD_ARG, "1..%d quantiles", SAMPLER_MAX_Q);
+        QuantileSpec spec{};
+        spec.nq = nq;
+        for (int i = 0; i < nq; ++i) {
+            if (!(qs[i] >= 0.0 && qs[i] <= 1.0)) return fail(ctx, POLEE_ERR_BAD_ARG, "quantile %g outside [0, 1]", qs[i]);
+            // Statistics.quantile, default (type 7): aleph = (N-1) q + 1, j = clamp(trunc(aleph), 1, N-1), gamma = aleph - j
+            const double aleph = (double)(ndraws - 1) * qs[i] + 1.0;
+            const int j = ndraws == 1 ? 1 : std::min(std::max((int)aleph, 1), ndraws - 1);
+            spec.j[i] = j;
+            spec.gamma[i] = std::min(std::max(aleph - j, 0.0), 1.0);
+        }
+        DevBuf<float> d_all, d_q;
+        POLEE_TRY(sampler_draw_device(t, mu, sigma, alpha, z0, ndraws, seed, d_all));
+        const int64_t n = t->n;
+        POLEE_TRY(d_q.alloc(ctx, (size_t)nq * n));
+        const bool in_lds = (size_t)ndraws * 64 * sizeof(float) <= 48 * 1024;
+        hipLaunchKernelGGL(sampler_quantile_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64),
+                           in_lds ? (size_t)ndraws * 64 * sizeof(float) : 0, ctx->stream, d_all.p, ndraws, n, spec,
+                           in_lds ? 1 : 0, d_q.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return d_q.download(ctx, quantiles, (size_t)nq * n);
+    });
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 //   vi_bwd_reduce / scan_spine / vi_bwd_apply : double-double leaf-order prefix of u*(g - efflen term)
 //   vi_update      : y_grad, chain rule, mean over K, finiteness flag, ADAM  (thread = node)
 #pragma once
+#include "adam.hpp"
 #include "ptt_internal.hpp"
 
 namespace polee {
@@ -698,13 +699,6 @@ __device__ inline double fast_rcp(double x)
     r = fma(fma(-x, r, 1.0), r, r);
     return r;
 }
-
-struct AdamConsts {
-    double lr, rm, rv, eps, m_denom, v_denom;
-    double inv_m_denom, inv_v_denom;  // reciprocals, computed once on the host (the update kernel is bound by its f64 instructions)
-    double max_mu, max_omega, max_alpha;
-    int first;  // step_num == 1
-};
 
 __device__ inline void adam_one(float &p, float &m, float &v, float grad, const AdamConsts &a, double max_step)
 {

@@ -843,26 +843,29 @@ static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcr
 polee_status polee_xbuild_run(polee_ctx *ctx, const polee_xb_transcripts *T, const polee_xb_fragments *F, const polee_xb_fragmodel *M,
                               polee_xbuild **out)
 {
-    return guarded(ctx, "polee_xbuild_run", [&] { return polee_xbuild_run_impl(ctx, T, F, M, nullptr, out); });
+    return ctx_entry(ctx, "polee_xbuild_run", [&]() -> polee_status {
+        return polee_xbuild_run_impl(ctx, T, F, M, nullptr, out);
+    });
 }
 
 polee_status polee_xbuild_run_biased(polee_ctx *ctx, const polee_xb_transcripts *T, const polee_xb_fragments *F, const polee_xb_fragmodel *M,
                                      const polee_xb_biasmodel *B, polee_xbuild **out)
 {
-    if (!B) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run_biased: null bias model");
-    return guarded(ctx, "polee_xbuild_run_biased", [&] { return polee_xbuild_run_impl(ctx, T, F, M, B, out); });
+    return ctx_entry(ctx, "polee_xbuild_run_biased", [&]() -> polee_status {
+        if (!B) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run_biased: null bias model");
+        return polee_xbuild_run_impl(ctx, T, F, M, B, out);
+    });
 }
 
 polee_status polee_xbuild_get_bias(const polee_xbuild *xb, float *left_bias, float *right_bias, double *ms_bias)
 {
-    if (!xb) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = xb->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (!xb->d_left_bias.p) return fail(ctx, POLEE_ERR_BAD_ARG, "this matrix was built without a bias model");
-    if (left_bias) POLEE_TRY(xb->d_left_bias.download(ctx, left_bias, (size_t)xb->total_bases));
-    if (right_bias) POLEE_TRY(xb->d_right_bias.download(ctx, right_bias, (size_t)xb->total_bases));
-    if (ms_bias) *ms_bias = xb->ms_bias;
-    return POLEE_OK;
+    return entry(xb, "polee_xbuild_get_bias", [&](polee_ctx *ctx) -> polee_status {
+        if (!xb->d_left_bias.p) return fail(ctx, POLEE_ERR_BAD_ARG, "this matrix was built without a bias model");
+        if (left_bias) POLEE_TRY(xb->d_left_bias.download(ctx, left_bias, (size_t)xb->total_bases));
+        if (right_bias) POLEE_TRY(xb->d_right_bias.download(ctx, right_bias, (size_t)xb->total_bases));
+        if (ms_bias) *ms_bias = xb->ms_bias;
+        return POLEE_OK;
+    });
 }
 
 void polee_xbuild_destroy(polee_xbuild *xb)
@@ -876,27 +879,27 @@ void polee_xbuild_destroy(polee_xbuild *xb)
 
 polee_status polee_xbuild_sizes(const polee_xbuild *xb, int64_t *rows, int64_t *nnz, double *ms_efflen, double *ms_count, double *ms_fill)
 {
-    if (!xb) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    if (rows) *rows = xb->rows;
-    if (nnz) *nnz = xb->nnz;
-    if (ms_efflen) *ms_efflen = xb->ms_efflen;
-    if (ms_count) *ms_count = xb->ms_count;
-    if (ms_fill) *ms_fill = xb->ms_fill;
-    return POLEE_OK;
+    return entry(xb, "polee_xbuild_sizes", [&](polee_ctx *ctx) -> polee_status {
+        if (rows) *rows = xb->rows;
+        if (nnz) *nnz = xb->nnz;
+        if (ms_efflen) *ms_efflen = xb->ms_efflen;
+        if (ms_count) *ms_count = xb->ms_count;
+        if (ms_fill) *ms_fill = xb->ms_fill;
+        return POLEE_OK;
+    });
 }
 
 polee_status polee_xbuild_get(const polee_xbuild *xb, uint64_t *tcolptr, uint32_t *trowval, float *tnzval, float *effective_lengths,
                               int64_t *row_fragment)
 {
-    if (!xb) return fail(nullptr, POLEE_ERR_BAD_ARG, "null handle");
-    polee_ctx *ctx = xb->ctx;
-    POLEE_TRY(use_device(ctx));
-    if (tcolptr) POLEE_TRY(xb->d_tcolptr.download(ctx, tcolptr, (size_t)xb->rows + 1));
-    if (trowval) POLEE_TRY(xb->d_cols.download(ctx, trowval, (size_t)xb->nnz));
-    if (tnzval) POLEE_TRY(xb->d_vals.download(ctx, tnzval, (size_t)xb->nnz));
-    if (effective_lengths) POLEE_TRY(xb->d_efflens.download(ctx, effective_lengths, (size_t)xb->n));
-    if (row_fragment) POLEE_TRY(xb->d_row_fragment.download(ctx, row_fragment, (size_t)xb->rows));
-    return POLEE_OK;
+    return entry(xb, "polee_xbuild_get", [&](polee_ctx *ctx) -> polee_status {
+        if (tcolptr) POLEE_TRY(xb->d_tcolptr.download(ctx, tcolptr, (size_t)xb->rows + 1));
+        if (trowval) POLEE_TRY(xb->d_cols.download(ctx, trowval, (size_t)xb->nnz));
+        if (tnzval) POLEE_TRY(xb->d_vals.download(ctx, tnzval, (size_t)xb->nnz));
+        if (effective_lengths) POLEE_TRY(xb->d_efflens.download(ctx, effective_lengths, (size_t)xb->n));
+        if (row_fragment) POLEE_TRY(xb->d_row_fragment.download(ctx, row_fragment, (size_t)xb->rows));
+        return POLEE_OK;
+    });
 }
 
 }  // extern "C"

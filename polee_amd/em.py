@@ -47,24 +47,17 @@ def _start(y0, n):
     return y
 
 
-class EM:
+class EM(L.Handle):
     """EM over the X of an existing core.RNASeqSample (polee_em): its device layout, its multiplicities ks and its effective
     lengths are used as they are.  While iterations run, nothing else may evaluate the same sample (one evaluation slot per
     likelihood handle)."""
+    _destroy = "polee_em_destroy"
 
     def __init__(self, sample, y0=None):
         self.sample, self.ctx, self.n = sample, sample.ctx, int(sample.n)
         self._h = C.c_void_p()
         y = _start(y0, self.n)
         check(L.lib().polee_em_create(sample._h, ptr(y, f32p), C.byref(self._h)), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_em_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def reset(self, y0=None):
         y = _start(y0, self.n)

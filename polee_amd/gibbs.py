@@ -34,10 +34,11 @@ class GibbsInfo(C.Structure):
                 ("multi_nnz", C.c_int64), ("num_tiles", C.c_int64), ("rows_per_tile", C.c_int32), ("sweeps_done", C.c_int64)]
 
 
-class GibbsSampler:
+class GibbsSampler(L.Handle):
     """num_chains collapsed Gibbs chains over X on the GPU (polee_gibbs).  X by columns as in the likelihood-matrix HDF5
     (colptr / rowval 1-based), or fragment-major through xt = (tcolptr u64 [m+1], trowval u32, tnzval f32), 1-based.
     efflens = None: no effective-length transformation of the stored draws (--no-efflen)."""
+    _destroy = "polee_gibbs_destroy"
 
     def __init__(self, m, n, colptr, rowval, nzval, efflens=None, num_chains=8, seed=DEFAULT_SEED, ctx=None, xt=None):
         from .core import default_context
@@ -59,14 +60,6 @@ class GibbsSampler:
             check(lib.polee_gibbs_create(self.ctx._h, C.c_int64(self.m), C.c_int64(self.n), colptr.ctypes.data_as(C.c_void_p),
                                          int(colptr.dtype.itemsize), ptr(rowval, u32p), ptr(nzval, f32p), ptr(el, f32p),
                                          C.c_int32(self.num_chains), C.c_uint64(int(seed)), C.byref(self._h)), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().polee_gibbs_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def set_state(self, g0=None):
         """Chains' unnormalised mixture [C, n] (finite, >= 0), or None = fresh Gamma(1) draws."""

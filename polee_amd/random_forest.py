@@ -36,8 +36,6 @@ def _bind():
     lib.polee_forest_default_opts.restype = None
     lib.polee_forest_default_opts.argtypes = [C.POINTER(ForestOpts)]
     lib.polee_forest_create.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(ForestOpts), C.POINTER(vp)]
-    lib.polee_forest_destroy.restype = None
-    lib.polee_forest_destroy.argtypes = [vp]
     lib.polee_forest_fit_points.argtypes = [vp, f32p, i32p, C.c_int32, C.c_uint64]
     lib.polee_forest_fit.argtypes = [vp, vp, i32p, C.c_int32, C.c_uint64, C.c_uint64, f32p]
     lib.polee_forest_node_count.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]

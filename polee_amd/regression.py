@@ -81,9 +81,10 @@ def estimate_sample_scales(x, upper_quantile=0.95):
     return np.median(x_mean[high][None, :] - x[:, high], axis=1, keepdims=True).astype(np.float32)
 
 
-class RNASeqLinearRegression:
+class RNASeqLinearRegression(L.Handle):
     """RNASeqLinearRegression (models/polee_regression.py:18-340).  `likelihood_model` is an
     RNASeqApproxLikelihood (or None with point estimates) instead of a TFP coroutine."""
+    _destroy = "polee_regression_destroy"
 
     def __init__(self, F, x_init, likelihood_model, x_bias_loc0, x_bias_scale0, x_scale_hinges, sample_scales,
                  use_distortion, scale_penalty, use_point_estimates, kernel_regression_degree,
@@ -164,17 +165,6 @@ class RNASeqLinearRegression:
         self.comm = comm
         if comm is not None:
             check(lib.polee_regression_set_comm(self._h, comm._h), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                f = L.lib().polee_regression_destroy
-                f.restype = None
-                f.argtypes = [C.c_void_p]
-                f(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     # ---- parameters by the reference's variable names
     def _shape(self, code):
@@ -646,9 +636,10 @@ DEFAULT_SEED = 123456789
 _MASK = (1 << 64) - 1
 
 
-class IsoformEffects:
+class IsoformEffects(L.Handle):
     """The device handle polee_effects_* (include/polee_hip.h): the transcripts of n are segmented by gene once; run() makes the
     Monte-Carlo draws and returns the six arrays.  gene_of: the 0-based gene of every transcript, in any order."""
+    _destroy = "polee_effects_destroy"
 
     def __init__(self, gene_of, num_genes, num_factors, ctx=None):
         g = arr(np.asarray(gene_of).reshape(-1), np.int32)
@@ -657,16 +648,6 @@ class IsoformEffects:
         self._h = C.c_void_p()
         self.kernel_ms = None
         check(L.lib().polee_effects_create(self.ctx._h, self.n, self.G, ptr(g, L.i32p), self.F, C.byref(self._h)), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                f = L.lib().polee_effects_destroy
-                f.restype, f.argtypes = None, [C.c_void_p]
-                f(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def run(self, qw_loc, qw_scale, qx_bias_loc, qx_bias_scale, niter=EFFECT_DRAWS, target_coverage=0.1, effect_size=None,
             aitchison_effect_size=None, seed=DEFAULT_SEED, zx=None, zw=None):

@@ -34,18 +34,10 @@ DEFAULT_BATCH = 16
 COUNT_EXPECTED, COUNT_SAMPLED = 0, 1
 
 
-def _bind():
-    lib = L.lib()
-    if not getattr(lib, "_polee_sample_bound", False):
-        lib.polee_sampler_destroy.restype = None
-        lib.polee_sampler_destroy.argtypes = [C.c_void_p]
-        lib._polee_sample_bound = True
-    return lib
-
-
-class ApproxSampleStream:
+class ApproxSampleStream(L.Handle):
     """A stream of draws from one fitted approximation on the GPU (polee_sampler): t a PolyaTreeTransform, mu / sigma / alpha f32
     [n-1] (sigma = exp(omega)), efflens f32 [n], m reads.  Draw d of a seed is the same whatever the batch sizes."""
+    _destroy = "polee_sampler_destroy"
 
     def __init__(self, t, mu, sigma, alpha, efflens, m, seed=DEFAULT_SEED):
         self.t, self.ctx, self.n, self.m = t, t.ctx, int(t.n), int(m)
@@ -54,18 +46,8 @@ class ApproxSampleStream:
         if mu.size != self.n - 1 or sigma.size != self.n - 1 or alpha.size != self.n - 1 or l.size != self.n:
             raise ValueError("mu, sigma, alpha need n - 1 = %d entries and efflens n" % (self.n - 1))
         self._h = C.c_void_p()
-        check(_bind().polee_sampler_create(t._h, ptr(mu, f32p), ptr(sigma, f32p), ptr(alpha, f32p), ptr(l, f32p), C.c_int64(self.m),
+        check(L.lib().polee_sampler_create(t._h, ptr(mu, f32p), ptr(sigma, f32p), ptr(alpha, f32p), ptr(l, f32p), C.c_int64(self.m),
                                            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.byref(self._h)), self.ctx._h)
-
-    def __del__(self):
-        try:
-            if self._h:
-                _bind().polee_sampler_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    close = __del__
 
     @property
     def num_draws(self):

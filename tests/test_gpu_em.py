@@ -356,7 +356,7 @@ def test_argument_rejection(P, ctx, lm_fixture, prob):
     lib = L.lib()
     h = C.c_void_p()
     assert lib.polee_em_create(None, None, C.byref(h)) == 1 and not h
-    assert b"null likelihood" in lib.polee_last_error(None)
+    assert b"polee_em_create: null handle" in lib.polee_last_error(None)
     s = _sample(P, ctx, lm)
     good = np.full(n, 1.0, np.float32)
     for name, j, v in (("negative", 3, -1.0), ("NaN", 4, np.nan), ("infinite", 5, np.inf)):

@@ -22,3 +22,14 @@ def test_host_builders_clean_under_sanitizer(san):
                        timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "ok" in r.stdout
+
+
+def test_entry_openers_clean_under_sanitizer():
+    """The three openers of the C entry points (csrc/common.hpp) with bodies that throw and with null handles, address+undefined:
+    tests/san/entry_main.cpp, its own program, linked with ctx.hip only."""
+    subprocess.check_call(["make", "-s", "-C", CSRC, "_obj/san_address_undefined/entry_check", "SAN=address,undefined"],
+                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    r = subprocess.run([os.path.join(CSRC, "_obj", "san_address_undefined", "entry_check")], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "ok" in r.stdout
