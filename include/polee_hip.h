@@ -100,9 +100,11 @@ polee_status polee_make_inverse_ptt_params(const int32_t *node_parent_idxs, cons
                                            int32_t N, int32_t *left_index, int32_t *right_index,
                                            int32_t *leaf_index);
 
-/* transform! (src/ptt.jl:125-160): ys f64 [B][n-1] in (0,1) -> xs f32 [B][n] on the
+/* transform! (src/ptt.jl:125-160): ys f64 [B][n-1] in [0,1] -> xs f32 [B][n] on the
  * simplex, leaves floored at 1e-16; ladj (optional, [B]) = sum over internal nodes of
- * log u.  The node values u of the last call stay on the device for
+ * log u.  A y of exactly 0 or 1 gives the subtree on its dead side u = 0: its leaves
+ * come out at the floor, and ladj is -inf if that subtree has an internal node (a NaN
+ * or +inf ladj is POLEE_ERR_NONFINITE).  The node values u of the last call stay on the device for
  * polee_ptt_transform_gradients, like t.us does in the reference. */
 polee_status polee_ptt_transform(polee_ptt *t, const double *ys, int32_t B, float *xs,
                                  double *ladj_or_null);

@@ -154,7 +154,8 @@ polee_status ptt_forward_device(polee_ptt *t, const double *d_ys, int32_t B, con
     FwdEmit emit{t->view(), el,         o.uleaf,    o.logu,     o.xs,     o.xs_rs,
                  o.xs_es,   o.leaf_floor, o.clamp_lo, o.clamp_hi, o.efflens, o.efflens_rs};
     double *partials = o.row_sums ? t->d_part.p : nullptr;
-    hipError_t e = run_scan_partial<double>(ctx->stream, B, t->TL, (double *)t->d_chunk.p, partials, load, emit);
+    static_assert(sizeof(logprod) <= sizeof(dd), "the forward scan's chunk totals live in d_chunk");
+    hipError_t e = run_scan_partial<logprod>(ctx->stream, B, t->TL, (logprod *)t->d_chunk.p, partials, load, emit);
     if (e != hipSuccess) return fail(ctx, POLEE_ERR_HIP, "forward scan launch failed: %s", hipGetErrorString(e));
     if (o.row_sums) {
         hipLaunchKernelGGL(reduce_partials_kernel, dim3(B), dim3(SCAN_THREADS), 0, ctx->stream, t->d_part.p,
@@ -444,8 +445,9 @@ polee_status polee_ptt_transform(polee_ptt *t, const double *ys, int32_t B, floa
             POLEE_TRY(t->d_row.download(ctx, rs.data(), rs.size()));
             for (int b = 0; b < B; ++b) {
                 ladj[b] = rs[(size_t)b * 2 + 1];
-                if (!std::isfinite(ladj[b]))
-                    return fail(ctx, POLEE_ERR_NONFINITE, "transform!: non-finite ladj (ptt.jl:157)");
+                // (-inf is the value for ys with a closed end, where a subtree's u is 0; NaN and +inf stay errors)
+                if (std::isnan(ladj[b]) || ladj[b] == HUGE_VAL)
+                    return fail(ctx, POLEE_ERR_NONFINITE, "transform!: ladj is NaN or +inf (ptt.jl:157)");
             }
         }
         return POLEE_OK;

@@ -104,17 +104,21 @@ struct EdgeLogs {
 
 // Forward (transform!, src/ptt.jl:125-160; HSB op hsb_ops.cpp:87-109): Euler-tour scan
 // of signed edge logs.  log u(node) = inclusive prefix at its ENTER; leaves add their
-// own edge.
+// own edge.  A dead edge (y exactly 1 on a right edge or 0 on a left one: edge log -inf, which the sampler and the HSB op
+// reach with a saturated logistic) is counted, not summed (scan.hpp's logprod): every node and leaf under it has u = 0 as
+// in the reference's products, and the prefixes behind its EXIT are what they are without it.
 struct FwdLoad {
     PttView v;
     EdgeLogs el;
-    __device__ double operator()(int row, int64_t e) const
+    __device__ logprod operator()(int row, int64_t e) const
     {
         const uint32_t code = v.tour_code[(int64_t)v.tree(row) * v.TL + e];
         const uint32_t type = code & 3u;
-        if (type == TOUR_LEAF) return 0.0;
+        if (type == TOUR_LEAF) return logprod{0.0, 0};
         const double lf = el(code, row);
-        return type == TOUR_ENTER ? lf : -lf;
+        const bool enter = type == TOUR_ENTER;
+        if (lf == -HUGE_VAL) return logprod{0.0, enter ? 1 : -1};
+        return logprod{enter ? lf : -lf, 0};
     }
 };
 
@@ -130,7 +134,7 @@ struct FwdEmit {
     const float *efflens;  // optional: partial sum 0 accumulates x/efflen (likelihood.jl:97-100)
     int64_t efflens_rs;    // row stride of efflens (0: one vector shared by all rows)
     // returns the element's contribution to the two per-chunk partial sums
-    __device__ void operator()(int row, int64_t e, double /*excl*/, double incl, double &p0, double &p1) const
+    __device__ void operator()(int row, int64_t e, logprod /*excl*/, logprod incl, double &p0, double &p1) const
     {
         const int64_t tb = (int64_t)v.tree(row) * v.TL;
         const uint32_t code = v.tour_code[tb + e];
@@ -138,8 +142,8 @@ struct FwdEmit {
         p0 = 0.0;
         p1 = 0.0;
         if (type == TOUR_LEAF) {
-            const double lu = incl + el(code, row);
-            const double u = exp(lu);
+            const double lu = incl.s + el(code, row);
+            const double u = incl.dead > 0 ? 0.0 : exp(lu);  // (exp(-inf) = 0: the leaf's own edge is dead)
             const int pos = v.tour_tgt[tb + e];
             if (uleaf) uleaf[(int64_t)row * v.n + pos] = u;
             if (xs) {
@@ -151,8 +155,9 @@ struct FwdEmit {
                 if (efflens) p0 = (double)(x / efflens[(int64_t)row * efflens_rs + tid]);
             }
         } else if (type == TOUR_ENTER) {
-            if (logu) logu[(int64_t)row * (v.n - 1) + v.tour_tgt[tb + e]] = incl;
-            p1 = incl;  // ladj = sum over internal nodes of log u (ptt.jl:150-152)
+            const double lu = incl.dead > 0 ? -HUGE_VAL : incl.s;
+            if (logu) logu[(int64_t)row * (v.n - 1) + v.tour_tgt[tb + e]] = lu;
+            p1 = lu;  // ladj = sum over internal nodes of log u (ptt.jl:150-152); -inf, never NaN, below a dead edge
         }
     }
 };

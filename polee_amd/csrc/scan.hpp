@@ -78,6 +78,25 @@ struct ScanOps<dd> {
     __device__ static dd dpp(dd v) { return dd{dpp_f64<CTRL, ROW_MASK>(v.hi), dpp_f64<CTRL, ROW_MASK>(v.lo)}; }
 };
 
+// A log-space product with its count of zero factors: the forward tree scan's element (ptt_internal.hpp).  A factor of
+// exactly 0 has log -inf, and the -inf of an ENTER and the +inf of its EXIT would leave NaN in every later prefix; such an
+// edge adds 0 to `s` and +-1 to `dead` instead, and a prefix with dead > 0 stands for the product 0.
+struct logprod {
+    double s;
+    int32_t dead;
+};
+template <>
+struct ScanOps<logprod> {
+    __device__ static logprod zero() { return logprod{0.0, 0}; }
+    __device__ static logprod add(logprod a, logprod b) { return logprod{a.s + b.s, a.dead + b.dead}; }
+    __device__ static logprod shfl_up(logprod v, int d) { return logprod{__shfl_up(v.s, d, 64), __shfl_up(v.dead, d, 64)}; }
+    template <int CTRL, int ROW_MASK>
+    __device__ static logprod dpp(logprod v)
+    {
+        return logprod{dpp_f64<CTRL, ROW_MASK>(v.s), __builtin_amdgcn_update_dpp(0, v.dead, CTRL, ROW_MASK, 0xf, false)};
+    }
+};
+
 // Inclusive scan across the 64 lanes of a wave: four shifts inside the rows of 16 lanes, then the rows' totals handed on
 // (row 0 -> 1 and 2 -> 3, then rows 0-1 -> 2-3) -- six adds per lane like the shuffle form it replaces (round 6), whose six
 // ds_bpermute round trips and per-step selects it does without.

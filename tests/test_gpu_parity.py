@@ -705,6 +705,30 @@ def test_sampler_quantiles_and_posterior_mean(P, ctx, prep_fixture):
         for d in range(N):  # f32 accumulation in draw order, as the reference
             acc += np.clip(draws[d], np.float32(1e-15), np.float32(0.9999999))
         np.testing.assert_allclose(pm, acc / np.float32(N), rtol=3e-5, atol=1e-30)
+    # the LDS boundary with supplied noise: a column of N = 192 draws fills the 48 KiB of LDS exactly, 193 takes the global-memory
+    # path.  Also with a few saturated nodes (mu = 30, -120, 17: y is exactly 1 or 0), whose dead transcripts are ties at the floor.
+    mu_s = mu.copy()
+    mu_s[[5, 40, 100]] = (30.0, -120.0, 17.0)
+    als_s = P.ApproxLikelihoodSampler()
+    als_s.set_transform(t, mu_s, sigma, alpha)
+    floor = np.float32(1e-16)
+    for N in (192, 193):
+        z0 = np.stack([O.randn(t.n - 1, 2000 + d) for d in range(N)])
+        for sampler, m in ((als, mu), (als_s, mu_s)):
+            draws = np.stack([O.sampler_draw(to, m, sigma, alpha, z0[d]) for d in range(N)])
+            qs = (0.0, 0.01, 0.5, 0.99, 1.0)
+            q = sampler.quantile(qs, N, z0=z0)
+            np.testing.assert_allclose(q, np.quantile(draws.astype(np.float64), qs, axis=0), rtol=3e-5, atol=1e-30)
+            at_floor = (draws == floor).sum(axis=0)
+            if sampler is als_s:
+                assert (at_floor == N).sum() >= 20
+            assert (q[:, at_floor == N] == floor).all()  # ties: exactly the floor
+            assert (q[:3, at_floor >= N // 2 + 2] == floor).all()  # at the floor in most draws: up to the median
+            pm = sampler.posterior_mean(N, z0=z0)
+            acc = np.zeros(t.n, np.float32)
+            for d in range(N):
+                acc += np.clip(draws[d], np.float32(1e-15), np.float32(0.9999999))
+            np.testing.assert_allclose(pm, acc / np.float32(N), rtol=3e-5, atol=1e-30)
     # more draws than fit in LDS (global fallback) and the device RNG: quantiles are ordered and bracket the mean draw
     q = als.quantile((0.05, 0.5, 0.95), 300)
     assert np.all(q[0] <= q[1]) and np.all(q[1] <= q[2])
