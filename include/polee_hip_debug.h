@@ -98,6 +98,17 @@ polee_status polee_debug_fast_log(polee_ctx *ctx, const double *x, int64_t count
 /* fast_exp (csrc/scan.hpp), the double-precision exp of the VI loop's forward kernel (leaf u = exp of a path sum of edge logs) */
 polee_status polee_debug_fast_exp(polee_ctx *ctx, const double *x, int64_t count, double *out);
 
+/* The device normal generator (csrc/rng.hpp), piece by piece; tests/rng_restatement.py restates both in NumPy.
+ * polee_debug_philox: philox4x32_10 of every counter under the key (low word of seed, high word of seed): counters u32 [count][4]
+ * -> words u32 [count][4].
+ * polee_debug_box_muller: the normals of every block of words, words u32 [count][4] -> z f32 [count][4], through the inline function
+ * the production kernels call.  which = 0: philox_box_muller4, the hardware log2 / sqrt / sin / cos of the VI loop, the alternative
+ * approximations, the samplers, regression and the isoform effects: z[0], z[1] = radius(word 0) * (cos, sin)(word 1), z[2], z[3] the
+ * same of words 2, 3.  which = 1: philox_box_muller_libm, the libm variant of polee_approx_sample: one normal per block,
+ * z[0] = radius(word 0) * cos(word 1); z[1], z[2], z[3] are written as 0 and words 2, 3 are not read.  count in [1, 2^28]. */
+polee_status polee_debug_philox(polee_ctx *ctx, uint64_t seed, const uint32_t *counters, int64_t count, uint32_t *words);
+polee_status polee_debug_box_muller(polee_ctx *ctx, int32_t which, const uint32_t *words, int64_t count, float *z);
+
 /* Per-node intermediates of the approximation density (csrc/approx.hip) as the last polee_approx_logprob call WITH a gradient left
  * them on the device: tpair f64 [S][n-1][2] = the two tour terms of InvHSBGrad of every internal node k (the plan's node order;
  * [0]: the edge to its right child, leaves [lo, mid), [1]: to its left child, [mid, hi1)), bp f32 [S][n] = d / d q per transcript.

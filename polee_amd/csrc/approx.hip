@@ -11,6 +11,7 @@
 //   (grad) finish    : chain through q = r/R, r = p*l, p = softmax(x):
 //                      x_grad_j = q_j (bp_j - <bp,q> - 1) + 1 - (n-2) p_j
 #include "ptt_internal.hpp"
+#include "rng.hpp"
 #include "../../include/polee_hip_debug.h"
 
 #include <cmath>
@@ -327,22 +328,10 @@ __global__ void approx_sample_finish_kernel(ApproxView a, const double *row_sums
 
 __device__ inline float approx_philox_randn(uint64_t seed, uint32_t s, uint32_t k)
 {
-    // Philox4x32-10 as in vi.hip (kept local: separate translation unit)
+    // counter (node, sample, 1, 'appx'); one normal per block, the libm Box-Muller of rng.hpp on words 0 and 1
     uint32_t c[4] = {k, s, 1u, 0x61707078u};
-    uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ key[0], n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ key[1], n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        key[0] += 0x9E3779B9u;
-        key[1] += 0xBB67AE85u;
-    }
-    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+    philox4x32_10(c, seed);
+    return philox_box_muller_libm(c[0], c[1]);
 }
 
 __global__ void approx_sample_y_kernel(ApproxView a, const float *z0, uint64_t seed, double *ys)

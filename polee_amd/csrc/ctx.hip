@@ -73,7 +73,9 @@ extern "C" {
 #define POLEE_BUILD_INFO "unknown compiler"
 #endif
 // (the build records the hipcc version and the backend tuning flags loglik.hip was compiled with: csrc/Makefile)
-const char *polee_version(void) { return "polee_hip 0.3 (gfx950); " POLEE_BUILD_INFO; }
+// 0.4: the device normal generator's u1 is clamped below 1 (rng.hpp philox_u01f): of 2^24 u1 words the last one draws another pair.
+// 0.3 also covers the builds before and after Box-Muller moved to the hardware's log2 / sin / cos (every draw differs by ~1e-6).
+const char *polee_version(void) { return "polee_hip 0.4 (gfx950); " POLEE_BUILD_INFO; }
 
 // the host builders keep their large scratch blocks for the next sample (common.hpp HugeBlockCache)
 void polee_host_cache_trim(void)

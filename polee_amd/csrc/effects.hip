@@ -60,13 +60,13 @@ __device__ inline void fx_block(uint64_t seed, uint32_t j, uint32_t t, uint32_t 
     c[3] = 0x65666678u;  // 'effx'
     philox4x32_10(c, seed);
 }
-// element e (0..3) of the block's four N(0,1): Box-Muller on the hardware's log2 / sqrt / sin / cos as philox_randn4 (rng.hpp)
+// element e (0..3) of the block's four N(0,1): the Box-Muller pair of philox_randn4 (rng.hpp philox_box_muller) that holds it
 __device__ inline float fx_normal(const uint32_t (&c)[4], int e)
 {
     const uint32_t a = (e & 2) ? c[2] : c[0], b = (e & 2) ? c[3] : c[1];
-    const float u1 = philox_u01f(a), u2 = philox_u01f(b);
-    const float r = __builtin_amdgcn_sqrtf(-1.38629436111989061883f * __log2f(u1));
-    return r * ((e & 1) ? __builtin_amdgcn_sinf(u2) : __builtin_amdgcn_cosf(u2));
+    float zc, zs;
+    philox_box_muller(a, b, zc, zs);
+    return (e & 1) ? zs : zc;
 }
 __device__ inline float fx_noise_w(const FxArgs &A, int i, int j, int t)
 {

@@ -3,6 +3,7 @@
 // two are fused into vi_sample / vi_update (vi_fused.hpp); these exist so that callers of the individual
 // reference functions (alt approximations, tests) find them behind the same C ABI.
 #include "common.hpp"
+#include "rng.hpp"
 #include "scan.hpp"
 
 namespace polee {
@@ -184,6 +185,27 @@ __global__ void fast_log_kernel(double *x, int64_t count)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) x[i] = fast_log(x[i]);
+}
+// test hooks of the normal generator (rng.hpp): a thread per Philox block
+__global__ void debug_philox_kernel(uint64_t seed, const uint32_t *counters, int64_t count, uint32_t *words)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    uint32_t c[4] = {counters[4 * i], counters[4 * i + 1], counters[4 * i + 2], counters[4 * i + 3]};
+    philox4x32_10(c, seed);
+    for (int e = 0; e < 4; ++e) words[4 * i + e] = c[e];
+}
+__global__ void debug_box_muller_kernel(int which, const uint32_t *words, int64_t count, float *z)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t w[4] = {words[4 * i], words[4 * i + 1], words[4 * i + 2], words[4 * i + 3]};
+    float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (which == 0)
+        philox_box_muller4(w, q);
+    else
+        q[0] = philox_box_muller_libm(w[0], w[1]);
+    for (int e = 0; e < 4; ++e) z[4 * i + e] = q[e];
 }
 }  // namespace polee
 
@@ -384,6 +406,38 @@ polee_status polee_debug_fast_log(polee_ctx *ctx, const double *x, int64_t count
         hipLaunchKernelGGL(fast_log_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, d.p, count);
         POLEE_KERNEL_CHECK(ctx);
         return d.download(ctx, out, (size_t)count);
+    });
+}
+
+// test hook (include/polee_hip_debug.h): the device's Philox4x32-10 block of every counter under the key `seed`
+polee_status polee_debug_philox(polee_ctx *ctx, uint64_t seed, const uint32_t *counters, int64_t count, uint32_t *words)
+{
+    return ctx_entry(ctx, "polee_debug_philox", [&]() -> polee_status {
+        if (!counters || !words) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_philox: null argument");
+        if (count < 1 || count > ((int64_t)1 << 28)) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_philox: count outside [1, 2^28]");
+        DevBuf<uint32_t> d_c, d_w;
+        POLEE_TRY(d_c.upload(ctx, counters, 4 * (size_t)count));
+        POLEE_TRY(d_w.alloc(ctx, 4 * (size_t)count));
+        hipLaunchKernelGGL(debug_philox_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, seed, d_c.p, count, d_w.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return d_w.download(ctx, words, 4 * (size_t)count);
+    });
+}
+
+// test hook (include/polee_hip_debug.h): the normals of every block of words, through the inline functions the production kernels call
+polee_status polee_debug_box_muller(polee_ctx *ctx, int32_t which, const uint32_t *words, int64_t count, float *z)
+{
+    return ctx_entry(ctx, "polee_debug_box_muller", [&]() -> polee_status {
+        if (!words || !z) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_box_muller: null argument");
+        if (which != 0 && which != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_box_muller: which must be 0 (rng.hpp) or 1 (approx.hip)");
+        if (count < 1 || count > ((int64_t)1 << 28)) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_debug_box_muller: count outside [1, 2^28]");
+        DevBuf<uint32_t> d_w;
+        DevBuf<float> d_z;
+        POLEE_TRY(d_w.upload(ctx, words, 4 * (size_t)count));
+        POLEE_TRY(d_z.alloc(ctx, 4 * (size_t)count));
+        hipLaunchKernelGGL(debug_box_muller_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, (int)which, d_w.p, count, d_z.p);
+        POLEE_KERNEL_CHECK(ctx);
+        return d_z.download(ctx, z, 4 * (size_t)count);
     });
 }
 

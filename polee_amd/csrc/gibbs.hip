@@ -47,7 +47,9 @@ __device__ inline float gb_uniform(uint64_t seed, uint32_t index, uint32_t chain
 {
     uint32_t c[4] = {index, chain, sweep, GB_TAG_ASSIGN};
     philox4x32_10(c, seed);
-    return philox_u01f(c[0]);
+    // the unclamped uniform (rng.hpp): exactly 1.0f can occur here, once in 2^24 words.  The pick below still ends at the last entry
+    // then: rr = 1.0f * sum and the last cs are the same f32 sum, so rr <= cs holds (tests/test_gibbs_host.py restates it bit for bit)
+    return philox_u01f_raw(c[0]);
 }
 
 // One (fragment, chain) per lane; CL = 2^cl_log lanes per fragment (lanes c >= C idle).  Compiled with -ffp-contract=off: the
