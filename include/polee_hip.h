@@ -622,8 +622,9 @@ polee_status polee_regression_fit(polee_regression *reg, int32_t niter, uint64_t
  *   parallel_intersection_loop (src/rnaseq_sample.jl:58-121), fragmentlength (src/transcripts.jl:273-446),
  *   effective_length / condfragprob (src/fragmodel.jl:119-169), sortperm + compact_indexes! + sparse
  *   (src/rnaseq_sample.jl:126-157, 470-489).
- * BAM / GFF parsing and read assignment stay upstream; the bias model is trained here from training fragments
- * (polee_bias_train_*, below).  Coordinates are 1-based inclusive.
+ * BAM / GFF parsing stays upstream; the fragment model is estimated here from the alignment pairs themselves
+ * (polee_fragmodel_estimate, polee_read_assign, below) and the bias model trained from the assigned fragments
+ * (polee_bias_train_*).  Coordinates are 1-based inclusive.
  *   transcripts  j = 0..n-1 (= t.metadata.id - 1): sequence id, strand (+1 / -1), exons ascending and disjoint
  *   fragments    i = 0..m-1 = alignment pairs: sequence id, strand, the LEFTMOST mate (m1) and, for paired-end reads,
  *                the other one (m2; m2_left == 0: single-end); per mate its CIGAR as (operation code, length) pairs
@@ -728,6 +729,36 @@ polee_status polee_loglik_create_from_xbuild(polee_ctx *ctx, const polee_xbuild 
 /* ... and the tree (polee_hclust_parallel_device) from the same result on the device: alignments -> X -> tree + layout -> fit
  * without X visiting the host (the columns of X by a stable sort of the result's rows by transcript). */
 polee_status polee_hclust_parallel_device_from_xbuild(polee_ctx *ctx, const polee_xbuild *xb, int32_t *node_parent_idxs, int32_t *node_js);
+
+/* ---- the fragment model from the alignment pairs themselves ------------------------------------------
+ * A fragment is one alignment pair of one read (there are no read ids: one pair is one read).
+ *
+ * polee_fragmodel_estimate: the counts of SimplisticFragModel(rs, ts) (src/fragmodel.jl:35-67).  Over every (transcript, fragment)
+ * pair of the same sequence whose transcript contains the fragment's span and is compatible with it (fragmentlength is not
+ * nothing): counts[0] = such pairs, counts[1] = pairs of equal strands, counts[2] = pairs whose fragment has the other of +1 / -1
+ * (any other fragment strand is STRAND_BOTH: neither); per fragment the MINIMUM of its positive lengths (the reference keys that
+ * minimum by hash(alnpr): here the pair itself); counts[3] = fragments whose minimum is above 2000, hist[l-1] = fragments whose
+ * minimum is l <= 2000, min_fraglen[i] = the minimum (0: none; host array [m] or NULL).  Integer reductions only: the result does
+ * not depend on scheduling.  The pmf / cdf / median and the strand specificity are host arithmetic on these (polee_amd/fragmodel.py). */
+polee_status polee_fragmodel_estimate(polee_ctx *ctx, const polee_xb_transcripts *transcripts, const polee_xb_fragments *fragments,
+                                      int64_t *counts, int64_t *hist, int64_t *min_fraglen_or_null);
+/* polee_read_assign: one transcript per row of an xbuild result (= per read) and the fragment's interval on it
+ * (src/rnaseq_sample.jl:346-373, genomic_to_transcriptomic src/transcripts.jl:452-517, src/fragmodel.jl:205-246).  transcripts /
+ * fragments: what xb was built from.  tseq_ptr [n+1]: the transcripts' lengths (tseq_ptr[0] = 0, lengths = exonic lengths).
+ * m1_reverse [m]: as in polee_xb_biasmodel (NULL only when every fragment is paired).  xs [n]: the mixture.
+ * mode 0, the draw: z_sum = the f64 sum, in the row's order, of the f32 products xs[j] * nzval; r = the 53-bit uniform of words
+ * 0, 1 of the Philox block (key seed, counter (low word of i, high word of i, 0, 0x66617373 'fass'), i = the row's fragment); the
+ * entries in ascending transcript order with zj = product / z_sum: the first zj > r is taken, otherwise r -= zj; the last entry
+ * takes what is left.  mode 1, as the reference is written (its loop has no break and its condition holds at the last entry):
+ * the LAST entry of every row; xs (may be NULL) and seed are not used.
+ * Outputs, host arrays [rows of xb]: transcript (0-based), tpos (1-based, transcript orientation) and fraglen of
+ * genomic_to_transcriptomic(t, rs, alnpr, fallback_fraglen) -- an empty interval is tpos = 0, fraglen = 0 --, flags: bit 0 the
+ * pair has both mates (its length was observed, not guessed), bit 1 strand match, bit 2 strand mismatch (bits 1, 2 only with a
+ * non-empty interval). */
+polee_status polee_read_assign(polee_ctx *ctx, const polee_xbuild *xb, const polee_xb_transcripts *transcripts,
+                               const polee_xb_fragments *fragments, const int64_t *tseq_ptr, const uint8_t *m1_reverse_or_null,
+                               const float *xs, uint64_t seed, int32_t mode, int32_t fallback_fraglen, int32_t *transcript,
+                               int64_t *tpos, int32_t *fraglen, uint8_t *flags);
 
 /* ---- Gibbs sampler of the exact posterior (src/gibbs.jl; `polee debug-sample`, src/main.jl:925-957) -----------------------------
  * Collapsed Gibbs sampling over fragment assignments: draws of the transcript mixture from p(y | X) under a Dirichlet(1) prior,

@@ -1118,6 +1118,72 @@ function build_likelihood_matrix_biased(ctx::Context, T, F, pmf::Vector{Float32}
     end
 end
 
+# ---- the fragment model from the alignment pairs themselves (DESIGN.md section 3.18) ---------------------------------------------
+"""
+    fragmodel_estimate(ctx, T, F; min_fraglen=false)
+
+The counts of SimplisticFragModel(rs, ts) (src/fragmodel.jl:35-67; polee_fragmodel_estimate): (counts, hist[, min_fraglen]) with
+counts = [compatible pairs, strand matches, strand mismatches, fragments longer than 2000] and hist[l] = fragments whose smallest
+positive length is l.  T, F as build_likelihood_matrix takes them.
+"""
+function fragmodel_estimate(ctx::Context, T, F; min_fraglen::Bool=false)
+    n = length(T.seq); m = length(F.seq)
+    counts, hist = zeros(Int64, 4), zeros(Int64, 2000)
+    mins = min_fraglen ? zeros(Int64, m) : nothing
+    GC.@preserve T F counts hist mins begin
+        ts = XbTranscripts(n, pointer(T.seq), pointer(T.strand), pointer(T.exon_ptr), pointer(T.exon_first), pointer(T.exon_last))
+        fs = XbFragments(m, pointer(F.seq), pointer(F.strand), pointer(F.m1_left), pointer(F.m1_right), pointer(F.m2_left),
+                         pointer(F.m2_right), pointer(F.m1_is_flag16), pointer(F.cig1_ptr), pointer(F.cig2_ptr), pointer(F.cig_op),
+                         pointer(F.cig_len))
+        check(ccall((:polee_fragmodel_estimate, LIB), Cint, (Ptr{Cvoid}, Ref{XbTranscripts}, Ref{XbFragments}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                    ctx.h, ts, fs, counts, hist, mins === nothing ? Ptr{Int64}(C_NULL) : pointer(mins)), ctx.h)
+    end
+    return min_fraglen ? (counts, hist, mins) : (counts, hist)
+end
+
+"""
+    read_assign(ctx, T, F, pmf, cdf, median, tseq_ptr, xs; strand_specificity, alt_frag_model, m1_reverse, seed, mode, fallback_fraglen)
+
+X of the fragments under the SimplisticFragModel (polee_xbuild_run), then one transcript per row and the fragment's interval on it
+(polee_read_assign; src/rnaseq_sample.jl:346-373, src/transcripts.jl:452-517).  mode 0: drawn in proportion to xs[j] X[i, j]; mode 1: the
+last entry of every row, as the reference is written.  Returns (row_fragment, transcript (0-based), tpos, fraglen, flags).
+"""
+function read_assign(ctx::Context, T, F, pmf::Vector{Float32}, cdf::Vector{Float32}, median::Integer, tseq_ptr::Vector{Int64},
+                     xs::Vector{Float32}; strand_specificity::Real=0.9, alt_frag_model::Bool=false, m1_reverse=nothing, seed::Integer=0,
+                     mode::Integer=0, fallback_fraglen::Integer=150)
+    n = length(T.seq); m = length(F.seq)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve T F pmf cdf tseq_ptr xs m1_reverse begin
+        ts = XbTranscripts(n, pointer(T.seq), pointer(T.strand), pointer(T.exon_ptr), pointer(T.exon_first), pointer(T.exon_last))
+        fs = XbFragments(m, pointer(F.seq), pointer(F.strand), pointer(F.m1_left), pointer(F.m1_right), pointer(F.m2_left),
+                         pointer(F.m2_right), pointer(F.m1_is_flag16), pointer(F.cig1_ptr), pointer(F.cig2_ptr), pointer(F.cig_op),
+                         pointer(F.cig_len))
+        ms = XbFragModel(pointer(pmf), pointer(cdf), median, strand_specificity, alt_frag_model)
+        check(ccall((:polee_xbuild_run, LIB), Cint, (Ptr{Cvoid}, Ref{XbTranscripts}, Ref{XbFragments}, Ref{XbFragModel}, Ref{Ptr{Cvoid}}),
+                    ctx.h, ts, fs, ms, out), ctx.h)
+        h = out[]
+        try
+            rows = Ref{Int64}(0)
+            check(ccall((:polee_xbuild_sizes, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                        h, rows, C_NULL, C_NULL, C_NULL, C_NULL), ctx.h)
+            rowfrag, transcript, tpos = Vector{Int64}(undef, rows[]), Vector{Int32}(undef, rows[]), Vector{Int64}(undef, rows[])
+            fraglen, flags = Vector{Int32}(undef, rows[]), Vector{UInt8}(undef, rows[])
+            GC.@preserve rowfrag transcript tpos fraglen flags begin
+                check(ccall((:polee_xbuild_get, LIB), Cint, (Ptr{Cvoid}, Ptr{UInt64}, Ptr{UInt32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int64}),
+                            h, C_NULL, C_NULL, C_NULL, C_NULL, rowfrag), ctx.h)
+                check(ccall((:polee_read_assign, LIB), Cint,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Ref{XbTranscripts}, Ref{XbFragments}, Ptr{Int64}, Ptr{UInt8}, Ptr{Float32}, UInt64, Int32, Int32,
+                             Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{UInt8}),
+                            ctx.h, h, ts, fs, tseq_ptr, m1_reverse === nothing ? Ptr{UInt8}(C_NULL) : pointer(m1_reverse), xs, UInt64(seed), mode,
+                            fallback_fraglen, transcript, tpos, fraglen, flags), ctx.h)
+            end
+            return rowfrag, transcript, tpos, fraglen, flags
+        finally
+            ccall((:polee_xbuild_destroy, LIB), Cvoid, (Ptr{Cvoid},), h)
+        end
+    end
+end
+
 "fast_log of the tree kernels (csrc/scan.hpp), element-wise on the device: the tests compare it with Base.log"
 function debug_fast_log(ctx::Context, x::Vector{Float64})
     out = similar(x)

@@ -29,6 +29,8 @@ would use).  Names, argument meaning and error behaviour follow the reference:
   (`polee fit-tree`: python -m polee_amd.fit_tree)                           src/main.jl:638-660
   train_bias_model / fragment_length_model (BiasModel, BiasedFragModel)      src/bias.jl:266-828, src/fragmodel.jl:263-343
   (python -m polee_amd.bias)
+  train_fragment_model / estimate_simplistic / assign_reads                   src/rnaseq_sample.jl:330-380, src/fragmodel.jl:35-113, :186-293
+  (python -m polee_amd.fragmodel)
 
 All numerics run in libpolee_hip.so on the GPU; nothing here computes on the CPU.
 """
@@ -81,6 +83,9 @@ def __getattr__(name):
                 "bias_training_examples", "bias_candidate_losses"):
         from . import bias
         return getattr(bias, name)
+    if name in ("train_fragment_model", "estimate_simplistic", "assign_reads", "subsample_fragments", "fragment_length_model_from_hist"):
+        from . import bias, fragmodel
+        return getattr(bias if name == "fragment_length_model_from_hist" else fragmodel, name)
     if name in ("IsoformEffects", "estimate_isoform_effect_sizes", "build_design_matrix", "gene_map", "gene_initial_values",
                 "write_isoform_regression_effects", "write_aitchison_results", "write_expression", "load_kallisto_estimates"):
         from . import regression

@@ -108,7 +108,7 @@ def lib():
                      "polee_approx_destroy", "polee_debug_psell_free", "polee_comm_destroy", "polee_devx_destroy",
                      "polee_gibbs_destroy", "polee_em_destroy", "polee_altvi_destroy", "polee_bias_train_destroy",
                      "polee_regression_destroy", "polee_effects_destroy", "polee_sampler_destroy", "polee_classify_destroy",
-                     "polee_tsne_destroy", "polee_forest_destroy"):
+                     "polee_tsne_destroy", "polee_forest_destroy", "polee_xbuild_destroy"):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         L.polee_vi_default_opts.restype = None
@@ -148,6 +148,10 @@ def lib():
         L.polee_bias_train_get_examples.argtypes = [C.c_void_p, i64p, i64p, u64p, u64p, f64p, i64p]
         L.polee_bias_train_get_trace.argtypes = [C.c_void_p, C.c_int32, i32p, i32p, f64p]
         L.polee_bias_train_candidates.argtypes = [C.c_void_p, C.c_int32, i32p, f64p, f64p]
+        # the fragment model from the alignment pairs (polee_amd/fragmodel.py)
+        L.polee_fragmodel_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, i64p, i64p, i64p]
+        L.polee_read_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64p, u8p, f32p, C.c_uint64, C.c_int32, C.c_int32,
+                                        i32p, i64p, i32p, u8p]
         _lib = L
     return _lib
 

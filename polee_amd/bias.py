@@ -179,14 +179,23 @@ def fragment_length_model(fraglens):
     in f32 over two halves in sequence -- Julia's own order is its SIMD loop's).  high_prob_fraglens: the 200 most probable lengths in a
     STABLE descending sort (equal probabilities: the shorter length first, as sortperm(rev=true) leaves them)."""
     fl = np.asarray(fraglens, np.int64).ravel()
-    if len(fl) < MIN_FRAG_LEN_COUNT:
+    hist = np.bincount(fl[(fl >= 1) & (fl <= MAX_FRAG_LEN)] - 1, minlength=MAX_FRAG_LEN)
+    return fragment_length_model_from_hist(hist, len(fl))
+
+
+def fragment_length_model_from_hist(hist, num_observations=None):
+    """The same from a histogram: hist[l-1] = observations of length l <= 2000; num_observations: what is held against the 1000 of the
+    fallback (fragment_length_model: every length it was given, SimplisticFragModel: those <= 2000 = hist.sum(), the default)."""
+    hist = np.asarray(hist, np.int64).ravel()
+    assert hist.shape == (MAX_FRAG_LEN,)
+    if (int(hist.sum()) if num_observations is None else int(num_observations)) < MIN_FRAG_LEN_COUNT:
         x = np.arange(1, MAX_FRAG_LEN + 1, dtype=np.float64)
         z = (x - FALLBACK_FRAGLEN_MEAN) / FALLBACK_FRAGLEN_SD
         pmf = (np.exp(-(z * z) / 2) * 0.3989422804014326779 / FALLBACK_FRAGLEN_SD).astype(np.float32)
         half = MAX_FRAG_LEN // 2
         total = np.float32(np.cumsum(pmf[:half], dtype=np.float32)[-1] + np.cumsum(pmf[half:], dtype=np.float32)[-1])
     else:
-        counts = 1 + np.bincount(fl[(fl >= 1) & (fl <= MAX_FRAG_LEN)] - 1, minlength=MAX_FRAG_LEN)
+        counts = 1 + hist
         pmf = counts.astype(np.float32)
         total = np.float32(int(counts.sum()))
     pmf = (pmf / total).astype(np.float32)

@@ -40,6 +40,24 @@ __device__ inline double wave_sum_to_lane63(double v)
     v = dpp_add<0x143, 0xc, 0xf>(v);
     return v;
 }
+// the same for 64-bit integers (xbuild.hip's counts): exact, so the order of the additions does not show
+template <int CTRL, int ROW_MASK, int BANK_MASK>
+__device__ inline uint64_t dpp_add(uint64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, BANK_MASK, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, BANK_MASK, true);
+    return v + (((uint64_t)hi << 32) | (uint64_t)lo);
+}
+__device__ inline uint64_t wave_sum_to_lane63(uint64_t v)
+{
+    v = dpp_add<0x111, 0xf, 0xf>(v);
+    v = dpp_add<0x112, 0xf, 0xf>(v);
+    v = dpp_add<0x114, 0xf, 0xf>(v);
+    v = dpp_add<0x118, 0xf, 0xf>(v);
+    v = dpp_add<0x142, 0xa, 0xf>(v);
+    v = dpp_add<0x143, 0xc, 0xf>(v);
+    return v;
+}
 // the same for N values at once, step-major so that the N dependency chains interleave
 template <int N>
 __device__ inline void wave_sum_to_lane63_n(float (&v)[N])

@@ -11,7 +11,10 @@
 // Round 4: the same with the reference's DEFAULT BiasedFragModel given a TRAINED bias model (polee_xbuild_run_biased): the
 // transcripts' bias vectors (compute_transcript_bias!, bias.jl:834-858), the biased effective lengths (fragmodel.jl:372-410)
 // and condfragprob with the fragment's interval on the transcript (fragmodel.jl:413-445, transcripts.jl:452-538).
-// BAM / GFF parsing, TRAINING of the bias model and read assignment stay upstream (out of scope).
+// BAM / GFF parsing stays upstream (out of scope); the bias model is trained by bias_train.hip.
+// The fragment model from the alignment pairs themselves: polee_fragmodel_estimate -- the counts of
+// SimplisticFragModel(rs, ts) (src/fragmodel.jl:35-67) -- and polee_read_assign -- one transcript per read and the fragment's
+// interval on it (src/rnaseq_sample.jl:346-373, src/transcripts.jl:452-517, src/fragmodel.jl:205-246) --, at the end of this file.
 //
 // Formulation: the reference joins two interval trees per sequence on threads.  Here a thread owns a FRAGMENT: the
 // transcripts of its sequence are sorted by first base (once, on the host: a few hundred thousand of them) with a running
@@ -23,8 +26,10 @@
 // Precision: as the reference -- Float32 products for a fragment on the transcript's strand, Float64 when it is not
 // (`1.0 - strand_specificity`), the effective length accumulated in Float32 in sequence (one thread per transcript, so
 // that the sum is the same sum); see oracle/xbuild_oracle.c for the quirks kept and not kept.
+#include "binomial.hpp"
 #include "common.hpp"
 #include "scan.hpp"
+#include "wave.hpp"
 
 #include <algorithm>
 #include <numeric>
@@ -390,17 +395,15 @@ __device__ inline int64_t xb_g2t_pos(const XbView &v, int32_t j, int64_t positio
     if (v.t_strand[j] < 0) tpos = exonic_length(v, j) - tpos + 1;
     return tpos;
 }
-// condfragprob(::BiasedFragModel, ...) (fragmodel.jl:413-445) with genomic_to_transcriptomic (transcripts.jl:452-517)
-__device__ inline float condfragprob_biased(const XbView &v, int32_t j, int64_t i)
+// genomic_to_transcriptomic(t, rs, alnpr, fraglen_median) (transcripts.jl:452-517) behind its call of fragmentlength: fraglen comes in
+// as that call's result (>= 0) and leaves, with tpos, as the fragment's interval tpos .. tpos + fraglen - 1 on the transcript of
+// tlen bases; false = the interval is empty
+__device__ inline bool xb_frag_interval(const XbView &v, int32_t j, int64_t i, int64_t fraglen_median, int64_t tlen, int64_t &fraglen, int64_t &tpos)
 {
-    int64_t fraglen = fragmentlength(v, j, i);
-    if (fraglen < 0) return 0.0f;
     if (fraglen <= 0) {
-        fraglen = v.fraglen_median;
-        if (fraglen <= 0) return 0.0f;
+        fraglen = fraglen_median;
+        if (fraglen <= 0) return false;
     }
-    const int64_t off = v.tseq_ptr[j], tlen = v.tseq_ptr[j + 1] - off;
-    int64_t tpos;
     if (v.m2_left[i] > 0) {
         const int64_t lmin = min(v.m1_left[i], v.m2_left[i]), rmax = max(v.m1_right[i], v.m2_right[i]);
         tpos = xb_g2t_pos(v, j, v.t_strand[j] > 0 ? lmin : rmax);
@@ -414,7 +417,16 @@ __device__ inline float condfragprob_biased(const XbView &v, int32_t j, int64_t 
         tpos = 1;
     }
     if (tpos + fraglen - 1 > tlen) fraglen = tlen - tpos + 1;
-    if (fraglen <= 0) return 0.0f;
+    return fraglen > 0;
+}
+// condfragprob(::BiasedFragModel, ...) (fragmodel.jl:413-445)
+__device__ inline float condfragprob_biased(const XbView &v, int32_t j, int64_t i)
+{
+    int64_t fraglen = fragmentlength(v, j, i);
+    if (fraglen < 0) return 0.0f;
+    const int64_t off = v.tseq_ptr[j], tlen = v.tseq_ptr[j + 1] - off;
+    int64_t tpos;
+    if (!xb_frag_interval(v, j, i, v.fraglen_median, tlen, fraglen, tpos)) return 0.0f;
     const int64_t a = tpos, b = tpos + fraglen - 1;
     const float fraglenpr = fraglen <= XB_MAX_FRAG_LEN ? v.pmf[fraglen - 1] : 0.0f;
     const uint8_t *seq = v.tseq + off;
@@ -428,10 +440,9 @@ __device__ inline float condfragprob_biased(const XbView &v, int32_t j, int64_t 
     return (float)__ddiv_rn(__dmul_rn(__dmul_rn(1.0 - (double)v.strand_specificity, (double)fraglenpr), (double)fragbias), (double)efflen);
 }
 
-// Transcripts containing fragment i, in descending order of their position in the sorted list; f(j, fragpr) for the kept
-// ones (finite, > MIN_FRAG_PROB: rnaseq_sample.jl:99)
-template <typename F>
-__device__ inline void for_each_entry(const XbView &v, int64_t i, F &&f)
+// Transcripts of fragment i's sequence that contain its span, in descending order of their position in the sorted list: g(j)
+template <typename G>
+__device__ inline void for_each_candidate(const XbView &v, int64_t i, G &&g)
 {
     const int32_t s = v.f_seq[i];
     if (s < 0 || s >= v.num_seq) return;
@@ -448,9 +459,17 @@ __device__ inline void for_each_entry(const XbView &v, int64_t i, F &&f)
         if (v.ord_maxlast[k] < a_last) break;  // no transcript at or before k reaches the fragment's end
         const int32_t j = v.ord[k];
         if (v.exon_last[v.exon_ptr[j + 1] - 1] < a_last) continue;  // intersect_contains (rnaseq_sample.jl:77-79)
+        g(j);
+    }
+}
+// ... f(j, fragpr) for the kept ones (finite, > MIN_FRAG_PROB: rnaseq_sample.jl:99)
+template <typename F>
+__device__ inline void for_each_entry(const XbView &v, int64_t i, F &&f)
+{
+    for_each_candidate(v, i, [&](int32_t j) {
         const float p = v.tseq ? condfragprob_biased(v, j, i) : condfragprob(v, j, i);
         if (isfinite(p) && (double)p > XB_MIN_FRAG_PROB) f(j, p);
-    }
+    });
 }
 
 __global__ void xb_count_kernel(XbView v, int64_t *__restrict__ counts)
@@ -584,6 +603,92 @@ __global__ void xb_rows_kernel(const int64_t *__restrict__ off, const int64_t *_
     }
 }
 
+// ---- the fragment model from the alignment pairs themselves --------------------------------------------
+constexpr int FM_T = 256;
+constexpr uint32_t FM_ASSIGN_TAG = 0x66617373u;  // 'fass': counter word 3 of the assignment's uniform
+
+// SimplisticFragModel(rs, ts)'s counts (fragmodel.jl:35-67), a thread per fragment.  counts [4] = compatible pairs, strand matches,
+// strand mismatches, fragments whose minimum positive length is above 2000; hist [2000] = fragments by that minimum.  Integer
+// reductions only: a wave's counts by DPP and one atomic per wave and count, the histogram in LDS and its non-zero bins flushed.
+__global__ __launch_bounds__(FM_T) void fm_estimate_kernel(XbView v, unsigned long long *__restrict__ counts, unsigned long long *__restrict__ hist,
+                                                           int64_t *__restrict__ min_fraglen)
+{
+    __shared__ uint32_t lhist[XB_MAX_FRAG_LEN];
+    for (int k = threadIdx.x; k < XB_MAX_FRAG_LEN; k += FM_T) lhist[k] = 0u;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * FM_T + threadIdx.x;
+    uint64_t c[4] = {0, 0, 0, 0};
+    if (i < v.m) {
+        const int8_t fs = v.f_strand[i];
+        int64_t mn = 0;
+        for_each_candidate(v, i, [&](int32_t j) {
+            const int64_t fl = fragmentlength(v, j, i);
+            if (fl < 0) return;
+            ++c[0];
+            if (fs == v.t_strand[j]) ++c[1];
+            else if (fs == 1 || fs == -1) ++c[2];  // (anything else: STRAND_BOTH)
+            if (fl > 0 && (mn == 0 || fl < mn)) mn = fl;
+        });
+        if (mn > XB_MAX_FRAG_LEN) c[3] = 1;
+        else if (mn > 0) atomicAdd(&lhist[mn - 1], 1u);
+        if (min_fraglen) min_fraglen[i] = mn;
+    }
+    // (every lane of the workgroup is here: the DPP sums read all 64)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint64_t t = wave_sum_to_lane63(c[k]);
+        if ((threadIdx.x & 63) == 63 && t) atomicAdd(&counts[k], (unsigned long long)t);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < XB_MAX_FRAG_LEN; k += FM_T)
+        if (lhist[k]) atomicAdd(&hist[k], (unsigned long long)lhist[k]);
+}
+
+// One transcript per row of X (rnaseq_sample.jl:346-373) and the fragment's interval on it (genomic_to_transcriptomic,
+// transcripts.jl:452-517; the flags: fragmodel.jl:221-225, :237), a thread per row.  mode 0: the draw; mode 1: the last entry.
+__global__ __launch_bounds__(FM_T) void fm_assign_kernel(XbView v, int64_t rows, const uint64_t *__restrict__ tcolptr, const uint32_t *__restrict__ cols,
+                                                         const float *__restrict__ vals, const int64_t *__restrict__ row_fragment,
+                                                         const int64_t *__restrict__ tlen_ptr, const float *__restrict__ xs, uint64_t seed, int32_t mode,
+                                                         int32_t fallback_fraglen, int32_t *__restrict__ transcript, int64_t *__restrict__ tpos_out,
+                                                         int32_t *__restrict__ fraglen_out, uint8_t *__restrict__ flags)
+{
+    const int64_t r = (int64_t)blockIdx.x * FM_T + threadIdx.x;
+    if (r >= rows) return;
+    const int64_t i = row_fragment[r];
+    const int64_t b = (int64_t)tcolptr[r] - 1, e = (int64_t)tcolptr[r + 1] - 1;  // (e > b: a row has entries)
+    int64_t pick = e - 1;
+    if (mode == 0) {
+        double z_sum = 0.0;  // Float64 += Float32 * Float32, in the row's order
+        for (int64_t p = b; p < e; ++p) z_sum = __dadd_rn(z_sum, (double)__fmul_rn(xs[cols[p] - 1u], vals[p]));
+        uint32_t c[4] = {(uint32_t)(uint64_t)i, (uint32_t)((uint64_t)i >> 32), 0u, FM_ASSIGN_TAG};
+        philox4x32_10(c, seed);
+        double u = philox_u01_53(c[0], c[1]);
+        for (int64_t p = b; p < e - 1; ++p) {
+            const double zj = __ddiv_rn((double)__fmul_rn(xs[cols[p] - 1u], vals[p]), z_sum);
+            if (zj > u) {
+                pick = p;
+                break;
+            }
+            u = __dsub_rn(u, zj);
+        }
+    }
+    const int32_t j = (int32_t)(cols[pick] - 1u);
+    int64_t fl = fragmentlength(v, j, i), tp = 0;
+    uint8_t fg = v.m2_left[i] > 0 ? 1 : 0;
+    if (fl >= 0 && xb_frag_interval(v, j, i, fallback_fraglen, tlen_ptr[j + 1] - tlen_ptr[j], fl, tp)) {
+        const int8_t fs = v.f_strand[i];
+        if (fs == v.t_strand[j]) fg |= 2;
+        else if (fs == 1 || fs == -1) fg |= 4;
+    } else {
+        fl = 0;
+        tp = 0;
+    }
+    transcript[r] = j;
+    tpos_out[r] = tp;
+    fraglen_out[r] = (int32_t)fl;
+    flags[r] = fg;
+}
+
 }  // namespace polee
 
 using namespace polee;
@@ -614,24 +719,57 @@ polee_status xbuild_device_view(const polee_xbuild *xb, polee_ctx **ctx, int64_t
     *tnzval = xb->d_vals.p;
     return POLEE_OK;
 }
-}  // namespace polee
 
-extern "C" {
-
-static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcripts *T, const polee_xb_fragments *F, const polee_xb_fragmodel *M,
-                              const polee_xb_biasmodel *B, polee_xbuild **out)
+// The transcripts and fragments of a call, checked and on the device, with the transcripts of every sequence sorted by first base:
+// what polee_xbuild_run*, polee_fragmodel_estimate and polee_read_assign share.  `who` names the entry point in the messages.
+struct XbInputs {
+    int32_t n = 0, num_seq = 0;
+    int64_t m = 0;
+    DevBuf<int32_t> d_tseq, d_ord, d_fseq, d_ciglen;
+    DevBuf<int8_t> d_tstrand, d_fstrand;
+    DevBuf<int64_t> d_eptr, d_ef, d_el, d_ofirst, d_omax, d_seqptr, d_m1l, d_m1r, d_m2l, d_m2r, d_c1, d_c2;
+    DevBuf<uint8_t> d_flag16, d_cigop;
+    polee_status load(polee_ctx *ctx, const char *who, const polee_xb_transcripts *T, const polee_xb_fragments *F);
+    void fill(XbView &v) const
+    {
+        v.n = n;
+        v.t_seq = d_tseq.p;
+        v.t_strand = d_tstrand.p;
+        v.exon_ptr = d_eptr.p;
+        v.exon_first = d_ef.p;
+        v.exon_last = d_el.p;
+        v.ord = d_ord.p;
+        v.ord_first = d_ofirst.p;
+        v.ord_maxlast = d_omax.p;
+        v.seq_ptr = d_seqptr.p;
+        v.num_seq = num_seq;
+        v.m = m;
+        v.f_seq = d_fseq.p;
+        v.f_strand = d_fstrand.p;
+        v.m1_left = d_m1l.p;
+        v.m1_right = d_m1r.p;
+        v.m2_left = d_m2l.p;
+        v.m2_right = d_m2r.p;
+        v.m1_is_flag16 = d_flag16.p;
+        v.cig1_ptr = d_c1.p;
+        v.cig2_ptr = d_c2.p;
+        v.cig_op = d_cigop.p;
+        v.cig_len = d_ciglen.p;
+    }
+};
+polee_status XbInputs::load(polee_ctx *ctx, const char *who, const polee_xb_transcripts *T, const polee_xb_fragments *F)
 {
-    POLEE_TRY(use_device(ctx));
-    if (!T || !F || !M || !out) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run: null argument");
-    if (T->n < 1 || F->m < 0 || !T->seq || !T->strand || !T->exon_ptr || !T->exon_first || !T->exon_last || !M->fraglen_pmf || !M->fraglen_cdf)
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run: bad argument");
-    const int32_t n = T->n;
-    const int64_t m = F->m, nex = T->exon_ptr[n];
+    if (!T || !F) return fail(ctx, POLEE_ERR_BAD_ARG, "%s: null argument", who);
+    if (T->n < 1 || F->m < 0 || !T->seq || !T->strand || !T->exon_ptr || !T->exon_first || !T->exon_last)
+        return fail(ctx, POLEE_ERR_BAD_ARG, "%s: bad argument", who);
+    n = T->n;
+    m = F->m;
+    const int64_t nex = T->exon_ptr[n];
     // fragments: every array present, mates ordered as the reference orders them itself (a1 = the leftmost mate,
     // transcripts.jl:288-297 -- a caller holding them in BAM order swaps first, polee_amd/xbuild.py does), intervals and
     // CIGAR ranges well formed -- the kernels index with them
     if (m > 0 && (!F->seq || !F->strand || !F->m1_left || !F->m1_right || !F->m2_left || !F->m2_right || !F->m1_is_flag16 || !F->cig1_ptr))
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run: a fragment array is null (only cig2_ptr may be: all single-end)");
+        return fail(ctx, POLEE_ERR_BAD_ARG, "%s: a fragment array is null (only cig2_ptr may be: all single-end)", who);
     std::vector<int64_t> cig2_zero;  // cig2_ptr == NULL: no second mate has CIGAR operations
     const int64_t *cig2 = F->cig2_ptr;
     if (m > 0 && !cig2) {
@@ -640,7 +778,7 @@ static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcr
     }
     const int64_t ncig = m > 0 ? std::max(F->cig1_ptr[m], cig2[m]) : 0;
     if (m > 0 && (F->cig1_ptr[0] < 0 || cig2[0] < 0 || (ncig > 0 && (!F->cig_op || !F->cig_len))))
-        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run: bad CIGAR offsets");
+        return fail(ctx, POLEE_ERR_BAD_ARG, "%s: bad CIGAR offsets", who);
     {
         std::atomic<int> bad{0};
         std::atomic<int64_t> where{-1};
@@ -670,10 +808,10 @@ static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcr
                                           "m1 must be the LEFTMOST mate (the reference orders the mates by leftpos, transcripts.jl:288-297)",
                                           "CIGAR offsets are not monotone (or a single-end fragment has operations for a second mate)",
                                           "CIGAR operation out of range or negative length"};
-        if (bad) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run: fragment %lld: %s", (long long)where.load(), msg[bad.load()]);
+        if (bad) return fail(ctx, POLEE_ERR_BAD_ARG, "%s: fragment %lld: %s", who, (long long)where.load(), msg[bad.load()]);
     }
     // transcripts: every one needs exons, ascending and disjoint
-    int32_t num_seq = 0;
+    num_seq = 0;
     for (int32_t j = 0; j < n; ++j) {
         if (T->exon_ptr[j + 1] <= T->exon_ptr[j]) return fail(ctx, POLEE_ERR_BAD_ARG, "transcript %d has no exons", j);
         for (int64_t k = T->exon_ptr[j]; k < T->exon_ptr[j + 1]; ++k)
@@ -699,6 +837,36 @@ static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcr
         ++seq_ptr[(size_t)T->seq[j] + 1];
     }
     for (int32_t s = 0; s < num_seq; ++s) seq_ptr[(size_t)s + 1] += seq_ptr[(size_t)s];
+    polee_status s = POLEE_OK;
+    auto A = [&](polee_status r) {
+        if (s == POLEE_OK) s = r;
+    };
+    A(d_tseq.upload(ctx, T->seq, (size_t)n)); A(d_tstrand.upload(ctx, T->strand, (size_t)n));
+    A(d_eptr.upload(ctx, T->exon_ptr, (size_t)n + 1)); A(d_ef.upload(ctx, T->exon_first, (size_t)nex)); A(d_el.upload(ctx, T->exon_last, (size_t)nex));
+    A(d_ord.upload(ctx, ord)); A(d_ofirst.upload(ctx, ofirst)); A(d_omax.upload(ctx, omax)); A(d_seqptr.upload(ctx, seq_ptr));
+    A(d_fseq.upload(ctx, F->seq, (size_t)m)); A(d_fstrand.upload(ctx, F->strand, (size_t)m));
+    A(d_m1l.upload(ctx, F->m1_left, (size_t)m)); A(d_m1r.upload(ctx, F->m1_right, (size_t)m));
+    A(d_m2l.upload(ctx, F->m2_left, (size_t)m)); A(d_m2r.upload(ctx, F->m2_right, (size_t)m));
+    A(d_flag16.upload(ctx, F->m1_is_flag16, (size_t)m));
+    A(d_c1.upload(ctx, F->cig1_ptr, (size_t)m + 1)); A(d_c2.upload(ctx, cig2, (size_t)m + 1));
+    A(d_cigop.upload(ctx, F->cig_op, (size_t)ncig)); A(d_ciglen.upload(ctx, F->cig_len, (size_t)ncig));
+    return s;
+}
+}  // namespace polee
+
+extern "C" {
+
+static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcripts *T, const polee_xb_fragments *F, const polee_xb_fragmodel *M,
+                              const polee_xb_biasmodel *B, polee_xbuild **out)
+{
+    POLEE_TRY(use_device(ctx));
+    if (!T || !F || !M || !out) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run: null argument");
+    if (T->n < 1 || F->m < 0 || !T->seq || !T->strand || !T->exon_ptr || !T->exon_first || !T->exon_last || !M->fraglen_pmf || !M->fraglen_cdf)
+        return fail(ctx, POLEE_ERR_BAD_ARG, "polee_xbuild_run: bad argument");
+    XbInputs in;
+    POLEE_TRY(in.load(ctx, "polee_xbuild_run", T, F));
+    const int32_t n = in.n;
+    const int64_t m = in.m;
 
     // the trained bias model (BiasedFragModel): tables present and consistent with the transcripts
     int64_t total_bases = 0;
@@ -738,24 +906,12 @@ static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcr
     xb->n = n;
     xb->m = m;
     ctx_retain(ctx);
-    DevBuf<int32_t> d_tseq, d_ord, d_fseq, d_ciglen;
-    DevBuf<int8_t> d_tstrand, d_fstrand;
-    DevBuf<int64_t> d_eptr, d_ef, d_el, d_ofirst, d_omax, d_seqptr, d_m1l, d_m1r, d_m2l, d_m2r, d_c1, d_c2, d_counts, d_off, d_rowid, d_tmp;
-    DevBuf<uint8_t> d_flag16, d_cigop;
+    DevBuf<int64_t> d_counts, d_off, d_rowid, d_tmp;
     DevBuf<float> d_pmf, d_cdf;
     polee_status s = POLEE_OK;
     auto A = [&](polee_status r) {
         if (s == POLEE_OK) s = r;
     };
-    A(d_tseq.upload(ctx, T->seq, (size_t)n)); A(d_tstrand.upload(ctx, T->strand, (size_t)n));
-    A(d_eptr.upload(ctx, T->exon_ptr, (size_t)n + 1)); A(d_ef.upload(ctx, T->exon_first, (size_t)nex)); A(d_el.upload(ctx, T->exon_last, (size_t)nex));
-    A(d_ord.upload(ctx, ord)); A(d_ofirst.upload(ctx, ofirst)); A(d_omax.upload(ctx, omax)); A(d_seqptr.upload(ctx, seq_ptr));
-    A(d_fseq.upload(ctx, F->seq, (size_t)m)); A(d_fstrand.upload(ctx, F->strand, (size_t)m));
-    A(d_m1l.upload(ctx, F->m1_left, (size_t)m)); A(d_m1r.upload(ctx, F->m1_right, (size_t)m));
-    A(d_m2l.upload(ctx, F->m2_left, (size_t)m)); A(d_m2r.upload(ctx, F->m2_right, (size_t)m));
-    A(d_flag16.upload(ctx, F->m1_is_flag16, (size_t)m));
-    A(d_c1.upload(ctx, F->cig1_ptr, (size_t)m + 1)); A(d_c2.upload(ctx, cig2, (size_t)m + 1));
-    A(d_cigop.upload(ctx, F->cig_op, (size_t)ncig)); A(d_ciglen.upload(ctx, F->cig_len, (size_t)ncig));
     A(d_pmf.upload(ctx, M->fraglen_pmf, (size_t)XB_MAX_FRAG_LEN)); A(d_cdf.upload(ctx, M->fraglen_cdf, (size_t)XB_MAX_FRAG_LEN));
     A(xb->d_efflens.alloc(ctx, (size_t)n)); A(d_counts.alloc(ctx, (size_t)m + 1)); A(d_off.alloc(ctx, (size_t)m + 2)); A(d_rowid.alloc(ctx, (size_t)m + 2));
     if (s != POLEE_OK) {
@@ -788,12 +944,33 @@ static polee_status polee_xbuild_run_impl(polee_ctx *ctx, const polee_xb_transcr
             return s;
         }
     }
-    XbView v{n, d_tseq.p, d_tstrand.p, d_eptr.p, d_ef.p, d_el.p, d_ord.p, d_ofirst.p, d_omax.p, d_seqptr.p, num_seq, m, d_fseq.p, d_fstrand.p,
-             d_m1l.p, d_m1r.p, d_m2l.p, d_m2r.p, d_flag16.p, d_c1.p, d_c2.p, d_cigop.p, d_ciglen.p, d_pmf.p, d_cdf.p, M->fraglen_median,
-             M->strand_specificity, M->alt_frag_model, xb->d_efflens.p,
-             B ? d_tsp.p : nullptr, B ? d_tsq.p : nullptr, B ? B->seqbias_len : 0, B ? B->ps_ctx : 0, d_ol.p, d_or.p, d_psl.p, d_psr.p,
-             B ? B->gc_nbins : 0, d_gcb.p, B ? B->pos_p : 0.0, B && B->pos_terms ? d_pterms.p : nullptr, B ? B->num_fraglens : 0, d_hpf.p,
-             d_m1rev.p, xb->d_left_bias.p, xb->d_right_bias.p};
+    XbView v{};
+    in.fill(v);
+    v.pmf = d_pmf.p;
+    v.cdf = d_cdf.p;
+    v.fraglen_median = M->fraglen_median;
+    v.strand_specificity = M->strand_specificity;
+    v.alt_frag_model = M->alt_frag_model;
+    v.efflens = xb->d_efflens.p;
+    if (B) {
+        v.tseq_ptr = d_tsp.p;
+        v.tseq = d_tsq.p;
+        v.seqbias_len = B->seqbias_len;
+        v.ps_ctx = B->ps_ctx;
+        v.orders_left = d_ol.p;
+        v.orders_right = d_or.p;
+        v.ps_left = d_psl.p;
+        v.ps_right = d_psr.p;
+        v.gc_nbins = B->gc_nbins;
+        v.gc_bins = d_gcb.p;
+        v.pos_p = B->pos_p;
+        v.pos_terms = B->pos_terms ? d_pterms.p : nullptr;
+        v.num_fraglens = B->num_fraglens;
+        v.high_prob_fraglens = d_hpf.p;
+        v.m1_reverse = d_m1rev.p;
+        v.left_bias = xb->d_left_bias.p;
+        v.right_bias = xb->d_right_bias.p;
+    }
     hipStream_t st = ctx->stream;
     auto timed = [&](double &ms, auto &&launch) -> polee_status {
         (void)hipEventRecord(ctx->ev0, st);
@@ -898,6 +1075,91 @@ polee_status polee_xbuild_get(const polee_xbuild *xb, uint64_t *tcolptr, uint32_
         if (tnzval) POLEE_TRY(xb->d_vals.download(ctx, tnzval, (size_t)xb->nnz));
         if (effective_lengths) POLEE_TRY(xb->d_efflens.download(ctx, effective_lengths, (size_t)xb->n));
         if (row_fragment) POLEE_TRY(xb->d_row_fragment.download(ctx, row_fragment, (size_t)xb->rows));
+        return POLEE_OK;
+    });
+}
+
+polee_status polee_fragmodel_estimate(polee_ctx *ctx, const polee_xb_transcripts *T, const polee_xb_fragments *F, int64_t *counts, int64_t *hist,
+                                      int64_t *min_fraglen)
+{
+    return ctx_entry(ctx, "polee_fragmodel_estimate", [&]() -> polee_status {
+        if (!T || !F || !counts || !hist) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_fragmodel_estimate: null argument");
+        XbInputs in;
+        POLEE_TRY(in.load(ctx, "polee_fragmodel_estimate", T, F));
+        DevBuf<int64_t> d_acc, d_min;  // counts [4], then hist [2000]
+        POLEE_TRY(d_acc.alloc(ctx, 4 + (size_t)XB_MAX_FRAG_LEN));
+        if (min_fraglen) POLEE_TRY(d_min.alloc(ctx, (size_t)in.m));
+        POLEE_HIP_TRY(ctx, hipMemsetAsync(d_acc.p, 0, (4 + (size_t)XB_MAX_FRAG_LEN) * sizeof(int64_t), ctx->stream));
+        XbView v{};
+        in.fill(v);
+        if (in.m > 0) {
+            hipLaunchKernelGGL(fm_estimate_kernel, dim3((unsigned)ceil_div(in.m, FM_T)), dim3(FM_T), 0, ctx->stream, v, (unsigned long long *)d_acc.p,
+                               (unsigned long long *)d_acc.p + 4, d_min.p);
+            POLEE_KERNEL_CHECK(ctx);
+        }
+        POLEE_TRY(d_acc.download(ctx, counts, 4));
+        POLEE_HIP_TRY(ctx, hipMemcpyAsync(hist, d_acc.p + 4, (size_t)XB_MAX_FRAG_LEN * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        POLEE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (min_fraglen) POLEE_TRY(d_min.download(ctx, min_fraglen, (size_t)in.m));
+        return POLEE_OK;
+    });
+}
+
+polee_status polee_read_assign(polee_ctx *ctx, const polee_xbuild *xb, const polee_xb_transcripts *T, const polee_xb_fragments *F, const int64_t *tseq_ptr,
+                               const uint8_t *m1_reverse, const float *xs, uint64_t seed, int32_t mode, int32_t fallback_fraglen, int32_t *transcript,
+                               int64_t *tpos, int32_t *fraglen, uint8_t *flags)
+{
+    return ctx_entry(ctx, "polee_read_assign", [&]() -> polee_status {
+        if (!xb || !T || !F || !tseq_ptr || !transcript || !tpos || !fraglen || !flags)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_read_assign: null argument");
+        if (mode != 0 && mode != 1) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_read_assign: mode %d (0: the draw, 1: the last entry)", mode);
+        if (mode == 0 && !xs) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_read_assign: the draw needs xs");
+        if (xb->ctx != ctx) return fail(ctx, POLEE_ERR_BAD_ARG, "polee_read_assign: the matrix belongs to another context");
+        if (xb->n != T->n || xb->m != F->m)
+            return fail(ctx, POLEE_ERR_BAD_ARG, "polee_read_assign: the matrix was built from %d transcripts and %lld fragments, not %d and %lld", xb->n,
+                        (long long)xb->m, T->n, (long long)F->m);
+        XbInputs in;
+        POLEE_TRY(in.load(ctx, "polee_read_assign", T, F));
+        const int32_t n = in.n;
+        const int64_t m = in.m, rows = xb->rows;
+        if (tseq_ptr[0] != 0) return fail(ctx, POLEE_ERR_BAD_ARG, "tseq_ptr[0] must be 0");
+        for (int32_t j = 0; j < n; ++j) {
+            int64_t ex = 0;
+            for (int64_t k = T->exon_ptr[j]; k < T->exon_ptr[j + 1]; ++k) ex += T->exon_last[k] - T->exon_first[k] + 1;
+            if (tseq_ptr[j + 1] - tseq_ptr[j] != ex)
+                return fail(ctx, POLEE_ERR_BAD_ARG, "transcript %d: sequence of %lld bases, exons of %lld", j, (long long)(tseq_ptr[j + 1] - tseq_ptr[j]), (long long)ex);
+        }
+        std::vector<uint8_t> rev_zero;
+        const uint8_t *rev = m1_reverse;
+        if (!rev) {
+            for (int64_t i = 0; i < m; ++i)
+                if (F->m2_left[i] == 0) return fail(ctx, POLEE_ERR_BAD_ARG, "single-end fragments need m1_reverse (transcripts.jl:486)");
+            rev_zero.assign((size_t)std::max<int64_t>(m, 1), 0);  // (every fragment is paired: never read)
+            rev = rev_zero.data();
+        }
+        if (rows == 0) return POLEE_OK;
+        DevBuf<int64_t> d_tsp, d_tpos;
+        DevBuf<uint8_t> d_rev, d_flags;
+        DevBuf<float> d_xs;
+        DevBuf<int32_t> d_tr, d_fl;
+        POLEE_TRY(d_tsp.upload(ctx, tseq_ptr, (size_t)n + 1));
+        POLEE_TRY(d_rev.upload(ctx, rev, (size_t)std::max<int64_t>(m, 1)));
+        if (mode == 0) POLEE_TRY(d_xs.upload(ctx, xs, (size_t)n));
+        POLEE_TRY(d_tr.alloc(ctx, (size_t)rows));
+        POLEE_TRY(d_tpos.alloc(ctx, (size_t)rows));
+        POLEE_TRY(d_fl.alloc(ctx, (size_t)rows));
+        POLEE_TRY(d_flags.alloc(ctx, (size_t)rows));
+        XbView v{};
+        in.fill(v);
+        v.m1_reverse = d_rev.p;
+        hipLaunchKernelGGL(fm_assign_kernel, dim3((unsigned)ceil_div(rows, FM_T)), dim3(FM_T), 0, ctx->stream, v, rows, (const uint64_t *)xb->d_tcolptr.p,
+                           (const uint32_t *)xb->d_cols.p, (const float *)xb->d_vals.p, (const int64_t *)xb->d_row_fragment.p, (const int64_t *)d_tsp.p,
+                           (const float *)d_xs.p, seed, mode, fallback_fraglen, d_tr.p, d_tpos.p, d_fl.p, d_flags.p);
+        POLEE_KERNEL_CHECK(ctx);
+        POLEE_TRY(d_tr.download(ctx, transcript, (size_t)rows));
+        POLEE_TRY(d_tpos.download(ctx, tpos, (size_t)rows));
+        POLEE_TRY(d_fl.download(ctx, fraglen, (size_t)rows));
+        POLEE_TRY(d_flags.download(ctx, flags, (size_t)rows));
         return POLEE_OK;
     });
 }

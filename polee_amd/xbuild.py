@@ -63,8 +63,16 @@ _F_TYPES = dict(seq=np.int32, strand=np.int8, m1_left=np.int64, m1_right=np.int6
                 m1_is_flag16=np.uint8, cig1_ptr=np.int64, cig2_ptr=np.int64, cig_op=np.uint8, cig_len=np.int32)
 
 
-def pack(transcripts, fragments, fraglen_pmf, fraglen_cdf, fraglen_median, strand_specificity, alt_frag_model):
-    """ctypes structs (+ the arrays they borrow) for polee_xbuild_run and for the oracle's twin of it."""
+class XBuild(L.Handle):
+    """Owner of a polee_xbuild handle: the rows of X on the device (build_likelihood_matrix(return_xbuild=True))."""
+    _destroy = "polee_xbuild_destroy"
+
+    def __init__(self, h, ctx):
+        self._h, self.ctx = h, ctx
+
+
+def pack_tf(transcripts, fragments):
+    """ctypes structs (+ the arrays they borrow) of the transcripts and the fragments alone"""
     keep = []
 
     def ptr(a, dt):
@@ -73,6 +81,17 @@ def pack(transcripts, fragments, fraglen_pmf, fraglen_cdf, fraglen_median, stran
         return a.ctypes.data_as(C.c_void_p)
     T = _Transcripts(int(transcripts["n"]), *[ptr(transcripts[k], dt) for k, dt in _T_TYPES.items()])
     F = _Fragments(int(fragments["m"]), *[ptr(fragments[k], dt) for k, dt in _F_TYPES.items()])
+    return T, F, keep
+
+
+def pack(transcripts, fragments, fraglen_pmf, fraglen_cdf, fraglen_median, strand_specificity, alt_frag_model):
+    """ctypes structs (+ the arrays they borrow) for polee_xbuild_run and for the oracle's twin of it."""
+    T, F, keep = pack_tf(transcripts, fragments)
+
+    def ptr(a, dt):
+        a = np.ascontiguousarray(a, dt)
+        keep.append(a)
+        return a.ctypes.data_as(C.c_void_p)
     M = _FragModel(ptr(fraglen_pmf, np.float32), ptr(fraglen_cdf, np.float32), int(fraglen_median), float(strand_specificity),
                    int(bool(alt_frag_model)))
     return T, F, M, keep
@@ -109,14 +128,16 @@ def order_mates(fragments):
 
 
 def build_likelihood_matrix(transcripts, fragments, fraglen_pmf, fraglen_cdf, fraglen_median, strand_specificity=0.9,
-                            alt_frag_model=False, ctx=None, bias=None, return_bias=False, return_sample=False, return_tree=False):
+                            alt_frag_model=False, ctx=None, bias=None, return_bias=False, return_sample=False, return_tree=False,
+                            return_xbuild=False):
     """-> dict(m, n, nnz, tcolptr u64 [m+1], trowval u32, tnzval f32 (the rows of X, 1-based, what RNASeqSample(xt=...)
     takes), effective_lengths f32 [n], row_fragment i64 [m], kernel_ms).  The mates of a pair may come in any order
     (order_mates).  bias: a trained bias model (pack_bias) -> the reference's default BiasedFragModel
     (src/fragmodel.jl:174-445) instead of the SimplisticFragModel; return_bias adds left_bias / right_bias (the
     transcripts' bias vectors, compute_transcript_bias!).  return_sample adds "sample": the RNASeqSample made straight from the
     result on the device (polee_loglik_create_from_xbuild: X never visits the host on its way into the likelihood); return_tree adds
-    "node_parent_idxs" / "node_js": the clustering tree of the rounds variant, built from the same result on the device."""
+    "node_parent_idxs" / "node_js": the clustering tree of the rounds variant, built from the same result on the device;
+    return_xbuild adds "xbuild": the result itself, still on the device (XBuild; what fragmodel.assign_reads reads)."""
     from .core import default_context
     ctx = ctx or default_context()
     fragments = order_mates(fragments)
@@ -129,6 +150,7 @@ def build_likelihood_matrix(transcripts, fragments, fraglen_pmf, fraglen_cdf, fr
         check(L.lib().polee_xbuild_run_biased(ctx._h, C.byref(T), C.byref(F), C.byref(M), C.byref(Bs), C.byref(h)), ctx._h)
     else:
         check(L.lib().polee_xbuild_run(ctx._h, C.byref(T), C.byref(F), C.byref(M), C.byref(h)), ctx._h)
+    xbh = XBuild(h, ctx)
     try:
         rows, nnz = C.c_int64(), C.c_int64()
         ms = [C.c_double(), C.c_double(), C.c_double()]
@@ -154,7 +176,10 @@ def build_likelihood_matrix(transcripts, fragments, fraglen_pmf, fraglen_cdf, fr
             msb = C.c_double()
             check(L.lib().polee_xbuild_get_bias(h, p(out["left_bias"]), p(out["right_bias"]), C.byref(msb)), ctx._h)
             out["kernel_ms"]["bias"] = msb.value
+        if return_xbuild:
+            out["xbuild"], xbh = xbh, None
     finally:
-        L.lib().polee_xbuild_destroy(h)
+        if xbh is not None:
+            xbh.close()
     del keep
     return out
