@@ -1213,6 +1213,36 @@ polee_status polee_bias_train_get_trace(polee_bias_train *bt, int32_t side, int3
 polee_status polee_bias_train_candidates(polee_bias_train *bt, int32_t side, const int32_t *orders_in, double *losses_out,
                                          double *loss0_out);
 
+/* ---- Splicing features from the transcripts' exon structure (splice_features.hip, host twin splice_features_host.cpp):
+ * splicing_features (src/splicing.jl:98-230) over get_introns, get_cassette_exons, get_alt_donor_acceptor_sites and get_alt_fp_tp_ends
+ * (src/transcripts.jl:545-950), restated as written.  transcripts: as polee_xbuild_run takes them, every transcript with at least one
+ * exon, exons ascending and disjoint; transcript ids in the result are 1-based positions.  gene_of_or_null: i32 [n], the 1-based gene of
+ * every transcript; with it the alternative 5' / 3' ends are made too (alt_ends = true), without it they are left out.
+ * COORDINATE RANGE: 1 <= first <= last <= 2^31 - 2 (keys carry first - 1 and last + 1 in 32 bits); anything outside, fewer than one
+ * exon, a negative sequence id, a strand outside -1 .. +1 or a gene number below 1 is refused with POLEE_ERR_BAD_ARG.
+ * The result, F features in the blocks cassette_exon, mutex_exon, alt_acceptor_site / alt_donor_site (one block), retained_intron, alt_5p_end,
+ * alt_3p_end; within a block ascending by (seq, strand, included_first, included_last, excluded_first, excluded_last) -- mutex exons with
+ * equal unions by their outer interval -- and the alternative ends by (gene, start clusters before end clusters, cluster start): the project's
+ * own order (upstream's is that of its interval collections and Dicts).
+ *   type i32 [F]       0 cassette_exon, 1 mutex_exon, 2 alt_acceptor_site, 3 alt_donor_site, 4 retained_intron, 5 alt_5p_end, 6 alt_3p_end
+ *   seq i32 [F], strand i8 [F]; coords i64 [F][4] = included_first, included_last, excluded_first, excluded_last (-1 where the
+ *   reference's table holds -1); end_span i64 [F][2] = (min_first, max_last) of an alternative end's gene as upstream computes them
+ *   (max_last is the MINIMUM of the ends, transcripts.jl:884), -1 elsewhere
+ *   included_ptr / excluded_ptr i64 [F+1], 0-based into included_idx / excluded_idx i32: the transcripts, ascending and unique
+ * polee_splice_run works on the device and is the same from run to run; polee_splice_run_host builds the same arrays element for
+ * element on POLEE_HOST_THREADS without a GPU.  POLEE_ERR_UNSUPPORTED from the device path when the member rows before repeats are
+ * dropped number 2^32 or more.  POLEE_BUILD_TIMING=1: the phases on stderr. */
+typedef struct polee_splice polee_splice;
+polee_status polee_splice_run(polee_ctx *ctx, const polee_xb_transcripts *transcripts, const int32_t *gene_of_or_null, polee_splice **out);
+polee_status polee_splice_run_host(const polee_xb_transcripts *transcripts, const int32_t *gene_of_or_null, polee_splice **out);
+void polee_splice_destroy(polee_splice *sf);
+/* each pointer may be NULL; num_overlapping_pairs: unordered pairs of overlapping internal exons of one sequence and strand */
+polee_status polee_splice_sizes(const polee_splice *sf, int64_t *num_features, int64_t *num_included, int64_t *num_excluded, int64_t *num_exons,
+                                int64_t *num_internal_exons, int64_t *num_overlapping_pairs);
+/* copies the result to host arrays (any pointer may be NULL) */
+polee_status polee_splice_get(const polee_splice *sf, int32_t *type, int32_t *seq, int8_t *strand, int64_t *coords, int64_t *end_span,
+                              int64_t *included_ptr, int32_t *included_idx, int64_t *excluded_ptr, int32_t *excluded_idx);
+
 #ifdef __cplusplus
 }
 #endif

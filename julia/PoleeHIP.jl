@@ -1966,4 +1966,51 @@ function bias_candidates(bt::BiasTrainer, side::Integer, orders::Vector{Int32})
     return losses, loss0[]
 end
 
+const SPLICE_TYPE_NAMES = ["cassette_exon", "mutex_exon", "alt_acceptor_site", "alt_donor_site", "retained_intron", "alt_5p_end", "alt_3p_end"]
+"""
+    splicing_features(T; gene_of=nothing, ctx=nothing)
+
+splicing_features (src/splicing.jl:98-230) from the exon structure (polee_splice_run; ctx = nothing: polee_splice_run_host, the same
+arrays from the host threads).  T: NamedTuple (seq, strand, exon_ptr, exon_first, exon_last) in the layout of polee_xb_transcripts;
+gene_of: Int32 [n], 1-based, for the alternative ends (alt_ends = true).  Returns (num_features, type (0-based index into
+SPLICE_TYPE_NAMES), seq, strand, coords Int64 [4, F], end_span Int64 [2, F], included_ptr, included_idx, excluded_ptr, excluded_idx,
+feature_idxs, feature_transcript_idxs, antifeature_idxs, antifeature_transcript_idxs); the order is this project's own (DESIGN.md 3.19).
+"""
+function splicing_features(T; gene_of::Union{Nothing,Vector{Int32}}=nothing, ctx::Union{Nothing,Context}=nothing)
+    n = Int32(length(T.seq))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    ch = ctx === nothing ? C_NULL : ctx.h
+    g = gene_of === nothing ? Int32[] : gene_of
+    GC.@preserve T g begin
+        ts = XbTranscripts(n, pointer(T.seq), pointer(T.strand), pointer(T.exon_ptr), pointer(T.exon_first), pointer(T.exon_last))
+        gp = gene_of === nothing ? Ptr{Int32}(C_NULL) : pointer(g)
+        if ctx === nothing
+            check(ccall((:polee_splice_run_host, LIB), Cint, (Ref{XbTranscripts}, Ptr{Int32}, Ref{Ptr{Cvoid}}), ts, gp, out))
+        else
+            check(ccall((:polee_splice_run, LIB), Cint, (Ptr{Cvoid}, Ref{XbTranscripts}, Ptr{Int32}, Ref{Ptr{Cvoid}}), ch, ts, gp, out), ch)
+        end
+    end
+    h = out[]
+    try
+        F, ni, ne = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:polee_splice_sizes, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                    h, F, ni, ne, C_NULL, C_NULL, C_NULL))
+        typ, seq, strand = Vector{Int32}(undef, F[]), Vector{Int32}(undef, F[]), Vector{Int8}(undef, F[])
+        coords, span = Matrix{Int64}(undef, 4, F[]), Matrix{Int64}(undef, 2, F[])
+        iptr, eptr = Vector{Int64}(undef, F[] + 1), Vector{Int64}(undef, F[] + 1)
+        iidx, eidx = Vector{Int32}(undef, ni[]), Vector{Int32}(undef, ne[])
+        GC.@preserve typ seq strand coords span iptr eptr iidx eidx check(
+            ccall((:polee_splice_get, LIB), Cint,
+                  (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int8}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+                  h, typ, seq, strand, coords, span, iptr, iidx, eptr, eidx))
+        fidx = Int32[f for f in 1:F[] for _ in iptr[f]+1:iptr[f+1]]
+        aidx = Int32[f for f in 1:F[] for _ in eptr[f]+1:eptr[f+1]]
+        return (num_features=F[], type=typ, seq=seq, strand=strand, coords=coords, end_span=span, included_ptr=iptr, included_idx=iidx,
+                excluded_ptr=eptr, excluded_idx=eidx, feature_idxs=fidx, feature_transcript_idxs=iidx, antifeature_idxs=aidx,
+                antifeature_transcript_idxs=eidx)
+    finally
+        ccall((:polee_splice_destroy, LIB), Cvoid, (Ptr{Cvoid},), h)
+    end
+end
+
 end # module

@@ -108,7 +108,7 @@ def lib():
                      "polee_approx_destroy", "polee_debug_psell_free", "polee_comm_destroy", "polee_devx_destroy",
                      "polee_gibbs_destroy", "polee_em_destroy", "polee_altvi_destroy", "polee_bias_train_destroy",
                      "polee_regression_destroy", "polee_effects_destroy", "polee_sampler_destroy", "polee_classify_destroy",
-                     "polee_tsne_destroy", "polee_forest_destroy", "polee_xbuild_destroy"):
+                     "polee_tsne_destroy", "polee_forest_destroy", "polee_xbuild_destroy", "polee_splice_destroy"):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         L.polee_vi_default_opts.restype = None
@@ -152,6 +152,11 @@ def lib():
         L.polee_fragmodel_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, i64p, i64p, i64p]
         L.polee_read_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64p, u8p, f32p, C.c_uint64, C.c_int32, C.c_int32,
                                         i32p, i64p, i32p, u8p]
+        # splicing features from the exon structure (polee_amd/splicing.py)
+        L.polee_splice_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.polee_splice_run_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.polee_splice_sizes.argtypes = [C.c_void_p] + [i64p] * 6
+        L.polee_splice_get.argtypes = [C.c_void_p] * 10
         _lib = L
     return _lib
 

@@ -725,13 +725,27 @@ polee_status polee_approx_sample(polee_approx *ap, const float *z0, uint64_t see
 }
 
 // ---- feature (gene) expression approximated by a normal, from sampler draws (polee_gene_expression.py:157-222)
-__global__ void feature_sum_kernel(const int32_t *fidx, const int32_t *tidx, int64_t P, int n, int F, const float *x,
-                                   float *fx)
+// fx[s][f] = the sum of x[s][t] over the transcripts t of feature f, added one after the other in the pairs' order (the reference's
+// loop): the pairs come grouped by feature, ptr [F + 1] into tidx.  One thread per (sample, feature): no atomics, so the moments are the
+// same from call to call
+__global__ void feature_sum_kernel(const int64_t *ptr, const int32_t *tidx, int n, int F, const float *x, float *fx)
 {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int s = blockIdx.y;
-    if (p >= P) return;
-    atomicAdd(&fx[(size_t)s * F + fidx[p]], x[(size_t)s * n + tidx[p]]);
+    if (f >= F) return;
+    float a = 0.0f;
+    for (int64_t p = ptr[f]; p < ptr[f + 1]; ++p) a += x[(size_t)s * n + tidx[p]];
+    fx[(size_t)s * F + f] = a;
+}
+// pairs (feature, transcript) grouped by feature, the order within a feature kept
+static void group_pairs(const std::vector<int32_t> &fi, const std::vector<int32_t> &ti, int32_t F, std::vector<int64_t> &ptr, std::vector<int32_t> &grouped)
+{
+    ptr.assign((size_t)F + 1, 0);
+    for (int32_t f : fi) ++ptr[(size_t)f + 1];
+    for (int32_t f = 0; f < F; ++f) ptr[(size_t)f + 1] += ptr[(size_t)f];
+    std::vector<int64_t> at(ptr.begin(), ptr.end() - 1);
+    grouped.resize(fi.size());
+    for (size_t p = 0; p < fi.size(); ++p) grouped[(size_t)at[(size_t)fi[p]]++] = ti[p];
 }
 // mode 0: acc += log fx;  mode 1: acc += (loc - log fx)^2;  fx is reset for the next draw
 __global__ void feature_accum_kernel(int64_t SF, float *fx, float *afx, const float *loc, double *acc, int mode)
@@ -768,12 +782,16 @@ static polee_status feature_moments_impl(polee_approx *ap, const std::vector<int
     polee_ctx *ctx = ap->ctx;
     const int S = ap->S, n = ap->n;
     const bool anti = !afi.empty();
-    DevBuf<int32_t> d_fi, d_ti, d_afi, d_ati;
+    DevBuf<int64_t> d_fi, d_afi;  // (the features' ranges in d_ti / d_ati)
+    DevBuf<int32_t> d_ti, d_ati;
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> grouped;
     DevBuf<float> d_fx, d_afx, d_loc, d_out;
     DevBuf<double> d_acc;
     const size_t SF = (size_t)S * F, sk = (size_t)S * (n - 1);
-    POLEE_TRY(d_fi.upload(ctx, fi));
-    POLEE_TRY(d_ti.upload(ctx, ti));
+    group_pairs(fi, ti, F, ptr, grouped);
+    POLEE_TRY(d_fi.upload(ctx, ptr));
+    POLEE_TRY(d_ti.upload(ctx, grouped));
     POLEE_TRY(d_fx.alloc(ctx, SF));
     POLEE_TRY(d_loc.alloc(ctx, SF));
     POLEE_TRY(d_out.alloc(ctx, SF));
@@ -781,25 +799,21 @@ static polee_status feature_moments_impl(polee_approx *ap, const std::vector<int
     POLEE_HIP_TRY(ctx, hipMemsetAsync(d_fx.p, 0, SF * sizeof(float), ctx->stream));
     POLEE_HIP_TRY(ctx, hipMemsetAsync(d_acc.p, 0, SF * sizeof(double), ctx->stream));
     if (anti) {
-        POLEE_TRY(d_afi.upload(ctx, afi));
-        POLEE_TRY(d_ati.upload(ctx, ati));
+        group_pairs(afi, ati, F, ptr, grouped);
+        POLEE_TRY(d_afi.upload(ctx, ptr));
+        POLEE_TRY(d_ati.upload(ctx, grouped));
         POLEE_TRY(d_afx.alloc(ctx, SF));
         POLEE_HIP_TRY(ctx, hipMemsetAsync(d_afx.p, 0, SF * sizeof(float), ctx->stream));
     }
-    const int64_t P = (int64_t)fi.size(), Q = (int64_t)afi.size();
-    const dim3 gp((unsigned)ceil_div(P, 256), (unsigned)S), gq((unsigned)ceil_div(std::max<int64_t>(Q, 1), 256), (unsigned)S),
-        gf((unsigned)ceil_div((int64_t)SF, 256));
+    const dim3 gp((unsigned)ceil_div((int64_t)F, 256), (unsigned)S), gf((unsigned)ceil_div((int64_t)SF, 256));
     int64_t draw = 0;
     for (int mode = 0; mode < 2; ++mode) {
         const int nd = mode == 0 ? num_mean_draws : num_var_draws;
         for (int d = 0; d < nd; ++d, ++draw) {
             if (z0) POLEE_TRY(ap->d_z0.upload(ctx, z0 + (size_t)draw * sk, sk));
             POLEE_TRY(approx_sample_device(ap, z0 ? ap->d_z0.p : nullptr, seed + POLEE_DRAW_STRIDE * (uint64_t)draw));
-            hipLaunchKernelGGL(feature_sum_kernel, gp, dim3(256), 0, ctx->stream, d_fi.p, d_ti.p, P, n, F, ap->d_x.p,
-                               d_fx.p);
-            if (anti)
-                hipLaunchKernelGGL(feature_sum_kernel, gq, dim3(256), 0, ctx->stream, d_afi.p, d_ati.p, Q, n, F,
-                                   ap->d_x.p, d_afx.p);
+            hipLaunchKernelGGL(feature_sum_kernel, gp, dim3(256), 0, ctx->stream, d_fi.p, d_ti.p, n, F, ap->d_x.p, d_fx.p);
+            if (anti) hipLaunchKernelGGL(feature_sum_kernel, gp, dim3(256), 0, ctx->stream, d_afi.p, d_ati.p, n, F, ap->d_x.p, d_afx.p);
             hipLaunchKernelGGL(feature_accum_kernel, gf, dim3(256), 0, ctx->stream, (int64_t)SF, d_fx.p,
                                anti ? d_afx.p : nullptr, d_loc.p, d_acc.p, mode);
         }
